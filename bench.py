@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — ICP iterations/s on MI355X (BASELINE.json metric, config C4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points N] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points N] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-cow] [--no-cases] [--no-registration] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the result line (the headline and what the timed steps' own
+counters give).  --full adds every other measurement described below, each in runs of its own
+after the timed region: steady_state, step_phases, registration, the bundle filter's executed
+work, streaming, cow_frame_rate, reference_cases, baseline_configs, csv_io, grid_nn,
+full_nxm_filter and cpu_baseline.
 
 Workload (BASELINE.json configs[3]): synthetic 2^20-point model uniform in
 [-1,1]^3 (mt19937_64 seed 42), scene = R(5 deg about (1,2,3)) model + (0.05,-0.03,0.02),
@@ -520,6 +528,33 @@ def registration(ctx, m, p_local, n_total, iters=30, reps=3, device=None):
                           "(slot order, grid seeds, unseeded search); seeded = the rest of the run per iteration"}
 
 
+DUMP_MAX_ROWS = 1 << 20  # --dump-outputs: 32 B a row (+ 8 B a sampled row's number), under 64 MB in all
+
+
+def dump_outputs(ctx, res, errs, out_dir, rank, world):
+    """--dump-outputs: what the last timed registration gave its caller, as float64 <name>.npy
+    (<name>_rank<r>.npy for each rank's shard of a multi-rank run): `transform` (s, R row-major, t:
+    13 values), `result` (iterations, converged, err), `err_trace` (the error of every iteration),
+    `scene` (the registered scene, icp_get_scene, n x 3) and `correspondences` (icp_get_indices).
+    A shard of more than DUMP_MAX_ROWS points is written as a fixed sample of that many rows (seed 0,
+    ascending; their numbers in `sample_rows`).  Both reads leave the registration's state as it is."""
+    scene = ctx.get_scene()
+    idx = ctx.get_indices()
+    arrays = {"transform": np.concatenate(([res.s], list(res.R), list(res.t))),
+              "result": np.array([res.iterations, res.converged, res.err]),
+              "err_trace": errs}
+    if scene.shape[0] > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(scene.shape[0], size=DUMP_MAX_ROWS, replace=False))
+        scene, idx = scene[rows], idx[rows]
+        arrays["sample_rows"] = rows
+    arrays["scene"] = scene
+    arrays["correspondences"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def cow_frame_rate(device, reps=20):
     """Reference headline: opti_gpu_loop frame_rate = complete cow registrations/s."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -549,11 +584,19 @@ def main():
     ap.add_argument("--points", "--n", dest="n", type=int, default=1 << 20)
     ap.add_argument("--nn", choices=["certified", "fp64"], default="certified")
     ap.add_argument("--variant", choices=["auto", "valu", "mfma", "mfma16", "grid", "bundle"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cow", action="store_true")
-    ap.add_argument("--no-cases", action="store_true", help="skip the reference's 14 benchmark cases")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (steady state, "
+                         "step phases, registration, rooflines' own runs, cow, reference cases, baseline "
+                         "configurations, CPU baseline); the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cow", action="store_true", help="with --full: skip the cow frame rate")
+    ap.add_argument("--no-cases", action="store_true",
+                    help="with --full: skip the reference's 14 benchmark cases")
     ap.add_argument("--no-registration", dest="registration", action="store_false",
-                    help="skip the registration block (SURVEY §8d: set_model through the last iteration)")
+                    help="with --full: skip the registration block (SURVEY §8d: set_model through the last "
+                         "iteration)")
     ap.add_argument("--rccl", action="store_true",
                     help="N=1: route the per-iteration sums through a 1-rank RCCL communicator, as N>1 does")
     args = ap.parse_args()
@@ -633,13 +676,17 @@ def main():
     dt = time.perf_counter() - t0
     dt_local = dt
     st = ctx.stats()
-    # the steady-state rate beside it: the last registration continued (seeded iterations only)
-    ctx.run(3, -1.0)
-    barrier_sync()
-    t1 = time.perf_counter()
-    ctx.run(STEADY_ITERS, -1.0)
-    barrier_sync()
-    dt_ss = time.perf_counter() - t1
+    if args.dump_outputs:
+        dump_outputs(ctx, res, errs, args.dump_outputs, rank, world)
+    dt_ss = 0.0
+    if args.full:
+        # the steady-state rate beside it: the last registration continued (seeded iterations only)
+        ctx.run(3, -1.0)
+        barrier_sync()
+        t1 = time.perf_counter()
+        ctx.run(STEADY_ITERS, -1.0)
+        barrier_sync()
+        dt_ss = time.perf_counter() - t1
     if dist is not None:
         t = torch.tensor([dt, dt_ss], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -652,7 +699,7 @@ def main():
     nn_avg_ms = st["nn_ms"] / max(st["nn_launches"], 1)
     ar_ms = st["allreduce_ms"] / st["allreduce_calls"] if st["allreduce_calls"] else None
     work = None
-    if level1 == "bundle":
+    if args.full and level1 == "bundle":
         # untimed, after the timed region, on every rank (icp_run all-reduces): the bundle
         # filter's executed work per search from its device counters, over a few more seeded
         # iterations of the same registration
@@ -665,9 +712,12 @@ def main():
     # SURVEY §8d's clock: whole registrations from the model upload (every rank: icp_run
     # all-reduces), untimed by the headline
     progress("timed iterations done")
-    reg = registration(ctx, m, p[b:b + c], args.n, iters=REGISTRATION_ITERS) if args.registration else None
-    # the headline step's phases (device-resident clouds), untimed by the headline
-    reg_dev = registration(ctx, m, p[b:b + c], args.n, iters=REGISTRATION_ITERS, device=(dm, dps))
+    reg = reg_dev = None
+    if args.full and args.registration:
+        reg = registration(ctx, m, p[b:b + c], args.n, iters=REGISTRATION_ITERS)
+    if args.full:
+        # the headline step's phases (device-resident clouds), untimed by the headline
+        reg_dev = registration(ctx, m, p[b:b + c], args.n, iters=REGISTRATION_ITERS, device=(dm, dps))
     # what a timed step ran: one more registration's counters (the searches by kind, the fused
     # iterations' certified / walked queries), for the line's dtype
     ctx.reset_stats()
@@ -737,10 +787,6 @@ def main():
                     "copy of the clouds (value_pcie_inclusive: the same registration from host arrays)",
             "iterations_per_step": REGISTRATION_ITERS,
             "ms_per_iteration": dt * 1e3 / its,
-            "steady_state": {"iterations_per_s": STEADY_ITERS / dt_ss, "ms_per_iteration": dt_ss * 1e3 / STEADY_ITERS,
-                             "iterations": STEADY_ITERS,
-                             "definition": "seeded iterations of the last registration continued (no set_model / "
-                                           "set_scene / unseeded first search): round 4's headline"},
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -772,15 +818,21 @@ def main():
             "fp64_resolved_per_iter": st["ambiguous"] / max(st["iterations"], 1),
             "final_err": float(errs[-1]) if errs.size else None,
         }
-        out["step_phases"] = dict(reg_dev)
+        if args.full:
+            out["steady_state"] = {
+                "iterations_per_s": STEADY_ITERS / dt_ss, "ms_per_iteration": dt_ss * 1e3 / STEADY_ITERS,
+                "iterations": STEADY_ITERS,
+                "definition": "seeded iterations of the last registration continued (no set_model / "
+                              "set_scene / unseeded first search): round 4's headline"}
+            out["step_phases"] = dict(reg_dev)
+            out["step_phases"]["note"] = ("the headline step's phases from device-resident clouds (median of 3 "
+                                          "registrations after the timed region): set_model_device, "
+                                          "set_scene_device, first (unseeded) iteration, seeded iterations")
         out["step_paths"] = {"run_grid_searches": path_st["run_grid_searches"],
                              "run_bundle_searches": path_st["run_bundle_searches"],
                              "run_certified": path_st["run_certified"], "run_walked": path_st["run_walked"],
                              "run_path_bits": hex(path_st["run_path_bits"]),
                              "note": "one registration after the timed region (icp_stats)"}
-        out["step_phases"]["note"] = ("the headline step's phases from device-resident clouds (median of 3 "
-                                      "registrations after the timed region): set_model_device, set_scene_device, "
-                                      "first (unseeded) iteration, seeded iterations")
         if reg is not None:  # (host arrays in: the PCIe copy of both clouds included)
             regs = [r for r in per_rank if r.get("registration_ms")]
             out["registration"] = dict(reg)
@@ -793,15 +845,17 @@ def main():
                                             "set_model_ms_max": max(r["set_model_ms"] for r in regs)})
                 out["registration"]["iterations_per_s_inclusive"] = reg["iterations"] / (worst["registration_ms"] * 1e-3)
             out["value_pcie_inclusive"] = out["registration"]["iterations_per_s_inclusive"]
-        if level1 == "bundle" and nn_s > 0:
+        if work is not None and nn_s > 0:
             out["roofline"].update(bundle_roofline(c, args.n, nn_s, work, v1=bundle_v1()))
+        elif level1 == "bundle":
+            out["roofline"]["note"] = "the bundle filter's executed MFMA work is counted in runs of its own: --full"
         if level1 == "mfma16" and nn_s > 0:
             ex = MFMA16_FLOP_PER_PAIR * pairs / nn_s / 1e12
             out["roofline"]["mfma_pipe"] = {
                 "executed_tflops": ex, "util": ex / PEAK_F16_MFMA_TFLOPS,
                 "note": "v_mfma_f32_32x32x16_f16 executes 32 flop per pair (K = 16, 14 slots used): "
                         "matrix-pipe utilisation, not the roofline fraction"}
-        if args.nn == "certified" and args.variant == "auto" and world == 1 and args.n == 1 << 20:
+        if args.full and args.nn == "certified" and args.variant == "auto" and world == 1 and args.n == 1 << 20:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             try:
                 import roofline as RF
@@ -818,9 +872,9 @@ def main():
         if level1 == "grid":
             out["roofline"] = grid_roofline(c, args.n, nn_avg_ms, traffic, traffic_src, args.variant == "grid")
             out["dtype"] = "f64 (" + path_description(path_st) + ")"
-        if world == 1 and not args.no_cow:
+        if args.full and world == 1 and not args.no_cow:
             out["cow_frame_rate"] = cow_frame_rate(local)
-        if world == 1 and not args.no_cases:
+        if args.full and world == 1 and not args.no_cases:
             out["reference_cases"] = reference_cases_gpu()
             out["baseline_configs"] = baseline_configs(local)
             out["csv_io"] = csv_io(m)
@@ -828,7 +882,7 @@ def main():
                 out["grid_nn"] = grid_nn_rate(local, m, p, args.steps)
             if level1 == "bundle":
                 out["full_nxm_filter"] = full_nxm_rate(local, m, p)
-        if not args.no_cpu_baseline:  # rank 0 at every N: the same host-side baseline
+        if args.full and not args.no_cpu_baseline:  # rank 0 at every N: the same host-side baseline
             out["cpu_baseline"] = cpu_baseline(m, p)
             if not args.no_cases:
                 out["cpu_baseline"]["reference_cases_cpu"] = reference_cases_cpu()

@@ -55,6 +55,18 @@ def run_config(name):
     return name, m.shape[0], p.shape[0], r, int((idx_sqrt != r["idx0"]).sum())
 
 
+def savez_lzma(path, **arrays):
+    """np.savez with LZMA members: np.load reads it like any .npz, and the horse pair's 1.16 MB
+    of fp64 coordinates stays under the 1 MiB a committed file may have (deflate leaves 1.1 MB)."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(a), allow_pickle=False)
+            z.writestr(name + ".npy", buf.getvalue())
+
+
 def summary(new_p):
     return dict(sum=new_p.sum(axis=0).tolist(), abs_sum=float(np.abs(new_p).sum()),
                 head=new_p[:8].tolist(), tail=new_p[-8:].tolist())
@@ -70,8 +82,7 @@ def main():
                              err=r["err"].tolist(), s=r["s"].tolist(), R=r["R"].tolist(),
                              t=r["t"].tolist(), final=summary(r["new_p"]),
                              idx0_sqrt_vs_squared_mismatches=sqrt_diff)
-            np.savez_compressed(os.path.join(HERE, f"{name}_oracle.npz"), idx0=r["idx0"],
-                                new_p=r["new_p"])
+            savez_lzma(os.path.join(HERE, f"{name}_oracle.npz"), idx0=r["idx0"], new_p=r["new_p"])
             print(name, r["iterations"], r["err"][-1], file=sys.stderr)
     # small synthetic pair, fixed 30 iterations (threshold disabled)
     m, p = synthetic_small()

@@ -12,8 +12,9 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-BENCH_FLAGS = ["--gpus", "8", "--steps", "30", "--warmup", "2", "--points", "8388608", "--no-cow", "--no-cases",
-               "--no-cpu-baseline", "--variant", "auto", "--nn", "certified"]
+BENCH_FLAGS = ["--full", "--gpus", "8", "--steps", "30", "--warmup", "2", "--points", "8388608", "--no-cow",
+               "--no-cases", "--no-cpu-baseline", "--variant", "auto", "--nn", "certified",
+               "--dump-outputs", "out"]
 
 
 def test_torchrun_passes_every_bench_flag_through():
@@ -29,6 +30,7 @@ def test_bench_help_lists_points_and_keeps_n_alias():
                          timeout=120, cwd=ROOT)
     assert out.returncode == 0, out.stderr
     assert re.search(r"--points N, --n N", out.stdout), out.stdout
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout, out.stdout
 
 
 @pytest.mark.parametrize("doc", ["README.md", "DESIGN.md"])
@@ -55,6 +57,44 @@ def _bench_module():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def test_dump_outputs_writes_float64_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every output of the last step as float64 <name>.npy; a shard above
+    DUMP_MAX_ROWS is written as the same seeded, ascending sample of rows on every call."""
+    import numpy as np
+    bench = _bench_module()
+    scene = np.arange(30.0).reshape(10, 3)
+    idx = np.arange(10, dtype=np.int32)[::-1].copy()
+
+    class Ctx:
+        def get_scene(self):
+            return scene.copy()
+
+        def get_indices(self):
+            return idx.copy()
+
+    class Res:
+        iterations, converged, err, s, R, t = 3, 0, 0.25, 1.0, list(range(9)), [0.5, 0.25, 0.125]
+
+    errs = np.array([1.0, 0.5, 0.25])
+    bench.dump_outputs(Ctx(), Res(), errs, str(tmp_path / "a"), 0, 1)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["correspondences", "err_trace", "result", "scene", "transform"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["scene"], scene) and np.array_equal(got["correspondences"], idx)
+    assert np.array_equal(got["transform"], [1.0] + list(range(9)) + [0.5, 0.25, 0.125])
+    assert np.array_equal(got["result"], [3, 0, 0.25]) and np.array_equal(got["err_trace"], errs)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(Ctx(), Res(), errs, str(tmp_path / d), 1, 2)
+    b = {f.stem: np.load(f) for f in (tmp_path / "b").iterdir()}
+    rows = b["sample_rows_rank1"].astype(int)
+    assert rows.size == 4 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(b["scene_rank1"], scene[rows]) and np.array_equal(b["correspondences_rank1"], idx[rows])
+    for name, a in b.items():
+        assert np.array_equal(a, np.load(tmp_path / "c" / f"{name}.npy"))
 
 
 def test_dtype_describes_what_ran():

@@ -9,6 +9,6 @@ for k in 1 2; do
   timeout -k 10 300 python tools/configs_probe.py --configs C2_bunny C3_horse --variants auto grid --reps 3 >> $O/new.log 2>&1 || exit 1
   ICP_AMD_LIB=$OLD timeout -k 10 300 python tools/configs_probe.py --configs C2_bunny C3_horse --variants auto grid --reps 3 >> $O/old.log 2>&1 || exit 1
 done
-timeout -k 10 200 python bench.py --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases > $O/grid_new.log 2>&1 || exit 1
-ICP_AMD_LIB=$OLD timeout -k 10 200 python bench.py --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases > $O/grid_old.log 2>&1 || exit 1
+timeout -k 10 200 python bench.py --full --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases > $O/grid_new.log 2>&1 || exit 1
+ICP_AMD_LIB=$OLD timeout -k 10 200 python bench.py --full --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases > $O/grid_old.log 2>&1 || exit 1
 echo done

@@ -17,7 +17,7 @@ step() { # name timeout cmd...
     tail -n 3 "$OUT/$name.log" | cut -c1-300
 }
 step pytest 600 python -u -m pytest tests -m gpu -q -rf -x --timeout 300 --timeout-method thread
-B="python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-cow --no-cases"
+B="python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-cow --no-cases"
 for r in 1 2; do
     ICP_AMD_LIB=$BASE step bench_base_$r 300 $B
     step bench_new_$r 300 $B

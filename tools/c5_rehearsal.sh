@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 (for i in $(seq 1 14); do sleep 45; echo "[c5_rehearsal] $((45 * i)) s"; done) &
 TICK=$!
 ICP_BENCH_HOST_REDUCE=1 timeout -k 10 660 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$RANKS" \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$RANKS" --points 8388608 --steps 5 --warmup 1 \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus "$RANKS" --points 8388608 --steps 5 --warmup 1 \
     > "$OUT/bench_c5_dist$RANKS.log" 2>&1
 rc=$?
 kill $TICK 2>/dev/null

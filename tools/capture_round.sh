@@ -10,7 +10,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${1:?tag}
 O=gpurun_out/$TAG; mkdir -p "$O" "profiles/$TAG"; export TMPDIR=/tmp
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases"
+B="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases"
 step() { # name timeout cmd...
     local name=$1 to=$2; shift 2
     timeout -k 10 "$to" "$@" > "$O/$name.log" 2>&1
@@ -26,6 +26,6 @@ python3 tools/pmc_summary.py "$(find "$O/fetch" -name '*counter_collection.csv' 
     "$(find "$O/write" -name '*counter_collection.csv' | head -1)" "profiles/${TAG}_pmc_traffic.json"
 step sq 600 bash tools/pmc_probe.sh "$TAG/sq" nn_grid_iter2
 python3 tools/sq_summary.py "profiles/${TAG}_sq_iter.json" "$O"/sq/p*/p_counter_collection.csv > /dev/null
-step bench 400 python3 bench.py
+step bench 400 python3 bench.py --full
 cp "$O/bench.log" "profiles/$TAG/bench.log"
 echo done

@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/${1:-envab}; VAR=$2; VALS=$3; mkdir -p $O; export TMPDIR=/tmp
 for v in $VALS; do
-  env $VAR=$v timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_$v.log 2>&1 || exit 1
+  env $VAR=$v timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_$v.log 2>&1 || exit 1
   env $VAR=$v timeout -k 10 120 python3 tools/shard_probe.py --worlds 8 --steps 30 --warmup 5 > $O/s_$v.log 2>&1 || exit 1
   python3 - "$O/b_$v.log" "$O/s_$v.log" "$VAR=$v" <<'PY' | tee -a $O/summary.txt
 import json, sys

@@ -4,7 +4,7 @@ set -u
 O=gpurun_out/${1:-farab}; mkdir -p $O; export TMPDIR=/tmp
 VALS=${2:-"5 3 2 1 0"}
 for v in $VALS; do
-  ICP_GRID_FAR_SHIFT=$v timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-cow --no-cases > $O/b_$v.log 2>&1 || exit 1
+  ICP_GRID_FAR_SHIFT=$v timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-cow --no-cases > $O/b_$v.log 2>&1 || exit 1
   python3 - "$O/b_$v.log" "shift=$v" <<'PY' | tee -a $O/summary.txt
 import json, sys
 for l in open(sys.argv[1]):

@@ -30,20 +30,20 @@ for s in $STEPS; do
     case $s in
     test)  run pytest_gpu 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeout-method thread --durations=15 ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    bench_mfma) run bench_mfma 300 python bench.py --variant mfma --no-cpu-baseline --no-cow ;;
-    bench_mfma16) run bench_mfma16 300 python bench.py --variant mfma16 --no-cpu-baseline --no-cow ;;
-    bench_valu) run bench_valu 300 python bench.py --variant valu --no-cpu-baseline --no-cow ;;
-    bench_fp64) run bench_fp64 300 python bench.py --nn fp64 --steps 5 --warmup 1 --no-cpu-baseline --no-cow ;;
+    bench) run bench 600 python bench.py --full ;;
+    bench_mfma) run bench_mfma 300 python bench.py --full --variant mfma --no-cpu-baseline --no-cow ;;
+    bench_mfma16) run bench_mfma16 300 python bench.py --full --variant mfma16 --no-cpu-baseline --no-cow ;;
+    bench_valu) run bench_valu 300 python bench.py --full --variant valu --no-cpu-baseline --no-cow ;;
+    bench_fp64) run bench_fp64 300 python bench.py --full --nn fp64 --steps 5 --warmup 1 --no-cpu-baseline --no-cow ;;
     prof)  run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-               python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases ;;
+               python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases ;;
     profv) for v in ${PROFV:-mfma16 valu}; do
                run rocprof_$v 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$v" -o bench -- \
-                   python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-cow --variant $v; done ;;
+                   python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-cow --variant $v; done ;;
     pmc)   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc1" -o fetch -- \
-               python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
+               python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
            run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc2" -o write -- \
-               python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
+               python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
     sq)    for v in ${SQV:-mfma valu}; do
                run sq1_$v 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_VALU_MFMA_COEXEC_CYCLES GRBM_GUI_ACTIVE \
                    --output-format csv -d "$OUT/sq1_$v" -o sq -- python3 tools/nn_probe.py --variant $v --reps 1
@@ -61,7 +61,7 @@ for s in $STEPS; do
              done ;;
     test16plain) ICP_MFMA16_KERNEL=plain run pytest_gpu_plain 900 python -m pytest tests -m gpu -q -rf -k "mfma16 or grid or sharded" ;;
     dist2) ICP_BENCH_HOST_REDUCE=1 run bench_dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-               --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 10 --warmup 2 ;;
+               --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 10 --warmup 2 ;;
     profcow) COW=$(python3 -c 'import sys; sys.path.insert(0, "tests"); import datasets; print(datasets.path("cow_ref"), datasets.path("cow_tr1"))')
            set -- $COW
            run rocprof_cow 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_cow" -o cow -- \
@@ -84,7 +84,7 @@ for s in $STEPS; do
                python3 tools/shard_probe.py --n 8388608 --worlds 8 --steps 4 --warmup 8 ;;
     c5dist8) # the 8-rank C5 flow rehearsed on one GPU (8 processes, sums through gloo)
            ICP_BENCH_HOST_REDUCE=1 run bench_c5_dist8 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-               --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --points 8388608 --steps 10 --warmup 2 \
+               --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 8 --points 8388608 --steps 10 --warmup 2 \
                --no-cpu-baseline --no-cow --no-cases ;;
     shard) run shard_c4 600 python tools/shard_probe.py --worlds 1 2 4 8 &&
            run shard_c5 600 python tools/shard_probe.py --n 8388608 --worlds 8 --steps 5 --warmup 2 ;;
@@ -133,11 +133,11 @@ for s in $STEPS; do
                python3 tools/configs_probe.py --configs C3_horse --variants auto --reps 1 &&
            ICP_PERSIST_STAMPS=1 run c3_stamps 120 python3 tools/configs_probe.py --configs C3_horse --variants auto --reps 1 ;;
     gridhbm) run grid_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/grid_trace" -o grid -- \
-               python3 bench.py --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases &&
+               python3 bench.py --full --variant grid --steps 10 --warmup 2 --no-cpu-baseline --no-cow --no-cases &&
            run grid_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/grid_pmc1" -o fetch -- \
-               python3 bench.py --variant grid --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
+               python3 bench.py --full --variant grid --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
            run grid_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/grid_pmc2" -o write -- \
-               python3 bench.py --variant grid --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
+               python3 bench.py --full --variant grid --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
     bprobe) run bprobe 600 python3 tools/bundle_probe.py --steps 10 --variants mfma16 bundle &&
             run bprobe8 300 python3 tools/bundle_probe.py --steps 10 --shard 8 --variants mfma16 bundle ;;
     test_bundle) run pytest_bundle 900 python -u -m pytest tests/test_gpu_split.py tests/test_gpu_parity.py tests/test_gpu_c4c5.py -m gpu -x -v -rf \
@@ -240,7 +240,7 @@ for s in $STEPS; do
                cat $OUT/sceneab_$o.log >> $OUT/sceneab_all_$o.log
                ICP_SCENE_ORDER=$o run sceneab8_$o 300 python3 tools/bundle_probe.py --steps 20 --shard 8 --variants bundle || exit 1
                cat $OUT/sceneab8_$o.log >> $OUT/sceneab_all_$o.log
-               ICP_SCENE_ORDER=$o run sceneabg_$o 300 python3 bench.py --variant grid --steps 20 --no-cpu-baseline --no-cow --no-cases || exit 1
+               ICP_SCENE_ORDER=$o run sceneabg_$o 300 python3 bench.py --full --variant grid --steps 20 --no-cpu-baseline --no-cow --no-cases || exit 1
                cat $OUT/sceneabg_$o.log >> $OUT/sceneab_all_$o.log
              done ;;
     recab) for o in 1 0 1 0; do
@@ -250,9 +250,9 @@ for s in $STEPS; do
                cat $OUT/recab8_$o.log >> $OUT/recab_all_$o.log
              done ;;
     pmcsq) run pmcsq1 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE \
-               --output-format csv -d "$OUT/pmcsq1" -o sq -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
+               --output-format csv -d "$OUT/pmcsq1" -o sq -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases &&
            run pmcsq2 300 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES SQ_INST_LEVEL_VMEM SQ_ACCUM_PREV_HIRES GRBM_GUI_ACTIVE \
-               --output-format csv -d "$OUT/pmcsq2" -o sq -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
+               --output-format csv -d "$OUT/pmcsq2" -o sq -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cow --no-cases ;;
     percu) for pc in 2 3 4 2 3 4; do
                ICP_BUNDLE_PER_CU=$pc ICP_DEBUG_PLAN=1 run percu_$pc 300 python3 tools/bundle_probe.py --steps 20 --variants bundle || exit 1
                cat $OUT/percu_$pc.log >> $OUT/percu_all_$pc.log
@@ -304,7 +304,7 @@ for s in $STEPS; do
     momab) for k in 1 2; do
              for b in 1 4 2; do
                ICP_MOM_BATCH=$b run momab_${b}_$k 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/momab_${b}_$k" -o c4 -- \
-                   python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-cow --no-cases || exit 1
+                   python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-cow --no-cases || exit 1
              done
            done ;;
     shardab) for k in 1 2; do
@@ -319,7 +319,7 @@ for s in $STEPS; do
               for f in 1 0; do
                 ICP_BUNDLE_FUSE_TASKS=$f run fuseab_${f}_$k 300 python tools/shard_probe.py --worlds 1 8 --steps 20 || exit 1
                 cat $OUT/fuseab_${f}_$k.log >> $OUT/fuseab_all_$f.log
-                ICP_BUNDLE_FUSE_TASKS=$f run fusebench_${f}_$k 300 python3 bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-cow --no-cases || exit 1
+                ICP_BUNDLE_FUSE_TASKS=$f run fusebench_${f}_$k 300 python3 bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-cow --no-cases || exit 1
                 cat $OUT/fusebench_${f}_$k.log >> $OUT/fuseab_all_$f.log
               done
             done ;;
@@ -333,7 +333,7 @@ for s in $STEPS; do
                 for r in 8 1; do
                   ICP_NN_TIMING_STRIDE=$r run strideab_${r}_$k 300 python tools/shard_probe.py --worlds 1 8 --steps 40 || exit 1
                   cat $OUT/strideab_${r}_$k.log >> $OUT/strideab_all_$r.log
-                  ICP_NN_TIMING_STRIDE=$r run stridebench_${r}_$k 300 python3 bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-cow --no-cases || exit 1
+                  ICP_NN_TIMING_STRIDE=$r run stridebench_${r}_$k 300 python3 bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-cow --no-cases || exit 1
                   cat $OUT/stridebench_${r}_$k.log >> $OUT/strideab_all_$r.log
                 done
               done ;;

@@ -15,7 +15,7 @@ while read -r pass; do
   i=$((i+1))
   echo "== pass $i: $pass" | tee -a $O/passes.txt
   timeout -s KILL 90 rocprofv3 --pmc $pass --kernel-include-regex "$K" --output-format csv -d $O/p$i -o p -- \
-    python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/p$i.log 2>&1
+    python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/p$i.log 2>&1
   rc=$?
   echo "   rc=$rc" | tee -a $O/passes.txt
   [ $rc -ge 124 ] && exit 1

@@ -4,7 +4,7 @@
     python tools/roofline.py [--tag r02a] [--n 1048576] [--world 1]
 
 Inputs (both written by tools/gpu_round.sh on the GPU box, then copied into profiles/):
-  profiles/<tag>_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `bench.py --no-cases`
+  profiles/<tag>_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `bench.py --full --no-cases`
   profiles/<tag>_pmc_traffic.json         tools/pmc_summary.py over separate FETCH_SIZE / WRITE_SIZE
                                           passes of the same command (FETCH_SIZE doubled, gfx950)
 Without --tag: the newest tag that has both files.
@@ -132,7 +132,7 @@ def roofline(tag=None, n=1 << 20, world=1):
 # --variants auto --reps 1` (BASELINE config C3: horse_ref vs horse_tr1, 50 iterations, one launch
 # of icp_persistent_mid_kernel per registration), and its ICP_PERSIST_STAMPS=1 phase timers.
 # profiles/<tag>_grid_kernel_stats.csv + <tag>_grid_pmc_traffic.json: the same of `bench.py
-# --variant grid` at C4 (nn_grid_resolve_kernel: the seeded exact grid search of every query).
+# --full --variant grid` at C4 (nn_grid_resolve_kernel: the seeded exact grid search of every query).
 C3_KERNEL = "icp_persistent_mid_kernel"
 C3_ITERATIONS = 50
 # the grid capture's kernel and its algorithmic bytes (per query, per model point): the seeded

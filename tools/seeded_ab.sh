@@ -29,19 +29,19 @@ for l in open(sys.argv[1]):
             print(f\"{sys.argv[2]:>14s} W=8 ms/iter {d['ms_per_iter']*1e3:7.1f}us grid {d['filter_ms']*1e3:7.1f}us other {d['other_ms']*1e3:6.1f}us\")
 " $1 "$2"; }
 for f in $FORMS; do
-  ICP_GRID_SEEDED=$f timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_$f.log 2>&1 || exit 1
+  ICP_GRID_SEEDED=$f timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_$f.log 2>&1 || exit 1
   line $O/b_$f.log "$f" | tee -a $O/summary.txt
   ICP_GRID_SEEDED=$f timeout -k 10 120 python3 tools/shard_probe.py --worlds 8 --steps 30 > $O/s_$f.log 2>&1 || exit 1
   shard8 $O/s_$f.log "$f" | tee -a $O/summary.txt
 done
 for fs in ${FUSED:-1 2 3}; do
-  ICP_FUSED_STEPS=$fs timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_fused$fs.log 2>&1 || exit 1
+  ICP_FUSED_STEPS=$fs timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_fused$fs.log 2>&1 || exit 1
   line $O/b_fused$fs.log "fused=$fs" | tee -a $O/summary.txt
   ICP_FUSED_STEPS=$fs timeout -k 10 120 python3 tools/shard_probe.py --worlds 8 --steps 30 > $O/s_fused$fs.log 2>&1 || exit 1
   shard8 $O/s_fused$fs.log "fused=$fs" | tee -a $O/summary.txt
 done
 for x in 0 2; do
-  ICP_GRID_XCD=$x timeout -k 10 120 python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_xcd$x.log 2>&1 || exit 1
+  ICP_GRID_XCD=$x timeout -k 10 120 python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-cow --no-cases --no-registration > $O/b_xcd$x.log 2>&1 || exit 1
   line $O/b_xcd$x.log "xcd=$x" | tee -a $O/summary.txt
 done
 timeout -k 10 200 python3 tools/shard_probe.py --worlds 1 8 --steps 30 > $O/shard.log 2>&1 || exit 1
