@@ -225,6 +225,29 @@ int icp_set_nn_rule(icp_ctx *ctx, int rule);
 #define ICP_RUN_PERSISTENT 2
 int icp_set_run_mode(icp_ctx *ctx, int mode);
 
+/* ---- partial overlap: the max-correspondence-distance gate --------------- */
+/* dmax > 0 and finite (the clouds' units): icp_run drops, in every iteration, the pairs farther
+ * apart than dmax (PCL / Open3D max_correspondence_distance).  With D = dmax * dmax in fp64 and
+ * d2_j = (dx*dx + dy*dy) + dz*dz between scene point j and its correspondence, pair j is kept
+ * when d2_j <= D; K = the pairs kept over all ranks.  Horn's closed form runs over the kept
+ * pairs with N = K, EVERY point is transformed (the outliers move with the cloud), and
+ * err = (e + e) / K with e the kept pairs' residual.  An iteration with K < 4 stops the run
+ * before it changes anything: icp_run returns ICP_E_TOO_FEW_POINTS with res and err_trace
+ * filled for the completed iterations and the scene as the last completed one left it.
+ * A gated run always takes the launch loop (ICP_RUN_LAUNCHES), whatever icp_set_run_mode says.
+ * 0 or +inf switches the gate off (the default: icp_run exactly as without this call); a
+ * negative value or NaN is ICP_E_ARG.  The setting survives icp_set_scene / icp_set_model. */
+int icp_set_max_distance(icp_ctx *ctx, double dmax);
+/* The last gate the last gated icp_run evaluated: the last recorded iteration's, or the failing
+ * one's after ICP_E_TOO_FEW_POINTS.  mask_out (nullable): this rank's np_local flags (0 / 1) in
+ * the caller's point order; count_out (nullable): K over all ranks.  ICP_E_NO_MODEL if no gated
+ * run has happened since icp_set_scene. */
+int icp_get_inliers(icp_ctx *ctx, uint8_t *mask_out, long long *count_out);
+/* K of each recorded iteration of the last gated icp_run: writes min(cap, iterations) entries
+ * (counts_out may be NULL when cap is 0) and returns the number of recorded iterations (>= 0),
+ * or ICP_E_NO_MODEL as icp_get_inliers. */
+int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap);
+
 /* ---- the ICP loop: GPU::ICP::find_corresponding_opti (src/GPU/gpu.cc:52-83) -- */
 /* Runs up to max_iter iterations on the resident clouds; stops after the iteration
  * whose err < threshold (pass threshold < 0 to run exactly max_iter iterations).

@@ -12,6 +12,8 @@
 //   --allow-unequal    run even when the clouds differ in size (reference: exit 255)
 //   --nn fp64|certified  NN arithmetic (default certified; identical results)
 //   --threshold X      convergence threshold (default 1e-5, src/cpu.hh:113)
+//   --max-dist X       max correspondence distance: pairs farther apart than X are left out of
+//                      each iteration's alignment and error (partial overlap; default: none)
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
 #include <cstdio>
@@ -44,7 +46,7 @@ int main(int argc, char **argv)
     bool allow_unequal = false;
     int nn_mode = ICP_NN_CERTIFIED, device = 0;
     int rule = std::strcmp(prog, "icp") == 0 ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
-    double threshold = 1e-5;
+    double threshold = 1e-5, max_dist = 0.0;
     const char *out = "output.txt";
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
@@ -55,6 +57,7 @@ int main(int argc, char **argv)
             ++a;
             rule = !std::strcmp(argv[a], "cpu") ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
         } else if (!std::strcmp(argv[a], "--threshold") && a + 1 < argc) threshold = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--max-dist") && a + 1 < argc) max_dist = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
         else {
@@ -85,6 +88,10 @@ int main(int argc, char **argv)
     }
     icp_set_allow_unequal(ctx, allow_unequal ? 1 : 0);
     icp_set_nn_rule(ctx, rule);
+    if ((rc = icp_set_max_distance(ctx, max_dist)) != ICP_OK) {
+        std::fprintf(stderr, "[error] --max-dist: %s\n", icp_strerror(rc));
+        return 3;
+    }
     if ((rc = icp_set_model(ctx, m, nm)) != ICP_OK || (rc = icp_set_scene(ctx, p, np, np)) != ICP_OK) {
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;

@@ -377,6 +377,20 @@ struct icp_ctx {
     int *s_tmp_idx = nullptr;
     size_t s_tmp_idx_cap = 0;
 
+    // the max-correspondence-distance gate (icp_set_max_distance; icp_gated.hip): dmax (0: off),
+    // the last gated run's mask words (the scene's order), its flags in the caller's order, the
+    // gate's device state with its mapped host mirror, and the mapped K trace
+    double gate_dmax = 0.0;
+    unsigned long long *gate_mask = nullptr;
+    unsigned char *gate_flags = nullptr;
+    double *gate_part = nullptr; // (the gated moments' partial rows: kGateSums a workgroup)
+    size_t gate_mask_cap = 0, gate_flags_cap = 0, gate_part_cap = 0;
+    GateState *gate_state = nullptr, *h_gate = nullptr, *d_gate_mirror = nullptr;
+    long long *h_ktrace = nullptr, *d_ktrace = nullptr;
+    size_t ktrace_cap = 0;
+    bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
+    int gate_iters = 0;     // ... and recorded this many iterations
+
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
     std::string err;
@@ -1575,13 +1589,16 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->mid_q4, (void *)ctx->mid_res, (void *)ctx->mid_perm, (void *)ctx->mid_cnt,
                     (void *)ctx->s_order, (void *)ctx->s_tmp_idx, (void *)ctx->b_pimg_l, (void *)ctx->b_frame,
                     (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
-                    (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts})
+                    (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
+                    (void *)ctx->gate_mask, (void *)ctx->gate_flags, (void *)ctx->gate_part, (void *)ctx->gate_state})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
     if (ctx->h_iter) (void)hipHostFree(ctx->h_iter);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
     if (ctx->h_far) (void)hipHostFree(ctx->h_far);
+    if (ctx->h_gate) (void)hipHostFree(ctx->h_gate);
+    if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
     if (ctx->h_few) (void)hipHostFree(ctx->h_few);
     if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
     if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
@@ -1631,6 +1648,37 @@ int icp_set_allow_unequal(icp_ctx *ctx, int allow)
     if (!ctx) return ICP_E_ARG;
     ctx->allow_unequal = allow != 0;
     return ICP_OK;
+}
+
+int icp_set_max_distance(icp_ctx *ctx, double dmax)
+{
+    if (!ctx || std::isnan(dmax) || dmax < 0.0) return ICP_E_ARG;
+    ctx->gate_dmax = std::isinf(dmax) ? 0.0 : dmax; // (0 and +inf: off -- every pair is kept)
+    return ICP_OK;
+}
+
+int icp_get_inliers(icp_ctx *ctx, uint8_t *mask_out, long long *count_out)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!ctx->has_scene || !ctx->gate_have)
+        return fail(ctx, ICP_E_NO_MODEL, "no gated icp_run since icp_set_scene (icp_set_max_distance)");
+    HIPCHK(hipSetDevice(ctx->device));
+    if (mask_out && ctx->scene.n) {
+        HIPCHK(hipMemcpyAsync(mask_out, ctx->gate_flags, ctx->scene.n, hipMemcpyDeviceToHost, ctx->st));
+        HIPCHK(hipStreamSynchronize(ctx->st));
+    }
+    if (count_out) *count_out = ctx->h_gate->K;
+    return ICP_OK;
+}
+
+int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap)
+{
+    if (!ctx || (!counts_out && cap)) return ICP_E_ARG;
+    if (!ctx->has_scene || !ctx->gate_have)
+        return fail(ctx, ICP_E_NO_MODEL, "no gated icp_run since icp_set_scene (icp_set_max_distance)");
+    const size_t k = std::min(cap, (size_t)ctx->gate_iters);
+    if (k) std::memcpy(counts_out, ctx->h_ktrace, sizeof(long long) * k);
+    return ctx->gate_iters;
 }
 
 // The model's AoS copy -> ctx->stage (pageable host memory: the runtime's staged copy).
@@ -1975,6 +2023,7 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
     ctx->has_scene = true;
     ctx->seeds_valid = false;
     ctx->seedd_valid = false;
+    ctx->gate_have = false;
     ctx->q_order_src = nullptr; // new contents: a new query order
     ctx->scene_slot = slot;     // (else in the caller's order)
     ctx->scene_revert = false;
@@ -2324,6 +2373,8 @@ static int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_
 // iteration already enqueued behind it changes nothing), which is exactly where the
 // reference's loop breaks (gpu.cc:79-80).
 static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool no_tail);
+static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
+                     std::chrono::steady_clock::time_point wall0);
 constexpr int kTailAborted = -1000; // run_loop: a fused tail's grid barrier timed out (state restored)
 
 int icp_run(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res)
@@ -2408,6 +2459,8 @@ static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_tr
         LAUNCHCHK("make_f32");
         ctx->p32_stale = false;
     }
+    // icp_set_max_distance: the gated loop (never the one-launch kernels or the fused iterations)
+    if (ctx->gate_dmax > 0.0) return run_gated(ctx, max_iter, threshold, err_trace, res, need_p32, wall0);
     {
         size_t lds = 0;
         bool mid = false;
@@ -3200,6 +3253,135 @@ static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_tr
     ctx->last_q2 = q2_obs;
     ctx->second_pass_items = 0;
     return finish_run(ctx, threshold, err_trace, res, wall0);
+}
+
+// icp_run with the max-correspondence-distance gate on (icp_set_max_distance; kernels in
+// icp_gated.hip).  run_loop has prepared the loop state, the mapped mirrors and the flag ring.
+// Per iteration: the search as the launch loop's generic path runs it (seeded by the previous
+// correspondences, nothing carried from a transform), the gated moments (gate, mask, 18 sums), the
+// fold and the gated Horn step, the transform of every point with the kept points' residual, the
+// fold and the error step with N = K.  With ranks or a communicator the 18 sums and the residual
+// are each all-reduced before their step (two all-reduces an iteration; the error test is not
+// lagged).  The scene keeps the order it is in (file or slot); on one rank the host does not
+// synchronise inside an iteration.
+static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
+                     std::chrono::steady_clock::time_point wall0)
+{
+    if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
+    const size_t n = ctx->scene.n;
+    DevCloud &P = ctx->scene, &Y = ctx->Y;
+    constexpr int kAhead = 1, kRing = 4;
+    const double D = ctx->gate_dmax * ctx->gate_dmax; // (fp64, once)
+    const bool ranks = lag_run(ctx);
+    const int nb = red_blocks(n);
+    TRY(grow(ctx, &ctx->gate_mask, &ctx->gate_mask_cap, (n + 63) / 64));
+    TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
+    TRY(grow(ctx, &ctx->gate_part, &ctx->gate_part_cap, (size_t)kRedMaxBlocksCap * kGateSums));
+    if (!ctx->gate_state) HIPCHK(hipMalloc((void **)&ctx->gate_state, sizeof(GateState)));
+    if (!ctx->h_gate) {
+        HIPCHK(hipHostMalloc((void **)&ctx->h_gate, sizeof(GateState), hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_gate_mirror, ctx->h_gate, 0));
+    }
+    if (ctx->ktrace_cap < (size_t)std::max(max_iter, 1)) { // (the previous run ended with a sync)
+        if (ctx->h_ktrace) HIPCHK(hipHostFree(ctx->h_ktrace));
+        ctx->h_ktrace = nullptr;
+        ctx->ktrace_cap = 0;
+        const size_t cap = (size_t)std::max(max_iter, 64);
+        HIPCHK(hipHostMalloc((void **)&ctx->h_ktrace, sizeof(long long) * cap, hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_ktrace, ctx->h_ktrace, 0));
+        ctx->ktrace_cap = cap;
+    }
+    std::memset(ctx->h_gate, 0, sizeof(GateState));
+    HIPCHK(hipMemsetAsync(ctx->gate_state, 0, sizeof(GateState), ctx->st));
+    IterState *sd = ctx->iter_state;
+    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first iteration's shifts: the model's centre)
+    if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
+    const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
+    ctx->stats.run_path_bits = 0;
+    int slot_ticket[kRing] = {};
+    int enqueued = 0, waited = 0, recorded = 0;
+    bool stop = false;
+    while (!stop && waited < max_iter) {
+        if (enqueued < max_iter && enqueued - waited <= kAhead) {
+            // 1. correspondences (a search queued behind the iteration that froze the run returns at once)
+            const SeedState ws;
+            ctx->second_pass_items = 0;
+            TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, nullptr, nullptr, false, &ws, &sd->done, ctx->scene_slot,
+                                false, nullptr));
+            if (ctx->stats.last_filter == ICP_FILTER_BUNDLE) ctx->stats.run_bundle_searches += 1;
+            else if (ctx->stats.last_filter == ICP_FILTER_GRID) ctx->stats.run_grid_searches += 1;
+            if (ctx->stats.last_filter == ICP_FILTER_GRID && enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
+            ctx->seeds_valid = true;
+            TRY(cpu_rule_fixup(ctx, P, n, &sd->done));
+            if ((size_t)enqueued < ctx->digest_cap) {
+                launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st, digest_order);
+                LAUNCHCHK("idx_digest");
+            }
+            // 2-4. the gate, the kept pairs' moments and count, the Horn step with N = K
+            launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
+                                 ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
+            launch_gated_horn(ctx->gate_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->gate_state,
+                              ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
+            LAUNCHCHK("gated_moments");
+            if (ranks) {
+                TRY(allreduce(ctx, ctx->sums, kGateSums));
+                launch_gated_horn(nullptr, 0, ctx->sums, true, ctx->c, ctx->amb_count, sd, ctx->gate_state,
+                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
+                LAUNCHCHK("gated_horn");
+            }
+            // 5-6. every point moves; the kept points' residual; err = (e + e) / K
+            launch_gated_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                   ctx->gate_mask, ctx->partials, ctx->st);
+            if (!need_p32) ctx->p32_stale = true;
+            const int sl = enqueued % kRing;
+            slot_ticket[sl] = ++ctx->flag_ticket;
+            launch_gated_err(ctx->partials, nb, ctx->sums, !ranks, threshold, max_iter, ctx->err_trace_dev, sd,
+                             ctx->gate_state, ctx->d_ktrace, ctx->d_flags + 4 * sl, slot_ticket[sl], ctx->d_iter_mirror,
+                             ctx->d_trace, ctx->st);
+            LAUNCHCHK("gated_transform");
+            if (ranks) {
+                TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
+                launch_gated_err(nullptr, 0, ctx->sums, true, threshold, max_iter, ctx->err_trace_dev, sd, ctx->gate_state,
+                                 ctx->d_ktrace, ctx->d_flags + 4 * sl, slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace,
+                                 ctx->st);
+                LAUNCHCHK("gated_err");
+            }
+            ++enqueued;
+            continue;
+        }
+        const int slot = waited % kRing;
+        TRY(wait_flag(ctx, ctx->h_flags + 4 * slot + 2, slot_ticket[slot]));
+        ++waited;
+        const int done = ctx->h_flags[4 * slot], iters = ctx->h_flags[4 * slot + 1];
+        report_progress(ctx, iters);
+        if (iters > recorded) {
+            ctx->stats.nn_pairs += (long long)n * (long long)ctx->nm;
+            recorded = iters;
+        }
+        stop = done != 0;
+    }
+    // the last gate evaluated, as flags in the caller's point order (icp_get_inliers)
+    if (enqueued > 0) {
+        launch_gated_unpack(ctx->gate_mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
+        LAUNCHCHK("gated_unpack");
+    }
+    HIPCHK(hipStreamSynchronize(ctx->st)); // (the iteration queued behind the last one drains)
+    // nothing of a transform is carried to the next run: it starts from the correspondences alone
+    ctx->seedd_valid = false;
+    ctx->last_far = -1;
+    ctx->last_q2 = -1;
+    ctx->second_pass_items = 0;
+    if (enqueued > 0) {
+        ctx->gate_have = true;
+        ctx->gate_iters = ctx->h_iter->iter;
+    }
+    const GateState hg = *ctx->h_gate;
+    TRY(finish_run(ctx, threshold, err_trace, res, wall0));
+    if (hg.status == kGateTooFew)
+        return fail(ctx, ICP_E_TOO_FEW_POINTS,
+                    "icp_run: iteration " + std::to_string(hg.fail_iter) + " kept K = " + std::to_string(hg.K) +
+                        " pairs within the max correspondence distance; need at least 4");
+    return ICP_OK;
 }
 
 // The run's result from the mapped host mirror of the last recorded iteration (both loops).

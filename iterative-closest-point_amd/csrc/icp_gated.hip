@@ -1,0 +1,246 @@
+// icp_gated.hip — the kernels of icp_run's gated iteration (icp_set_max_distance): the moments,
+// the transform + residual and their folds and steps over the pairs no farther apart than dmax.
+//
+// One gated iteration on the scene p (n points on this rank), after the search has left idx:
+//   y_j = m[idx_j];  d2_j = (dx*dx + dy*dy) + dz*dz in fp64 as written (the searches' own
+//   arithmetic);  keep_j = d2_j <= D (false for a NaN);  K = #kept over all ranks;
+//   K < 4: the run stops before the iteration changes anything;  else Horn's closed form over the
+//   kept pairs with N = K, every point moved by it (the outliers travel with the cloud), and
+//   err = (e + e) / K with e the kept pairs' residual.
+// The gate of an iteration is kept bit-packed, one 64-bit word per wave of points (__ballot), for
+// the transform's residual and for icp_get_inliers.
+// Compiled with IEEE semantics like icp_step.hip (the error step's `err < threshold` and the
+// gate's `d2 <= D` must stay false for a NaN).
+#include <hip/hip_runtime.h>
+
+#include "icp_device.h"
+#include "icp_fold.h"
+#include "icp_kernels.h"
+
+namespace icp {
+namespace {
+
+// Modelled on shifted_moments_kernel: the 17 one-pass moment terms around the shifts of *st, of
+// the kept pairs only, and the kept count as an 18th sum (a double: exact below 2^53).
+// The loop runs whole waves (its bound is the wave's first point), so that every lane takes part
+// in the ballot; word w of the mask holds points 64 w .. 64 w + 63 and is stored by lane 0.
+// A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
+template <bool YIN>
+__global__ __launch_bounds__(kBlock) void gated_moments_kernel(
+    const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ px,
+    const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
+    double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
+    unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
+    const double4 *__restrict__ m4kd)
+{
+    if (st->done != 0) return;
+    const double cp0 = st->shift_p[0], cp1 = st->shift_p[1], cp2 = st->shift_p[2];
+    const double cy0 = st->shift_y[0], cy1 = st->shift_y[1], cy2 = st->shift_y[2];
+    double a[17];
+#pragma unroll
+    for (int k = 0; k < 17; ++k) a[k] = 0.0;
+    double kept = 0.0;
+    const int lane = threadIdx.x & 63;
+    const long long G = (long long)gridDim.x * kBlock;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i - lane < n; i += G) {
+        bool keep = false;
+        if (i < n) {
+            double4 m;
+            if constexpr (YIN) { // (the search wrote y = m[idx]: the same values, streamed)
+                m = make_double4(yx[i], yy[i], yz[i], 0.0);
+            } else {
+                m = kpos ? m4kd[kpos[i]] : m4[idx[i]]; // (kpos: the same point, kd-ordered copy)
+                yx[i] = m.x;
+                yy[i] = m.y;
+                yz[i] = m.z;
+            }
+            const double q0 = px[i], q1 = py[i], q2 = pz[i];
+            const double dx = q0 - m.x, dy = q1 - m.y, dz = q2 - m.z;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            keep = d2 <= D;
+            if (keep) {
+                shifted_moment_terms(q0, q1, q2, m, cp0, cp1, cp2, cy0, cy1, cy2, a);
+                kept += 1.0;
+            }
+        }
+        const unsigned long long word = __ballot(keep);
+        if (lane == 0) mask[i >> 6] = word;
+    }
+    double b[kGateSums];
+#pragma unroll
+    for (int k = 0; k < 17; ++k) b[k] = a[k];
+    b[kGateCount] = kept;
+    block_sum_store<kGateSums>(b, partials + (size_t)blockIdx.x * kGateSums);
+}
+
+// reduce_kernel<K>'s tree over nblocks rows of K doubles: out[k] (global) and res[k] (LDS) for
+// k < K; every thread of the workgroup must call it.  One row folds to itself.
+template <int K>
+__device__ __forceinline__ void fold_to(const double *__restrict__ partials, int nblocks, double *__restrict__ out,
+                                        double *res)
+{
+    __shared__ double sh[kBlock / 64][K];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = 0.0;
+    fold_rows<K>(partials, nblocks, a);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) sh[wave][k] = a[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double r = sh[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) r += sh[w][threadIdx.x];
+        out[threadIdx.x] = r;
+        res[threadIdx.x] = r;
+    }
+    __syncthreads();
+}
+
+// The fold of the moments' partial rows into sums[0..17] (nblocks > 0) and / or the gated Horn
+// step on sums (step; nblocks = 0: the sums as they are, all-reduced).  The step decides from the
+// global count K = sums[kGateCount], identical on every rank: K < 4 freezes the run (done) with
+// the too-few status before anything of this iteration is applied, and mirrors the loop state of
+// the last completed iteration to the host; else Horn's closed form over the kept pairs, N = K.
+__global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__restrict__ partials, int nblocks,
+                                                            double *__restrict__ sums, int step, double c0, double c1,
+                                                            double c2, int *__restrict__ cnt, IterState *__restrict__ s,
+                                                            GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                                            IterState *__restrict__ h_state)
+{
+    __shared__ double res[kGateSums];
+    if (nblocks > 0) {
+        fold_to<kGateSums>(partials, nblocks, sums, res);
+    } else {
+        if (threadIdx.x < kGateSums) res[threadIdx.x] = sums[threadIdx.x];
+        __syncthreads();
+    }
+    if (!step || threadIdx.x != 0) return;
+    const double K = res[kGateCount];
+    if (!s->done) { // (a frozen iteration's sums are stale: its gate was not evaluated)
+        g->K = (long long)K;
+        h_g->K = (long long)K;
+        if (!(K >= 4.0)) {
+            s->done = 1;
+            g->status = kGateTooFew;
+            g->fail_iter = s->iter;
+            h_g->status = kGateTooFew;
+            h_g->fail_iter = s->iter;
+            const int *src = (const int *)s;
+            int *dst = (int *)h_state;
+            for (size_t k = 0; k < sizeof(IterState) / sizeof(int); ++k) dst[k] = src[k];
+        }
+    }
+    horn_step_body(res, K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
+}
+
+// Modelled on the plain branch of transform_err_kernel: every point moves, the residual is
+// summed over the kept points (the gate's mask words).  A no-op once *done.
+__global__ __launch_bounds__(kBlock) void gated_transform_kernel(
+    double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, const double *__restrict__ yx,
+    const double *__restrict__ yy, const double *__restrict__ yz, int n, const Xform *__restrict__ xfd,
+    const int *__restrict__ done, float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
+    double *__restrict__ partials)
+{
+    __shared__ Xform sxf;
+    __shared__ int sdone;
+    if (threadIdx.x == 0) {
+        sdone = *done;
+        sxf = *xfd;
+    }
+    __syncthreads();
+    if (sdone) return;
+    const Xform xf = sxf;
+    double a[1] = {0.0};
+    const long long G = (long long)gridDim.x * kBlock;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += G) {
+        double q0, q1, q2;
+        transform_point(xf, px[i], py[i], pz[i], q0, q1, q2);
+        if ((mask[i >> 6] >> (i & 63)) & 1ull) a[0] += residual2(yx[i], yy[i], yz[i], q0, q1, q2);
+        px[i] = q0;
+        py[i] = q1;
+        pz[i] = q2;
+        if (p32) p32[i] = make_float4((float)(q0 - xf.c[0]), (float)(q1 - xf.c[1]), (float)(q2 - xf.c[2]), 0.0f);
+    }
+    block_sum_store<1>(a, partials + blockIdx.x);
+}
+
+// The fold of the residual's partial rows into sums[kSumErr] (nblocks > 0) and / or the error
+// step with N = K (step): the iteration's K joins the mapped K trace as its error is recorded.
+__global__ __launch_bounds__(kBlock) void gated_err_kernel(const double *__restrict__ partials, int nblocks,
+                                                           double *__restrict__ sums, int step, double threshold,
+                                                           int max_iter, double *__restrict__ err_trace,
+                                                           IterState *__restrict__ s, const GateState *__restrict__ g,
+                                                           long long *__restrict__ h_ktrace, int *hflag, int ticket,
+                                                           IterState *h_state, double *h_trace)
+{
+    __shared__ double res[1];
+    if (nblocks > 0) fold_to<1>(partials, nblocks, sums + kSumErr, res);
+    if (!step || threadIdx.x != 0) return;
+    const long long K = g->K;
+    if (!s->done) h_ktrace[s->iter] = K;
+    err_step_body(sums, (double)K, threshold, max_iter, err_trace, s, hflag, ticket, h_state, h_trace);
+}
+
+// out[caller's index of point i] = bit i of the mask (order: point i is the caller's order[i])
+__global__ __launch_bounds__(kBlock) void gated_unpack_kernel(const unsigned long long *__restrict__ mask,
+                                                              const int *__restrict__ order, int n,
+                                                              unsigned char *__restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out[order ? order[i] : i] = (unsigned char)((mask[i >> 6] >> (i & 63)) & 1ull);
+}
+
+} // namespace
+
+void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
+                          int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
+                          unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                          const double4 *m4kd, bool y_ready)
+{
+    if (y_ready)
+        gated_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
+                                                                     partials, kpos, m4kd);
+    else
+        gated_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
+                                                                      partials, kpos, m4kd);
+}
+
+void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
+                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st)
+{
+    gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
+                                            gate, h_gate, h_state);
+}
+
+void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
+                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
+                            double *partials, hipStream_t st)
+{
+    gated_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, partials);
+}
+
+void launch_gated_err(const double *partials, int nblocks, double *sums, bool step, double threshold, int max_iter,
+                      double *err_trace, IterState *st_dev, const GateState *gate, long long *h_ktrace, int *hflag_dev,
+                      int ticket, IterState *h_state_dev, double *h_trace_dev, hipStream_t st)
+{
+    gated_err_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, threshold, max_iter, err_trace, st_dev,
+                                           gate, h_ktrace, hflag_dev, ticket, h_state_dev, h_trace_dev);
+}
+
+void launch_gated_unpack(const unsigned long long *mask, const int *order, int n, unsigned char *out, hipStream_t st)
+{
+    if (n <= 0) return;
+    gated_unpack_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(mask, order, n, out);
+}
+
+} // namespace icp

@@ -714,6 +714,42 @@ void launch_nn_exact_few(const double *q_aos, int nq, const double4 *m4, int nm,
 void launch_reduce_pair(const double *part17, const double *part1, int nblocks, double *out, hipStream_t st);
 void launch_reduce(const double *partials, int nblocks, int K, double *out, hipStream_t st);
 
+// ---- the gated iteration (icp_gated.hip; icp_set_max_distance) ---------------------------------
+// The moments' sums of a gated iteration: the 17 one-pass terms over the kept pairs (sums slots
+// 0..16) and the kept count.  The count takes slot 17 until the Horn step has read it (into
+// GateState::K); the residual's fold then writes its e there (kSumErr), as in the ungated loop.
+constexpr int kGateSums = 18, kGateCount = 17;
+constexpr int kGateTooFew = 1;
+// Per-run state of the gate, beside IterState (whose layout every other kernel reads): device
+// copy and mapped host mirror.
+struct GateState {
+    int status;    // 0, or kGateTooFew: an iteration's K < 4 froze the run
+    int fail_iter; // ... the iteration (0-based) that found it
+    long long K;   // kept pairs, all ranks', of the last gate evaluated
+};
+// y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; mask word w = the ballot of points
+// 64 w ..; partial [17 shifted moment terms of the kept pairs, their count]; a no-op once done
+void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
+                          int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
+                          unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                          const double4 *m4kd, bool y_ready);
+// nblocks > 0: sums[0..17] = the fold of the partial rows (reduce_kernel's tree); step: K < 4
+// sets done and the too-few status (the loop state mirrored to h_state), else the shifted Horn
+// step with N = K = sums[kGateCount]
+void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
+                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st);
+// p <- sR p + t for every point (p32 nullable); partial [sum over the kept points of ||y - p'||^2]
+void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
+                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
+                            double *partials, hipStream_t st);
+// nblocks > 0: sums[kSumErr] = the fold of the partial rows; step: launch_err_step's with N =
+// gate->K, and h_ktrace[iter] = K for a recorded iteration
+void launch_gated_err(const double *partials, int nblocks, double *sums, bool step, double threshold, int max_iter,
+                      double *err_trace, IterState *st_dev, const GateState *gate, long long *h_ktrace, int *hflag_dev,
+                      int ticket, IterState *h_state_dev, double *h_trace_dev, hipStream_t st);
+// out[order ? order[i] : i] = bit i of the mask (bytes, the caller's point order)
+void launch_gated_unpack(const unsigned long long *mask, const int *order, int n, unsigned char *out, hipStream_t st);
+
 // ---- the model's preparation on the device (icp_model.hip) ------------------------------------
 // out[10] = (sum x, sum y, sum z, lo xyz, hi xyz, non-finite coordinates) of n AoS points:
 // fixed-order two-stage reductions; scratch: model_stats_scratch_doubles()

@@ -68,6 +68,7 @@ EXPORTED = [
     "icp_get_index_digest", "icp_set_cert_audit", "icp_set_run_mode", "icp_set_nn_rule",
     "icp_get_comm_info", "icp_set_bundle_counters", "icp_get_bundle_counters", "icp_get_model_order",
     "icp_bundle_audit", "icp_sort_pairs",
+    "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
 ]
 
 
@@ -174,6 +175,10 @@ def lib() -> C.CDLL:
     L.icp_set_bundle_counters.argtypes = [vp, C.c_int]
     L.icp_get_bundle_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.icp_get_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    if hasattr(L, "icp_set_max_distance"):  # (an A/B library of an earlier round lacks them)
+        L.icp_set_max_distance.argtypes = [vp, C.c_double]
+        L.icp_get_inliers.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_longlong)]
+        L.icp_get_inlier_trace.argtypes = [vp, C.POINTER(C.c_longlong), sz]
     _lib = L
     return L
 
@@ -401,6 +406,28 @@ class Context:
     def set_allow_unequal(self, allow: bool):
         self._check(lib().icp_set_allow_unequal(self._h, 1 if allow else 0))
 
+    def set_max_distance(self, d: float):
+        """icp_set_max_distance: run() keeps only the pairs no farther apart than d (0 or inf: off)."""
+        self._check(lib().icp_set_max_distance(self._h, float(d)))
+
+    def inliers(self):
+        """The last gate of the last gated run() -> (mask: bool (np_local,), caller's order; K over all ranks)."""
+        mask = np.zeros(self._np_local, dtype=np.uint8)
+        k = C.c_longlong(0)
+        self._check(lib().icp_get_inliers(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(k)))
+        return mask.astype(bool), int(k.value)
+
+    def inlier_trace(self) -> np.ndarray:
+        """K of each recorded iteration of the last gated run() (int64)."""
+        n = lib().icp_get_inlier_trace(self._h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        rc = lib().icp_get_inlier_trace(self._h, out.ctypes.data_as(C.POINTER(C.c_longlong)), n)
+        if rc < 0:
+            self._check(rc)
+        return out[:n]
+
     def run(self, max_iter: int, threshold: float = 1e-5):
         errs = np.zeros(max(max_iter, 1))
         res = Result()
@@ -532,6 +559,7 @@ class ICP:
     device: int = 0
     threshold: float = 1e-5  # src/GPU/gpu.hh:103
     allow_unequal: bool = False
+    max_distance: float | None = None  # icp_set_max_distance (None: no gate)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -545,6 +573,8 @@ class ICP:
         self.errors = np.zeros(0)
         self._ctx = Context(self.device, self.nn_mode)
         self._ctx.set_allow_unequal(self.allow_unequal)
+        if self.max_distance is not None:
+            self._ctx.set_max_distance(self.max_distance)
         self._ctx.set_model(self.m)
         self._ctx.set_scene(self.p)
 
