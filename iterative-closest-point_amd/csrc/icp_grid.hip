@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "icp_canon.h"
 #include "icp_device.h"
@@ -670,11 +671,13 @@ __global__ __launch_bounds__(TB, W) void nn_grid_seeded_kernel(
 // (sum_a (|v_a| + e)^2)(1 + 2^-24)^4 <= (r + sqrt(3) e)^2 (1 + 2^-21).  A point with d32 above the
 // bound below is therefore strictly farther than best and cannot be the first minimum; the rest
 // (the candidates: the seed and the few points as close) are decided in fp64.
-__device__ __forceinline__ float seeded_bound32(double best, double e)
+// (root: fl(sqrt(best)), for a caller that holds it)
+__device__ __forceinline__ float seeded_bound32_root(double root, double e)
 {
-    const double s = sqrt(best) * (1.0 + 0x1.0p-50) + 1.7320508075688774 * e;
+    const double s = root * (1.0 + 0x1.0p-50) + 1.7320508075688774 * e;
     return (float)(s * s * (1.0 + 0x1.0p-20)) * (1.0f + 0x1.0p-22f); // (rounded up past fl32's halving)
 }
+__device__ __forceinline__ float seeded_bound32(double best, double e) { return seeded_bound32_root(sqrt(best), e); }
 
 // nn_grid_seeded_kernel with the box's points read from the fp32 image (16 B a point instead of
 // 32) and tested against seeded_bound32: a candidate that is the current winner itself (the seed,
@@ -1451,13 +1454,61 @@ static_assert(32 * kIter2Slot + 32 / 2 <= kIter2Tile, "the hand-off slots and th
 // NWG waves a workgroup: 4, the four strands of one canonical row (their sum formed in LDS), or
 // 1, one strand (its sums written as the strand's; the fold forms the rows, canon_row_value: the
 // same bits) -- a wave then frees its slot when it ends, not when its row's slowest wave does
-template <int KR, int KU, int CH, int NWG>
+//
+// The arguments are one struct, and each phase reads the fields it uses from the kernel-argument
+// segment when it starts (iter2_args): 76 dwords of arguments held in SGPRs for the whole kernel,
+// with the transform and the shifts of IterState, were more than the register file has beside the
+// walk's own scalars, and the compiler parked them in VGPR lanes (206 v_writelane / v_readlane,
+// 6% of the kernel's executed VALU instructions).  A wave runs one task at C4, so a phase's
+// fields are read once either way; the rare paths (a box over `box`, the counters) read theirs
+// where they run.  The argument segment and IterState are constant for the launch (the fold
+// writes IterState after it), so both are read through the constant address space: scalar loads.
+struct Iter2Args {
+    int n;
+    double *px, *py, *pz, *yx, *yy, *yz;
+    int *idx;
+    const IterState *st;
+    float4 *p32;
+    GridView gv;
+    int box, budget, nm;
+    const double4 *m4;
+    double *rows;
+    int *far_acc;
+    double far_d2;
+    int *big_count;
+    int xform, xcd_l;
+    CertArgs ca;
+    unsigned long long *dbg;
+};
+static_assert(std::is_trivially_copyable<Iter2Args>::value, "passed by value in the kernel-argument segment");
+#define ICP_CONST_AS __attribute__((address_space(4)))
+// (the empty asm: the loads that follow start here -- not hoisted to the kernel's entry, not
+// merged with another phase's)
+__device__ __forceinline__ const Iter2Args &iter2_args()
+{
+    auto *p = (const ICP_CONST_AS Iter2Args *)__builtin_amdgcn_kernarg_segment_ptr(); // (the only argument: offset 0)
+    asm volatile("" : "+s"(p));
+    return *(const Iter2Args *)p;
+}
+__device__ __forceinline__ const IterState &iter2_state(const IterState *st)
+{
+    auto *p = (const ICP_CONST_AS IterState *)st;
+    asm volatile("" : "+s"(p));
+    return *(const IterState *)p;
+}
+
+// b[i] for 0 <= i, A32: through a 32-bit byte offset (the array below 4 GiB -- iter2_addr32): the
+// load or store takes the scalar base and one VGPR of offset, where b + i is a 64-bit VGPR add; the
+// arrays of one index (the six coordinate streams) share the offset.  The same bytes either way.
+template <bool A32, class T> __device__ __forceinline__ T &at32(T *b, int i)
+{
+    if constexpr (A32) return *(T *)((char *)b + (unsigned)i * (unsigned)sizeof(T));
+    else return b[i];
+}
+
+template <int KR, int KU, int CH, int NWG, bool A32>
 __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_ITER2_WAVES))) void nn_grid_iter2_kernel(
-    int n, double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, double *__restrict__ yx,
-    double *__restrict__ yy, double *__restrict__ yz, int *__restrict__ idx, const IterState *__restrict__ st,
-    float4 *__restrict__ p32, GridView gv, int box, int budget, int nm, const double4 *__restrict__ m4,
-    double *__restrict__ rows, int *far_acc, double far_d2, int *big_count, int xform, int xcd_l, CertArgs ca,
-    unsigned long long *__restrict__ dbg)
+    Iter2Args args_) // (read through iter2_args())
 {
     static_assert(CH == 1 || CH == 2, "one or two chunks a task");
     // (ICP_ITER2_DBG: dcnt = tasks, walkers, walk batches, pair tests -- lane 0's counts, i.e. the
@@ -1468,7 +1519,10 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
     static_assert(NWG == 4 || NWG == 1, "a row or a strand a workgroup");
     constexpr int NW = NWG, QL = 2 / CH; // (lanes a query in phases A and G)
     __shared__ double s_tile[NW][CH * kIter2Tile];
-    if (st->done) return; // a frozen (converged) ICP iteration: nothing moves, nothing is searched
+    const Iter2Args &T = iter2_args(); // (the launch's shape; the phases read their own)
+    const IterState *const st = T.st;
+    if (iter2_state(st).done) return; // a frozen (converged) ICP iteration: nothing moves, nothing is searched
+    const int n = T.n, xcd_l = T.xcd_l, xform = T.xform;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = lane / QL, sub = lane % QL;
     const int C = canon_chunks((size_t)n), S = canon_strands((size_t)n), R = canon_rows((size_t)n);
     // (as nn_grid_iter_kernel: runs of rows an XCD -- for one-strand workgroups runs of 4 L strands)
@@ -1478,7 +1532,8 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
     double *const tile = s_tile[wave];
     double *const slots = tile;                            // (phases A-D) 32 CH slots of kIter2Slot doubles
     int *const wl = (int *)(tile + 32 * CH * kIter2Slot);  // (phase D) the task's walkers, in query order
-    const bool cert_on = ca.state != nullptr, cert_in = cert_on && ca.valid != 0;
+    auto at = [](auto *b, int i) -> auto & { return at32<A32>(b, i); };
+    const bool cert_on = T.ca.state != nullptr, cert_in = cert_on && T.ca.valid != 0, two = T.ca.two != 0;
     auto wave_sync = [] {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1492,19 +1547,28 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         const bool active = c + (u >> 5) * S < C && t < n;
         if (kDbg) dcnt[0] += 1;
         // ---- A: the previous transform, its residual = the seed distance, the certificate
+        // (the fields every task uses are copied here, in a few wide scalar loads and one wait;
+        // a field read where it is used costs a scalar load's round trip there, each on its own)
+        const Iter2Args &A = iter2_args();
+        const Xform xf = iter2_state(st).xf;
+        double *const px = A.px, *const py = A.py, *const pz = A.pz, *const yx = A.yx, *const yy = A.yy, *const yz = A.yz;
+        int *const idx = A.idx;
+        int4 *const cstate = A.ca.state;
+        float4 *const p32 = A.p32;
+        const double far_d2 = A.far_d2;
         double q[3] = {0.0, 0.0, 0.0}, y[3] = {0.0, 0.0, 0.0};
         int h = -1;
         int4 cs4 = make_int4(kNoBound, kNoBound, -1, -1); // (the certificate's state: R1, R3 bits, the pair)
         double mot = 0.0;
         if (active) {
-            const double p0 = px[t], p1 = py[t], p2 = pz[t];
-            y[0] = yx[t];
-            y[1] = yy[t];
-            y[2] = yz[t];
-            h = idx[t];
-            if (cert_in) cs4 = ca.state[t];
+            const double p0 = at(px, t), p1 = at(py, t), p2 = at(pz, t);
+            y[0] = at(yx, t);
+            y[1] = at(yy, t);
+            y[2] = at(yz, t);
+            h = at(idx, t);
+            if (cert_in) cs4 = at(cstate, t);
             if (xform) {
-                transform_point(st->xf, p0, p1, p2, q[0], q[1], q[2]);
+                transform_point(xf, p0, p1, p2, q[0], q[1], q[2]);
                 // (the motion rounded up: the square up to fp32, its root by v_sqrt_f32 -- within an
                 // ulp or two -- and 2^-21 of room; tests/test_iter_prune.py restates it)
                 if (cert_in)
@@ -1518,21 +1582,21 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         }
         const double e = active ? residual2(y[0], y[1], y[2], q[0], q[1], q[2]) : 0.0;
         if (active && sub == 0 && xform) {
-            px[t] = q[0];
-            py[t] = q[1];
-            pz[t] = q[2];
+            at(px, t) = q[0];
+            at(py, t) = q[1];
+            at(pz, t) = q[2];
             if (p32)
-                p32[t] = make_float4((float)(q[0] - st->xf.c[0]), (float)(q[1] - st->xf.c[1]), (float)(q[2] - st->xf.c[2]),
+                at(p32, t) = make_float4((float)(q[0] - xf.c[0]), (float)(q[1] - xf.c[1]), (float)(q[2] - xf.c[2]),
                                      0.0f);
         }
         if (active && sub == 0) { // the policy's far count (SeedArgs::far_box's rule, or the distance rule)
             if (far_d2 >= 0.0) {
                 if (xform) far += e > far_d2 ? 1 : 0;
-            } else if (!(h >= 0 && e * (gv.inv_h * gv.inv_h) < 2.2)) {
+            } else if (!(h >= 0 && e * (A.gv.inv_h * A.gv.inv_h) < 2.2)) {
                 // (a seed distance under 1.483 cells -- (e inv_h^2 < 2.2, rounding aside) -- spans at most
                 // 2 r / h + 2 < 5 cells an axis, at most 125 cells: never far; the rest are boxed exactly)
                 int b0[3], b1[3];
-                far += h >= 0 && e == e && e < INFINITY && complete_box(q, e, gv, box, b0, b1) ? 0 : 1;
+                far += h >= 0 && e == e && e < INFINITY && complete_box(q, e, A.gv, A.box, b0, b1) ? 0 : 1;
             }
         }
         double best = e; // (the pair's winner: the correspondence, or the second point)
@@ -1549,19 +1613,20 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
             double R1n = R1c;
             int2 pn = make_int2(cs4.z, cs4.w);
             certd = inside(e, R1c); // (one point: every other is beyond R1)
-            if (kDbg && !certd && ca.two && cs4.w >= 0 && R3c > 0.0) dcnt[3] += 1;
-            if (!certd && ca.two && cs4.w >= 0 && R3c > 0.0) {
+            if (kDbg && !certd && two && cs4.w >= 0 && R3c > 0.0) dcnt[3] += 1;
+            if (!certd && two && cs4.w >= 0 && R3c > 0.0) {
                 // the pair: the second point's record, the exact (D64, index) order of the two, every
                 // other point beyond R3
-                const double4 r2 = gv.pts[cs4.w];
+                const double4 r2 = at(A.gv.pts, cs4.w);
                 const double d2 = d64g(q[0], q[1], q[2], r2.x, r2.y, r2.z);
                 const int mi2 = (int)r2.w;
                 const bool swap = d2 < e || (d2 == e && (unsigned)mi2 < (unsigned)h);
                 const double db = swap ? d2 : e;
                 if (inside(db, R3c)) {
                     certd = true;
-                    // the next one-point bound: the pair's loser at its own distance (D64 >= |v|^2 (1 - 3u))
-                    const double lb = fmin(R3c, sqrt(swap ? e : d2) * (1.0 - 0x1.0p-40));
+                    // the next one-point bound: the pair's loser at its own distance (D64 >= |v|^2 (1 - 3u));
+                    // the square down to fp32, its root by v_sqrt_f32 (within two ulps) and 2^-21 of room
+                    const double lb = fmin(R3c, (double)__builtin_amdgcn_sqrtf(__double2float_rd(swap ? e : d2)) * (1.0 - 0x1.0p-21));
                     if (swap) {
                         best = d2;
                         bi = mi2;
@@ -1579,13 +1644,13 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                 const int4 ns = make_int4(__float_as_int(R1n > 0.0 ? __double2float_rd(R1n) : -1.0f),
                                           __float_as_int(R3c > 0.0 ? __double2float_rd(R3c) : -1.0f), pn.x, pn.y);
                 if (bi != h) {
-                    ca.state[t] = ns;
-                    idx[t] = bi;
-                    yx[t] = w[0];
-                    yy[t] = w[1];
-                    yz[t] = w[2];
+                    at(cstate, t) = ns;
+                    at(idx, t) = bi;
+                    at(yx, t) = w[0];
+                    at(yy, t) = w[1];
+                    at(yz, t) = w[2];
                 } else {
-                    *(int2 *)&ca.state[t] = make_int2(ns.x, ns.y); // (the pair as it was)
+                    *(int2 *)&at(cstate, t) = make_int2(ns.x, ns.y); // (the pair as it was)
                 }
             }
         }
@@ -1614,6 +1679,10 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         if (kDbg) dcnt[1] += nW;
         // ---- D: the walkers, at most 32 at a time, G = floor(64 / walkers) lanes each
         for (int b0 = 0; b0 < nW; b0 += 32) {
+            const Iter2Args &D = iter2_args();
+            const GridView gv = D.gv;
+            const int box = D.box;
+            const double skin = D.ca.skin;
             if (kDbg) dcnt[2] += 1;
             const int nb = min(32, nW - b0);
             // G lanes a walker: every lane the batch can use (17 walkers: 3 lanes each, not 2 -- a
@@ -1636,21 +1705,29 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                 wb = ws_sl[3];
                 wbi = ((const int *)(ws_sl + 7))[0];
             }
-            // the walk's squared radius: the seed distance, plus the skin the next bound needs
-            // (without the skin when that box is over `box`)
+            // the walk's radius rw: the seed distance s0 = fl(sqrt(wb)), plus the skin the next bound
+            // needs (without the skin when that box is over `box`).  The walk scans every point with
+            // D64 <= ew = fl(rw rw) (the seed alone: wb); ew itself is never formed: fl(sqrt(ew)) <=
+            // rw (1 + 2^-53)^2 <= rb = rw (1 + 2^-51) rounded, and the box and the prune take rb for
+            // the radius (the seed alone: rb = s0 = fl(sqrt(wb)), the root itself).  One fp64 root a
+            // batch, where the box, the prune and the next bound each took their own
+            // (tests/test_iter_bounds32.py restates the three)
             int c0[3] = {0, 0, 0}, c1[3] = {-1, -1, -1};
-            double ew = wb;
+            double rw = 0.0, rb = 0.0, s0 = 0.0;
             bool ok = false;
             if (wact && wbi >= 0 && wb == wb && wb < INFINITY) {
+                s0 = sqrt(wb);
                 if (cert_on) {
-                    const double rs = sqrt(wb) + ca.skin;
-                    ew = rs * rs;
-                    ok = complete_box(wq, ew, gv, box, c0, c1);
-                    if (!ok) ew = wb;
+                    rw = s0 + skin;
+                    rb = rw * (1.0 + 0x1.0p-51);
+                    ok = complete_box_r(wq, rb, gv, box, c0, c1);
                 }
-                if (!ok) ok = complete_box(wq, ew, gv, box, c0, c1);
+                if (!ok) {
+                    rw = rb = s0;
+                    ok = complete_box_r(wq, rb, gv, box, c0, c1);
+                }
             }
-            if (wact && ws == 0) slots[wu * kIter2Slot + 3] = ew; // (read back for the next bound)
+            if (wact && ws == 0) slots[wu * kIter2Slot + 3] = rw; // (read back for the next bound)
             int bk = -1;      // (the winner's grid position, when this lane scanned it)
             float a1 = INFINITY, a2 = INFINITY; // (the certificate: the two smallest others, a1 at k1)
             int k1 = -1;
@@ -1664,10 +1741,11 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                 const double o0 = wq[0] - gv.c32[0], o1 = wq[1] - gv.c32[1], o2 = wq[2] - gv.c32[2];
                 return std::ldexp(fmax(fabs(o0), fmax(fabs(o1), fabs(o2))), -23) + gv.em32;
             };
+            double eq = 0.0; // (kept for the next bound)
             if (ok) {
                 const float f0 = (float)(wq[0] - gv.c32[0]), f1 = (float)(wq[1] - gv.c32[1]), f2 = (float)(wq[2] - gv.c32[2]);
-                const double eq = eq_of();
-                const float T = seeded_bound32(wb, eq);
+                eq = eq_of();
+                const float T = seeded_bound32_root(s0, eq);
                 const int ny = c1[1] - c0[1] + 1, nrq = ny * (c1[2] - c0[2] + 1);
                 constexpr int kCand = ICP_ITER2_KCAND;
                 int cand[kCand], nc = 0;
@@ -1675,7 +1753,7 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                     double4 r[kCand];
 #pragma unroll
                     for (int j = 0; j < kCand; ++j)
-                        if (j < nc) r[j] = gv.pts[cand[j]];
+                        if (j < nc) r[j] = at(gv.pts, cand[j]);
 #pragma unroll
                     for (int j = 0; j < kCand; ++j) {
                         if (j >= nc) break;
@@ -1718,12 +1796,12 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                             }
                     }
                 };
-                // the sphere prune (nn_grid_iter_kernel's, radius sqrt(ew); tests/test_iter_prune.py)
+                // the sphere prune (nn_grid_iter_kernel's, radius rb >= sqrt(ew); tests/test_iter_prune.py)
                 const float inv_ny = 1.0f / (float)ny;
                 float tr[3];
 #pragma unroll
                 for (int a = 0; a < 3; ++a) tr[a] = (float)((wq[a] - gv.lo[a]) * gv.inv_h - (double)c0[a]);
-                const float rcf = (float)(sqrt(ew) * gv.inv_h * (1.0 + 0x1.0p-18) +
+                const float rcf = (float)(rb * gv.inv_h * (1.0 + 0x1.0p-18) +
                                           0x1.0p-20 * (1.0 + fabs((double)tr[0]) + fabs((double)tr[1]) + fabs((double)tr[2])));
                 const float rc2 = rcf * rcf, xroom = 0x1.0p-20f * (1.0f + fabsf(tr[0]));
                 const float xspan = (float)(c1[0] - c0[0] + 1);
@@ -1744,8 +1822,8 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                     x0 = max(x0, c0[0] + (int)floorf(fmaxf(tr[0] - xw, -1.0f)));
                     x1 = min(x1, c0[0] + (int)floorf(fminf(tr[0] + xw, xspan)));
                     if (x0 <= x1) {
-                        a0 = gv.start[row + x0];
-                        a1r = gv.start[row + x1 + 1];
+                        a0 = at(gv.start, row + x0);
+                        a1r = at(gv.start, row + x1 + 1);
                     }
                 };
                 { // (each lane its own rows, r = ws, ws + G, ...; the two-lane kernel's point-by-point
@@ -1780,7 +1858,7 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                                 // D64: a lower bound on its true square)
                                 double4 mm[KU];
 #pragma unroll
-                                for (int v = 0; v < KU; ++v) mm[v] = gv.pts[kk[v] >= 0 ? kk[v] : 0];
+                                for (int v = 0; v < KU; ++v) mm[v] = at(gv.pts, kk[v] >= 0 ? kk[v] : 0);
 #pragma unroll
                                 for (int v = 0; v < KU; ++v) {
                                     const double d = d64g(wq[0], wq[1], wq[2], mm[v].x, mm[v].y, mm[v].z);
@@ -1799,7 +1877,7 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
                             } else {
                                 float4 mm[KU];
 #pragma unroll
-                                for (int v = 0; v < KU; ++v) mm[v] = gv.pts32[kk[v] >= 0 ? kk[v] : 0];
+                                for (int v = 0; v < KU; ++v) mm[v] = at(gv.pts32, kk[v] >= 0 ? kk[v] : 0);
                                 test(mm, kk);
                             }
                         }
@@ -1851,19 +1929,20 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
             while (bigm) {
                 const int bl = __ffsll((long long)bigm) - 1;
                 bigm &= bigm - 1;
+                const Iter2Args &B = iter2_args();
                 const double bq[3] = {__shfl(wq[0], bl, 64), __shfl(wq[1], bl, 64), __shfl(wq[2], bl, 64)};
                 const double be = __shfl(wb, bl, 64);
                 const int bh = __shfl(wbi, bl, 64);
                 double b2 = INFINITY;
                 int bj = -1;
                 int d0[3], d1[3];
-                if (bh >= 0 && be == be && be < INFINITY && complete_box(bq, be, gv, budget, d0, d1)) {
+                if (bh >= 0 && be == be && be < INFINITY && complete_box(bq, be, B.gv, B.budget, d0, d1)) {
                     b2 = be;
                     bj = bh;
-                    scan_box<64>(bq, d0, d1, gv, lane, b2, bj);
+                    scan_box<64>(bq, d0, d1, B.gv, lane, b2, bj);
                 } else { // the exact fp64 scan of every point (a NaN query keeps index -1 -> 0)
-                    for (int k = lane; k < nm; k += 64) {
-                        const double4 m = m4[k];
+                    for (int k = lane; k < B.nm; k += 64) {
+                        const double4 m = B.m4[k];
                         lex_min(b2, bj, d64g(bq[0], bq[1], bq[2], m.x, m.y, m.z), k);
                     }
                 }
@@ -1876,43 +1955,49 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
             }
             // the walker's outputs: idx / y when changed, the next certificate, y for phase G
             if (wact && ws == 0) {
+                const Iter2Args &O = iter2_args();
+                int *const o_idx = O.idx;
+                double *const o_yx = O.yx, *const o_yy = O.yy, *const o_yz = O.yz;
+                int4 *const o_state = O.ca.state;
+                const double4 *const o_pts = O.gv.pts;
                 double *const rs_sl = slots + wu * kIter2Slot;
                 const int seed = ((const int *)(rs_sl + 7))[0], wh = ((const int *)(rs_sl + 7))[1];
                 const int wt = slot_t(c, wu);
                 if (wbi != seed) { // (a new winner: its coordinates from its record; y in the slot)
-                    const double4 m = whole ? m4[wbi] : gv.pts[bk];
+                    const double4 m = whole ? at(O.m4, wbi) : at(o_pts, bk);
                     rs_sl[4] = m.x;
                     rs_sl[5] = m.y;
                     rs_sl[6] = m.z;
                 }
                 if (wbi != wh) {
-                    idx[wt] = wbi;
-                    yx[wt] = rs_sl[4];
-                    yy[wt] = rs_sl[5];
-                    yz[wt] = rs_sl[6];
+                    at(o_idx, wt) = wbi;
+                    at(o_yx, wt) = rs_sl[4];
+                    at(o_yy, wt) = rs_sl[5];
+                    at(o_yz, wt) = rs_sl[6];
                 }
                 // the bound of the walk: the smaller of the radius it scanned (every point outside has
-                // D64 > ew, so a true distance above sqrt(ew) (1 - 2^-52)) and the bound of its
-                // smallest other outside the pair (two: a2, the second point being k1; one: a1).  A
-                // list value is a computed d32 (or a D64 rounded down, a larger lower bound): by
-                // seeded_bound32's analysis sqrt(d32) <= (|v| + sqrt(3) eq) (1 + 2^-24)^2.5, so the
-                // true distance |v| >= sqrt(d32) (1 - 2^-20) - sqrt(3) eq (1 + 2^-20).  A query the
-                // wave took whole gets no bound.
+                // D64 > ew = fl(rw rw) >= rw^2 (1 - 2^-53), so a true distance above rw (1 - 2^-51))
+                // and the bound of its smallest other outside the pair (two: a2, the second point
+                // being k1; one: a1).  A list value is a computed d32 (or a D64 rounded down, a larger
+                // lower bound): by seeded_bound32's analysis sqrt(d32) <= (|v| + sqrt(3) eq) (1 +
+                // 2^-24)^2.5, so |v| >= sqrt(d32) (1 - 2^-22.6) - sqrt(3) eq; the root is v_sqrt_f32's
+                // (within two ulps: a factor 1 - 2^-22 at worst), and the bound sqrtf(d32) (1 - 2^-20) -
+                // sqrt(3) eq (1 + 2^-20) keeps 2^-20.8 of room.  A query the wave took whole gets no bound.
                 if (cert_on) {
                     int4 ns = make_int4(kNoBound, kNoBound, -1, -1);
                     if (ok && !whole && bk >= 0) {
-                        const double u0 = sqrt(rs_sl[3]) * (1.0 - 0x1.0p-40); // (rs_sl[3]: the walk's ew)
+                        const double u0 = rs_sl[3] * (1.0 - 0x1.0p-40); // (rs_sl[3]: the walk's radius rw)
                         // (a list value's bound, the scan radius beyond the lists: a D64 rounded down gives
                         // |v| >= sqrt(a) (1 - 2^-52); an fp32 d32 needs the screen's error, -sqrt(3) eq)
-                        const double ec = ICP_ITER2_F64 ? 0.0 : 1.7320508075688774 * eq_of() * (1.0 + 0x1.0p-20);
+                        const double ec = ICP_ITER2_F64 ? 0.0 : 1.7320508075688774 * eq * (1.0 + 0x1.0p-20);
                         auto lower = [&](float a) {
-                            return a < INFINITY ? fmin(u0, sqrt((double)a) * (1.0 - 0x1.0p-20) - ec) : u0;
+                            return a < INFINITY ? fmin(u0, (double)__builtin_amdgcn_sqrtf(a) * (1.0 - 0x1.0p-20) - ec) : u0;
                         };
-                        const double r1 = lower(a1), r3 = ca.two ? lower(a2) : -1.0;
+                        const double r1 = lower(a1), r3 = two ? lower(a2) : -1.0;
                         ns = make_int4(__float_as_int(r1 > 0.0 ? __double2float_rd(r1) : -1.0f),
-                                       __float_as_int(r3 > 0.0 ? __double2float_rd(r3) : -1.0f), bk, ca.two ? k1 : -1);
+                                       __float_as_int(r3 > 0.0 ? __double2float_rd(r3) : -1.0f), bk, two ? k1 : -1);
                     }
-                    ca.state[wt] = ns;
+                    at(o_state, wt) = ns;
                 }
             }
             wave_sync();
@@ -1924,8 +2009,9 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
             y[2] = sl[6];
         }
         wave_sync(); // (the tile aliases the slots)
-        const double cp[3] = {st->shift_p[0], st->shift_p[1], st->shift_p[2]};
-        const double cy[3] = {st->shift_y[0], st->shift_y[1], st->shift_y[2]};
+        const IterState &sg = iter2_state(st);
+        const double cp[3] = {sg.shift_p[0], sg.shift_p[1], sg.shift_p[2]};
+        const double cy[3] = {sg.shift_y[0], sg.shift_y[1], sg.shift_y[2]};
         const double d[6] = {active ? q[0] - cp[0] : 0.0, active ? q[1] - cp[1] : 0.0, active ? q[2] - cp[2] : 0.0,
                              active ? y[0] - cy[0] : 0.0, active ? y[1] - cy[1] : 0.0, active ? y[2] - cy[2] : 0.0};
         double *const lf = tile + (u >> 5) * kIter2Tile;
@@ -1937,7 +2023,7 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
             else if (k == 15) leaf = 0.0 + ((d[3] * d[3] + d[4] * d[4]) + d[5] * d[5]);
             else if (k == 16) leaf = 0.0 + ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
             else leaf = active ? 0.0 + e : 0.0;
-            if (!active) leaf = 0.0;
+            // (a slot past the scene: d = +0.0, so every leaf above is +0.0 already -- no select a leaf)
             if (sub == 0) lf[k * kLeafStride + (u & 31)] = leaf;
         }
         wave_sync();
@@ -1961,6 +2047,8 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         }
         wave_sync(); // (the next task's slots alias the tiles)
     }
+    const Iter2Args &E = iter2_args();
+    unsigned long long *const dbg = E.dbg;
     if (kDbg && dbg && lane == 0)
         for (int f = 0; f < 4; ++f)
             if (dcnt[f]) atomicAdd(dbg + f, dcnt[f]);
@@ -1970,10 +2058,10 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         __syncthreads();
         if (threadIdx.x < kCanonCols) {
             const int k = threadIdx.x;
-            rows[(size_t)k * R + wr] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
+            E.rows[(size_t)k * R + wr] = (sh[0][k] + sh[1][k]) + (sh[2][k] + sh[3][k]);
         }
     } else if (s < S && lane < kCanonCols) { // the strand's sums (strands by column: k S + s)
-        rows[(size_t)lane * S + s] = acc;
+        E.rows[(size_t)lane * S + s] = acc;
     }
     // the far count (the policy's), the big boxes and the certificate's counts: one atomic each
     __shared__ int s_cnt[4][NW];
@@ -1993,12 +2081,20 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         int tot = 0;
         for (int w = 0; w < NW; ++w) tot += s_cnt[threadIdx.x][w];
         if (threadIdx.x < 2) {
-            int *dst = threadIdx.x == 0 ? far_acc : big_count;
+            int *dst = threadIdx.x == 0 ? E.far_acc : E.big_count;
             if (tot && dst) atomicAdd(dst, tot);
-        } else if (ca.counts && (NWG == 4 || s < S)) { // (this row's / strand's own counters: stream order separates the launches)
-            ca.counts[2 * (NWG == 4 ? wr : s) + (threadIdx.x - 2)] += (unsigned long long)tot;
+        } else if (E.ca.counts && (NWG == 4 || s < S)) { // (this row's / strand's own counters: stream order separates the launches)
+            E.ca.counts[2 * (NWG == 4 ? wr : s) + (threadIdx.x - 2)] += (unsigned long long)tot;
         }
     }
+}
+
+// at32's condition: every array the kernel indexes lies below 4 GiB (the scene's widest element
+// is 16 bytes, the model's 32, the grid's offsets 4)
+bool iter2_addr32(int n, int nm, const GridView &gv)
+{
+    const long long ncell = (long long)gv.g[0] * gv.g[1] * gv.g[2];
+    return n <= (1 << 28) && nm <= (1 << 27) && ncell < (1ll << 30);
 }
 
 } // namespace
@@ -2053,22 +2149,30 @@ bool launch_nn_grid_iter(int n, double *px, double *py, double *pz, double *yx, 
         }();
         const int S = canon_strands((size_t)n);
         if (strands) *strands = nwg == 1 ? S : 0;
-        if (ch == 2 && nwg == 1)
-            nn_grid_iter2_kernel<ICP_ITER2_KR, ICP_ITER2_KU, 2, 1><<<S, 64, 0, st>>>(
-                n, px, py, pz, yx, yy, yz, idx, st_dev, p32, gv, box, budget, nm, m4, rows, far_acc, far_d2, big_count,
-                xform, xcd_l, ca, dbg);
-        else if (ch == 2)
-            nn_grid_iter2_kernel<ICP_ITER2_KR, ICP_ITER2_KU, 2, 4><<<R, kBlock, 0, st>>>(
-                n, px, py, pz, yx, yy, yz, idx, st_dev, p32, gv, box, budget, nm, m4, rows, far_acc, far_d2, big_count,
-                xform, xcd_l, ca, dbg);
-        else if (nwg == 1)
-            nn_grid_iter2_kernel<ICP_ITER2_KR, ICP_ITER2_KU, 1, 1><<<S, 64, 0, st>>>(
-                n, px, py, pz, yx, yy, yz, idx, st_dev, p32, gv, box, budget, nm, m4, rows, far_acc, far_d2, big_count,
-                xform, xcd_l, ca, dbg);
-        else
-            nn_grid_iter2_kernel<ICP_ITER2_KR, ICP_ITER2_KU, 1, 4><<<R, kBlock, 0, st>>>(
-                n, px, py, pz, yx, yy, yz, idx, st_dev, p32, gv, box, budget, nm, m4, rows, far_acc, far_d2, big_count,
-                xform, xcd_l, ca, dbg);
+        const Iter2Args ka{n,      px, py, pz,   yx,      yy,     yz,        idx,   st_dev, p32, gv, box,
+                           budget, nm, m4, rows, far_acc, far_d2, big_count, xform, xcd_l,  ca,  dbg};
+        // ICP_ITER2_A32=0: 64-bit addresses whatever the sizes (A/B, tests)
+        static const bool a32_on = [] {
+            const char *e = getenv("ICP_ITER2_A32");
+            return !(e && e[0] == '0');
+        }();
+        const bool a32 = a32_on && iter2_addr32(n, nm, gv);
+        auto launch = [&](auto chc, auto nwgc, auto a32c) {
+            constexpr int kCh = decltype(chc)::value, kNwg = decltype(nwgc)::value;
+            nn_grid_iter2_kernel<ICP_ITER2_KR, ICP_ITER2_KU, kCh, kNwg, decltype(a32c)::value>
+                <<<kNwg == 1 ? S : R, 64 * kNwg, 0, st>>>(ka);
+        };
+        auto with_a32 = [&](auto chc, auto nwgc) {
+            if (a32) launch(chc, nwgc, std::true_type{});
+            else launch(chc, nwgc, std::false_type{});
+        };
+        using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
+        using I4 = std::integral_constant<int, 4>;
+        if (ch == 2 && nwg == 1) with_a32(I2{}, I1{});
+        else if (ch == 2) with_a32(I2{}, I4{});
+        else if (nwg == 1) with_a32(I1{}, I1{});
+        else with_a32(I1{}, I4{});
         return ca.state != nullptr;
     }
     if (!stage && wide_on && n <= kIterWideMax)

@@ -22,11 +22,12 @@ __device__ __forceinline__ int cell1(double x, double lo, double inv_h, int g)
     return cellt((x - lo) * inv_h, g);
 }
 
-// the cell box that must hold every m with D64(q, m) <= r2 (see the header); false if over budget
-__device__ __forceinline__ bool complete_box(const double q[3], double r2, const GridView &gv, int budget,
-                                             int c0[3], int c1[3])
+// the cell box that must hold every m with D64(q, m) <= R^2 (see the header); false if over budget.
+// R is the radius itself: a caller that holds a value at or above fl(sqrt(r2)) passes it and
+// spares the root (a larger R only grows the box)
+__device__ __forceinline__ bool complete_box_r(const double q[3], double R, const GridView &gv, int budget,
+                                               int c0[3], int c1[3])
 {
-    const double R = sqrt(r2);
     long long cells = 1;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -36,6 +37,12 @@ __device__ __forceinline__ bool complete_box(const double q[3], double r2, const
         cells *= (long long)(c1[a] - c0[a] + 1);
     }
     return cells <= budget;
+}
+
+__device__ __forceinline__ bool complete_box(const double q[3], double r2, const GridView &gv, int budget,
+                                             int c0[3], int c1[3])
+{
+    return complete_box_r(q, sqrt(r2), gv, budget, c0, c1);
 }
 
 // SeedArgs' far predicate for a moved point p' at squared seed distance d2
