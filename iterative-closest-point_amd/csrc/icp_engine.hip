@@ -2391,6 +2391,16 @@ int icp_run(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp
     return run_loop(ctx, max_iter, threshold, err_trace, res, true);
 }
 
+// ICP_FIRST_K1=1: the canonical first iteration's search and moments as one fused launch (A/B)
+static bool first_k1_env()
+{
+    static const bool on = [] {
+        const char *e = getenv("ICP_FIRST_K1");
+        return e && atoi(e) == 1;
+    }();
+    return on;
+}
+
 static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool no_tail)
 {
     TRY(check_ready(ctx, true));
@@ -2684,13 +2694,18 @@ static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_tr
         if (!ctx->h_far) HIPCHK(hipHostMalloc((void **)&ctx->h_far, sizeof(int), hipHostMallocDefault));
         // the first iteration's shift of p: the scene's centroid (all ranks'), where run_init put the
         // model's centre c -- a scene far from the model would otherwise cancel (D / sigma)^2 of the
-        // one-pass moments' precision (the shift of y stays c: the correspondences are model points)
+        // one-pass moments' precision (the shift of y follows the first search: the mean of a sample
+        // of its correspondences, launch_first_shift_y_sample below)
         launch_sum3(P.x, P.y, P.z, (int)n, red_target(ctx, n, ctx->sums + kSumScene), ctx->st, 1);
         red_finish(ctx, n, 3, ctx->sums + kSumScene);
         LAUNCHCHK("scene_sum");
         TRY(allreduce(ctx, ctx->sums + kSumScene, 3));
-        launch_first_shift(sd, ctx->sums + kSumScene, N, ctx->st);
-        LAUNCHCHK("first_shift");
+        // (set with the shift of y, after the first search; ICP_FIRST_K1=1 sums its first moments
+        // inside that search's launch and needs it now: its shift of y stays c)
+        if (first_k1_env()) {
+            launch_first_shift(sd, ctx->sums + kSumScene, N, ctx->st);
+            LAUNCHCHK("first_shift");
+        }
     }
     const bool lag_sched = lag || canon;
     // The fused grid iteration's exclusion certificate (icp_grid.hip): the state one fused
@@ -2863,10 +2878,7 @@ static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_tr
                 // (ICP_FIRST_K1=1; measured slower: the cell seeds' big boxes, 0.4% of the queries, are
                 // each the whole owning wave's serial work there, where the seeded pass queues them for
                 // a second pass of one wave each -- first iteration 0.53 against 0.37 ms, profiles/r05ab)
-                static const bool first_k1 = [] {
-                    const char *e = getenv("ICP_FIRST_K1");
-                    return e && atoi(e) == 1;
-                }();
+                static const bool first_k1 = first_k1_env();
                 const bool k1_first =
                     first_k1 && grid_iter_on() && enqueued == 0 && !xf_pending && !ctx->seeds_valid && cell_seed_on() &&
                     ctx->nn_mode == ICP_NN_CERTIFIED && ctx->nn_rule == ICP_NN_RULE_SQUARED && ctx->g_pts32 &&
@@ -2981,7 +2993,20 @@ static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_tr
                                       digest_order);
                     LAUNCHCHK("idx_digest");
                 }
-                if (enqueued == 0) { // the first moments in one pass around c, then the Horn step
+                if (enqueued == 0) { // the first moments in one pass around the first shifts, then the Horn step
+                    // the shift of y: the mean of a sample of these correspondences (all ranks'), where
+                    // run_init put the model's centre c -- matched points that are a small part of the
+                    // model, D from c, would otherwise cancel (D / sigma)^2 of the y moments' precision
+                    launch_first_shift_y_sample(ctx->idx, ctx->m4, Y.x, Y.y, Y.z, (int)n,
+                                                ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready,
+                                                ctx->sums + kSumYSample, lag ? nullptr : sd, ctx->sums + kSumScene, N,
+                                                ctx->st);
+                    LAUNCHCHK("first_shift_y_sample");
+                    if (lag) {
+                        TRY(allreduce(ctx, ctx->sums + kSumYSample, 4));
+                        launch_first_shifts(sd, ctx->sums + kSumYSample, ctx->sums + kSumScene, N, ctx->st);
+                        LAUNCHCHK("first_shifts");
+                    }
                     launch_canon_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, ctx->canon_rowbuf,
                                          ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
                     LAUNCHCHK("canon_moments");
@@ -3294,7 +3319,7 @@ static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_t
     std::memset(ctx->h_gate, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->gate_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
-    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first iteration's shifts: the model's centre)
+    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first iteration's pre-pass sums around the model's centre)
     if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
     const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
     ctx->stats.run_path_bits = 0;
@@ -3317,9 +3342,27 @@ static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_t
                 launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st, digest_order);
                 LAUNCHCHK("idx_digest");
             }
+            // the first iteration's shifts: a pre-pass of the same moments around c gives the kept
+            // pairs' centroids (all ranks'), and the pass below sums around those -- around c a scan
+            // D from the model's centre cancels (D / sigma)^2 of the moments' precision.  Later
+            // iterations get their shifts from the Horn step before them.
+            const bool pre_pass = enqueued == 0;
+            if (pre_pass) {
+                launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
+                                     ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
+                                     ctx->y_ready);
+                launch_gated_horn(ctx->gate_part, nb, ctx->sums, false, ctx->c, ctx->amb_count, sd, ctx->gate_state,
+                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st); // (the fold alone)
+                LAUNCHCHK("gated_moments (first shifts)");
+                if (ranks) TRY(allreduce(ctx, ctx->sums, kGateSums));
+                launch_gated_first_shift(sd, ctx->sums, ctx->st);
+                LAUNCHCHK("gated_first_shift");
+            }
             // 2-4. the gate, the kept pairs' moments and count, the Horn step with N = K
+            // (after the pre-pass y = m[idx] is stored: the pass streams it)
             launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
-                                 ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
+                                 ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
+                                 ctx->y_ready || pre_pass);
             launch_gated_horn(ctx->gate_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->gate_state,
                               ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
             LAUNCHCHK("gated_moments");

@@ -142,6 +142,20 @@ __global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__rest
     horn_step_body(res, K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
 }
 
+// The first gated iteration's shifts, from a pre-pass of the moments around the model's centre c
+// (where run_init put both shifts): the kept pairs' centroids, c + sum (p - c) / K and
+// c + sum (y - c) / K.  A partial-overlap scan D from c would otherwise cancel (D / sigma)^2 of the
+// one-pass moments' precision; sums of differences from c give the centroids to D eps, far closer
+// than a shift has to be.  sums: the folded (all ranks') pre-pass.  K = 0 leaves c (the step that
+// follows stops the run on the same count).
+__global__ void gated_first_shift_kernel(IterState *__restrict__ s, const double *__restrict__ sums)
+{
+    const double K = sums[kGateCount];
+    if (threadIdx.x >= 3 || s->done || !(K >= 1.0)) return;
+    s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / K;
+    s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / K;
+}
+
 // Modelled on the plain branch of transform_err_kernel: every point moves, the residual is
 // summed over the kept points (the gate's mask words).  A no-op once *done.
 __global__ __launch_bounds__(kBlock) void gated_transform_kernel(
@@ -220,6 +234,11 @@ void launch_gated_horn(const double *partials, int nblocks, double *sums, bool s
 {
     gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
                                             gate, h_gate, h_state);
+}
+
+void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
+{
+    gated_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums);
 }
 
 void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,

@@ -43,5 +43,8 @@ constexpr int kSumFar = 18;
 // [20..22] the scene's coordinate sums at a run's start (all ranks'): the canonical first
 // iteration's shift of p (its one-pass moments around the scene's own centroid)
 constexpr int kSumScene = 20;
+// [24..27] a sample of the first correspondences, their coordinate sums and count (all ranks'): the
+// canonical first iteration's shift of y
+constexpr int kSumYSample = 24;
 
 } // namespace icp

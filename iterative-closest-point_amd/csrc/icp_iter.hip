@@ -1771,6 +1771,78 @@ void launch_first_shift(IterState *st_dev, const double *sums3, double N, hipStr
     first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums3, N);
 }
 
+// The canonical first iteration's shifts, set after its search: of p the scene's centroid
+// (scene3 / N, as first_shift_kernel), of y the mean of a strided sample of the search's
+// correspondences (up to kFirstShiftSample = 256 of them, one workgroup).  The model's centre c, where
+// run_init put it, cancels (D / sigma)^2 of the one-pass y moments' precision when the matched
+// points are a small part of the model D away from c (a scan patch against a large map); the
+// sample's mean is within sigma / 16 of their centroid.  Any shift is exact in real arithmetic,
+// so the sample only has to land near the data.  out4 = (sum x, sum y, sum z, count); with s
+// the shifts are set here, else after the ranks' all-reduce of out4 (first_shifts_kernel).
+constexpr int kFirstShiftSample = kBlock; // (one correspondence a thread: an index load and a gather deep)
+__global__ __launch_bounds__(kBlock) void first_shift_y_sample_kernel(
+    const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ yx,
+    const double *__restrict__ yy, const double *__restrict__ yz, int n, const int *__restrict__ kpos,
+    const double4 *__restrict__ m4kd, int y_ready, double *out4, IterState *s, const double *__restrict__ scene3,
+    double N)
+{
+    const int stride = n > kFirstShiftSample ? n / kFirstShiftSample : 1;
+    const long long i = (long long)threadIdx.x * stride;
+    const double sc = s && threadIdx.x < 3 ? scene3[threadIdx.x] : 0.0;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    if (i < n) {
+        double4 m;
+        if (y_ready) m = make_double4(yx[i], yy[i], yz[i], 0.0);
+        else m = kpos ? m4kd[kpos[i]] : m4[idx[i]];
+        a[0] = m.x;
+        a[1] = m.y;
+        a[2] = m.z;
+        a[3] = 1.0;
+    }
+    // block_sum_store's tree, the totals kept in LDS for the shifts (no trip through global memory)
+    static_assert(kBlock == 256, "the four waves' rows are summed by hand below");
+    __shared__ double sh[kBlock / 64][4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] += __shfl_down(a[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sh[threadIdx.x >> 6][k] = a[k];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        const double tot = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
+        const double cnt = ((sh[0][3] + sh[1][3]) + sh[2][3]) + sh[3][3];
+        out4[k] = tot;
+        if (s && k < 3) {
+            s->shift_p[k] = sc / N;
+            if (cnt > 0.0) s->shift_y[k] = tot / cnt;
+        }
+    }
+}
+
+__global__ void first_shifts_kernel(IterState *__restrict__ s, const double *__restrict__ sums4,
+                                    const double *__restrict__ scene3, double N)
+{
+    if (threadIdx.x >= 3) return;
+    s->shift_p[threadIdx.x] = scene3[threadIdx.x] / N;
+    if (sums4[3] > 0.0) s->shift_y[threadIdx.x] = sums4[threadIdx.x] / sums4[3];
+}
+
+void launch_first_shift_y_sample(const int *idx, const double4 *m4, const double *yx, const double *yy,
+                                 const double *yz, int n, const int *kpos, const double4 *m4kd, bool y_ready,
+                                 double *out4, IterState *st_dev, const double *scene3, double N, hipStream_t st)
+{
+    first_shift_y_sample_kernel<<<1, kBlock, 0, st>>>(idx, m4, yx, yy, yz, n, kpos, m4kd, y_ready ? 1 : 0, out4, st_dev,
+                                                      scene3, N);
+}
+
+void launch_first_shifts(IterState *st_dev, const double *sums4, const double *scene3, double N, hipStream_t st)
+{
+    first_shifts_kernel<<<1, 64, 0, st>>>(st_dev, sums4, scene3, N);
+}
+
 void launch_run_init(IterState *st_dev, int *amb_count, hipStream_t st, const double *c)
 {
     run_init_kernel<<<1, 64, 0, st>>>(st_dev, amb_count, c ? c[0] : 0.0, c ? c[1] : 0.0, c ? c[2] : 0.0);

@@ -702,6 +702,14 @@ void launch_small_alignment(const double *p_aos, const double *y_aos, int n, dou
 void launch_run_init(IterState *st_dev, int *amb_count, hipStream_t st, const double *c = nullptr);
 // st->shift_p = sums3 / N (the scene's centroid: the canonical first iteration's shift of p)
 void launch_first_shift(IterState *st_dev, const double *sums3, double N, hipStream_t st);
+// The canonical first iteration's shifts, after its search: out4 = (sum, count) of a strided sample
+// of the correspondences y = m[idx] (or the stored y when y_ready).  st_dev non-null (one rank):
+// st->shift_y = their mean and st->shift_p = scene3 / N at once; else launch_first_shifts sets both
+// after the ranks' all-reduce of out4
+void launch_first_shift_y_sample(const int *idx, const double4 *m4, const double *yx, const double *yy,
+                                 const double *yz, int n, const int *kpos, const double4 *m4kd, bool y_ready,
+                                 double *out4, IterState *st_dev, const double *scene3, double N, hipStream_t st);
+void launch_first_shifts(IterState *st_dev, const double *sums4, const double *scene3, double N, hipStream_t st);
 
 // exact NN of nq (few) queries, one workgroup each: q_aos (3 x nq) in, idx and y = m[idx]
 // (3 x nq) out -- all three may be mapped host memory
@@ -738,6 +746,9 @@ void launch_gated_moments(const int *idx, const double4 *m4, const double *px, c
 // step with N = K = sums[kGateCount]
 void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st);
+// the first gated iteration's shifts: st->shift_p / shift_y (c, from run_init) += the folded
+// pre-pass sums' (p - c) / K and (y - c) / K, the kept pairs' centroids
+void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
 // p <- sR p + t for every point (p32 nullable); partial [sum over the kept points of ||y - p'||^2]
 void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                             int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
