@@ -364,6 +364,13 @@ int icp_get_model_order(icp_ctx *ctx, int32_t *kd_out);
  * the keys in that order.  Host arrays; runs on `device` (synchronous).  ICP_E_ARG for bits
  * outside [0, 32] or n > INT_MAX. */
 int icp_sort_pairs(int device, const uint32_t *keys, size_t n, int bits, uint32_t *keys_out, int32_t *order_out);
+/* The resident model's uniform grid (icp_grid.hip: launch_grid_build), exposed for its tests:
+ * g = the cells per axis, lo = the grid's origin, *inv_h = 1 / cell size (a point's cell per axis is
+ * clamp(floor((x - lo) * inv_h), 0, g - 1), its id (cz * g[1] + cy) * g[0] + cx); start (nullable,
+ * g[0] g[1] g[2] + 1 entries) = each cell's first position in the sorted point list; order
+ * (nullable, nm entries) = each sorted position's model index.  Call once with start = order =
+ * NULL for the sizes.  ICP_E_NO_MODEL without a model. */
+int icp_get_grid(icp_ctx *ctx, int g[3], double lo[3], double *inv_h, int32_t *start, int32_t *order);
 
 #ifdef __cplusplus
 }

@@ -161,6 +161,7 @@ struct icp_ctx {
     float *mm = nullptr;     // |m~|^2 rounded to fp32 (the MFMA's k = 0 operand)
     char *mimg16 = nullptr;  // f16 split image for the 32x32x16 f16 MFMA (1 KiB / 32 points)
     bool mimg16_pending = false; // (built at the first search that reads it: ensure_mimage16)
+    bool m32_pending = false;    // (m32, mperm, mm: built at their first reader, ensure_m32)
     float *mms16 = nullptr;  // |b_s|^2 (scaled) per model point, fp32
     double scale16 = 1.0;    // power of two: max |b_s| in [2^11, 2^12)
     size_t nm = 0, nm_pad = 0, m32_cap = 0, mperm_cap = 0, mm_cap = 0, mimg16_cap = 0, mms16_cap = 0;
@@ -885,6 +886,24 @@ static int ensure_mimage16(icp_ctx *ctx)
     return ICP_OK;
 }
 
+// The fp32 operand images (m32, its MFMA permutation mperm, the norms mm: the fp32 brute-force
+// filters and the brute-force resolver) at their first reader, from the resident SoA model -- the
+// caller's array is only promised until icp_run returns; the values are the same (one rounded
+// subtraction of c, one rounding to fp32, the same padding).  A registration the grid serves from
+// its first search never builds them (12 us at C4).
+static int ensure_m32(icp_ctx *ctx)
+{
+    if (!ctx->m32_pending) return ICP_OK;
+    TRY(grow(ctx, &ctx->m32, &ctx->m32_cap, ctx->nm_pad));
+    TRY(grow(ctx, &ctx->mperm, &ctx->mperm_cap, ctx->nm_pad));
+    TRY(grow(ctx, &ctx->mm, &ctx->mm_cap, ctx->nm_pad));
+    launch_model_f32_images_soa(ctx->model.x, ctx->model.y, ctx->model.z, (int)ctx->nm, (int)ctx->nm_pad, ctx->c,
+                                ctx->m32, (float *)ctx->mperm, ctx->mm, ctx->st);
+    LAUNCHCHK("model_f32_images");
+    ctx->m32_pending = false;
+    return ICP_OK;
+}
+
 // An unseeded search of a scene in slot order takes the seeded grid pass from cell seeds
 // (launch_nn_grid_cell_seed: the first minimum over the query's own cell, or the empty cell's
 // stand-in) instead of the ring search (nn_grid_search_kernel: rings of cells until one holds a
@@ -970,8 +989,10 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         ctx->stats.last_filter = ICP_FILTER_GRID;
         TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
         TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+        const bool cell_seeds = !seeded && slot_order && cell_seed_on();
+        if (!cell_seeds) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
-        if (!seeded && slot_order && cell_seed_on()) return grid_unseeded_slot(ctx, q, n, stop, ev1);
+        if (cell_seeds) return grid_unseeded_slot(ctx, q, n, stop, ev1);
         if (seeded) // (icp_run: the previous correspondence is each query's candidate; no ring search)
             launch_nn_grid_resolve_all((int)n, q.x, q.y, q.z, ctx->m4, grid_view(ctx), grid_budget(ctx), ctx->idx,
                                        ctx->amb_count + 1, ctx->fb_list, ctx->fb_T, ctx->st, stop, 0,
@@ -1002,6 +1023,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
             ctx->stats.last_filter = ICP_FILTER_GRID;
             TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
             TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+            if (!cell_seed_on()) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
             if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
             if (cell_seed_on()) return grid_unseeded_slot(ctx, q, n, stop, ev1);
             launch_nn_grid_search((int)n, q.x, q.y, q.z, grid_view(ctx), grid_budget(ctx), ctx->idx, ctx->amb_count + 1,
@@ -1013,6 +1035,8 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
             return ICP_OK;
         }
         if (l1 >= 2) TRY(ensure_mimage16(ctx));
+        // (the fp32 MFMA filter's mperm and mm; the brute-force resolver's m32)
+        if (l1 == 1 || !inline_nm) TRY(ensure_m32(ctx));
         if (l1 == 3 && ctx->bundle_pending && ws) ctx->stats.bundle_builds_in_run += 1; // (icp_run, mid-run)
         if (l1 == 3) TRY(ensure_bundle(ctx)); // (built at their first use)
         const bool gseed = l1 >= 2 && !seeded && grid_seed && ctx->g_pts;
@@ -1149,6 +1173,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         TRY(grow(ctx, &ctx->amb_hint, &ctx->amb_hint_cap, n));
         TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
         TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+        TRY(ensure_m32(ctx)); // (the fp32 filter and the brute-force resolver read m32)
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
         launch_nn_filter(q.f, (int)n, ctx->m32, (int)ctx->nm_pad, pl, pb, ps, pi, ctx->st, stop);
         if (ev1) HIPCHK(hipEventRecord(ev1, ctx->st));
@@ -1764,11 +1789,20 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     std::swap(ctx->model, ctx->model_alt);
     std::swap(ctx->m4, ctx->m4_alt);
     std::swap(ctx->m4_cap, ctx->m4_alt_cap);
-    TRY(grow(ctx, &ctx->m32, &ctx->m32_cap, nm_pad));
-    TRY(grow(ctx, &ctx->mperm, &ctx->mperm_cap, nm_pad));
-    TRY(grow(ctx, &ctx->mm, &ctx->mm_cap, nm_pad));
-    launch_model_f32_images(aos, (int)nm, (int)nm_pad, ctx->c, ctx->m32, (float *)ctx->mperm, ctx->mm, ctx->st);
-    LAUNCHCHK("model_f32_images");
+    // ICP_M32_LAZY=0 (A/B, read once): the fp32 images here, from the uploaded copy; else at
+    // their first reader (ensure_m32)
+    static const bool m32_lazy = [] {
+        const char *e = getenv("ICP_M32_LAZY");
+        return !(e && atoi(e) == 0);
+    }();
+    ctx->m32_pending = m32_lazy;
+    if (!m32_lazy) {
+        TRY(grow(ctx, &ctx->m32, &ctx->m32_cap, nm_pad));
+        TRY(grow(ctx, &ctx->mperm, &ctx->mperm_cap, nm_pad));
+        TRY(grow(ctx, &ctx->mm, &ctx->mm_cap, nm_pad));
+        launch_model_f32_images(aos, (int)nm, (int)nm_pad, ctx->c, ctx->m32, (float *)ctx->mperm, ctx->mm, ctx->st);
+        LAUNCHCHK("model_f32_images");
+    }
     ctx->scale16 = rm64 > 0.0 ? std::ldexp(1.0, (int)std::floor(std::log2(4096.0 / rm64))) : 1.0;
     while (rm64 * ctx->scale16 >= 4096.0) ctx->scale16 *= 0.5;
     ctx->mimg16_pending = true; // (the f16 image: at the first f16 / bundle search, ensure_mimage16)
@@ -3888,6 +3922,28 @@ int icp_sort_pairs(int device, const uint32_t *keys, size_t n, int bits, uint32_
               (!keys_out || hipMemcpy(keys_out, k1, n * 4, hipMemcpyDeviceToHost) == hipSuccess);
     ok = hipFree(buf) == hipSuccess && ok;
     return ok ? ICP_OK : ICP_E_HIP;
+}
+
+int icp_get_grid(icp_ctx *ctx, int g[3], double lo[3], double *inv_h, int32_t *start, int32_t *order)
+{
+    if (!ctx || !g || !lo || !inv_h) return ICP_E_ARG;
+    if (!ctx->has_model || !ctx->g_start || !ctx->g_pts) return fail(ctx, ICP_E_NO_MODEL, "no model grid");
+    HIPCHK(hipSetDevice(ctx->device));
+    for (int a = 0; a < 3; ++a) {
+        g[a] = ctx->grid.g[a];
+        lo[a] = ctx->grid.lo[a];
+    }
+    *inv_h = ctx->grid.inv_h;
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    if (start)
+        HIPCHK(hipMemcpy(start, ctx->g_start, sizeof(int32_t) * ((size_t)grid_cells(ctx->grid) + 1),
+                         hipMemcpyDeviceToHost));
+    if (order) { // (each sorted point's record carries its model index in w)
+        std::vector<double> pts(4 * ctx->nm);
+        HIPCHK(hipMemcpy(pts.data(), ctx->g_pts, sizeof(double) * 4 * ctx->nm, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < ctx->nm; ++k) order[k] = (int32_t)pts[4 * k + 3];
+    }
+    return ICP_OK;
 }
 
 int icp_get_stats(const icp_ctx *ctx, icp_stats *out)

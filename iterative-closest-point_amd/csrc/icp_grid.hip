@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void grid_keys_kernel(const double *__restr
     const int cy = cell1(my[i], gv.lo[1], gv.inv_h, gv.g[1]);
     const int cz = cell1(mz[i], gv.lo[2], gv.inv_h, gv.g[2]);
     key[i] = (unsigned)((cz * gv.g[1] + cy) * gv.g[0] + cx);
-    val[i] = i;
+    if (val) val[i] = i; // (nullable: the sort's first pass takes the positions as the values)
 }
 
 // start[c] = the first sorted position whose cell id is >= c (c = 0 .. ncell: start[ncell] = nm)
@@ -76,11 +76,53 @@ __global__ __launch_bounds__(kBlock) void grid_starts_kernel(const unsigned *__r
     start[c] = lo;
 }
 
+// skey (nullable: grid_starts_kernel then writes the starts): the sorted cell ids.  Position k
+// knows every start between its neighbour's id and its own: start[c] = k for c in
+// (skey[k - 1], skey[k]] (-1 before position 0), and the last position also start[c] = nm for c in
+// (skey[nm - 1], ncell] -- the same values as the binary search, each cell written once.  Empty
+// cells make a range longer than one; a range of more than kFillThread cells (a model on a plane
+// or a line, two far clumps) is filled by the whole workgroup, 16 bytes a lane where aligned.
+constexpr int kFillThread = 16;
+
 __global__ __launch_bounds__(kBlock) void grid_gather_kernel(const double4 *__restrict__ m4, int nm,
                                                            const int *__restrict__ sval, double4 *__restrict__ pts,
-                                                           float4 *__restrict__ pts32, double c0, double c1, double c2)
+                                                           float4 *__restrict__ pts32, double c0, double c1, double c2,
+                                                           const unsigned *__restrict__ skey, int ncell,
+                                                           int *__restrict__ start)
 {
+    __shared__ int s_n;
+    __shared__ int s_lo[kBlock + 1], s_hi[kBlock + 1], s_val[kBlock + 1]; // (long ranges: [lo, hi) <- val)
     const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (skey) {
+        if (threadIdx.x == 0) s_n = 0;
+        __syncthreads();
+        if (k < nm) {
+            const int cur = (int)skey[k], prev = k ? (int)skey[k - 1] : -1;
+            // (two ranges at the last position: its own cells, then the cells after every point)
+            for (int part = 0; part < (k == nm - 1 ? 2 : 1); ++part) {
+                const int lo = part ? cur + 1 : prev + 1, hi = part ? ncell + 1 : cur + 1, val = part ? nm : k;
+                if (hi - lo <= kFillThread) {
+                    for (int c = lo; c < hi; ++c) start[c] = val;
+                } else {
+                    const int s = atomicAdd(&s_n, 1); // (at most kBlock + 1 in a workgroup; any order: disjoint cells)
+                    s_lo[s] = lo;
+                    s_hi[s] = hi;
+                    s_val[s] = val;
+                }
+            }
+        }
+        __syncthreads();
+        const int nlong = s_n;
+        const bool al16 = ((size_t)start & 15) == 0;
+        for (int s = 0; s < nlong; ++s) {
+            const int lo = s_lo[s], hi = s_hi[s], val = s_val[s];
+            const int a = al16 ? min(hi, (lo + 3) & ~3) : hi, b = max(a, hi & ~3); // [a, b): whole aligned int4
+            for (int c = lo + (int)threadIdx.x; c < a; c += kBlock) start[c] = val;
+            for (int c = a + 4 * (int)threadIdx.x; c < b; c += 4 * kBlock)
+                *(int4 *)(start + c) = make_int4(val, val, val, val);
+            for (int c = b + (int)threadIdx.x; c < hi; c += kBlock) start[c] = val;
+        }
+    }
     if (k >= nm) return;
     const int i = sval[k];
     const double4 m = m4[i]; // (one 32-byte record: the SoA streams would cost a line each)
@@ -2291,12 +2333,20 @@ int launch_grid_build(const double *mx, const double *my, const double *mz, cons
     int *v0 = (int *)(k1 + nm), *v1 = v0 + nm;
     size_t temp_bytes = bytes - grid_keys_bytes(nm);
     const int g = (nm + kBlock - 1) / kBlock;
+    // ICP_GRID_FUSED=0 (A/B, read once): the build before -- the identity values written out for
+    // the sort's first pass, the starts by grid_starts_kernel's binary search
+    static const bool fused = [] {
+        const char *e = getenv("ICP_GRID_FUSED");
+        return !(e && atoi(e) == 0);
+    }();
+    if (fused) v0 = nullptr;
     grid_keys_kernel<<<g, kBlock, 0, st>>>(mx, my, mz, nm, gv, k0, v0);
     if (sort_pairs_u32((char *)scratch + grid_keys_bytes(nm), temp_bytes, k0, k1, v0, v1, nm, cell_bits(ncell), st) !=
         hipSuccess)
         return -1;
-    grid_starts_kernel<<<(int)((ncell + kBlock) / kBlock), kBlock, 0, st>>>(k1, nm, (int)ncell, start);
-    grid_gather_kernel<<<g, kBlock, 0, st>>>(m4, nm, v1, pts, pts32, p.c32[0], p.c32[1], p.c32[2]);
+    if (!fused) grid_starts_kernel<<<(int)((ncell + kBlock) / kBlock), kBlock, 0, st>>>(k1, nm, (int)ncell, start);
+    grid_gather_kernel<<<g, kBlock, 0, st>>>(m4, nm, v1, pts, pts32, p.c32[0], p.c32[1], p.c32[2],
+                                             fused ? k1 : nullptr, (int)ncell, start);
     return 0;
 }
 

@@ -769,6 +769,9 @@ void launch_model_stats(const double *aos, int n, double *scratch, double *out, 
 // m32 (centred fp32, nm_pad rows, padding = far points), mperm (the f32 MFMA operand order), mm
 void launch_model_f32_images(const double *aos, int nm, int nm_pad, const double c[3], float4 *m32, float *mperm,
                              float *mm, hipStream_t st);
+// the same images from the resident SoA model (the same values)
+void launch_model_f32_images_soa(const double *x, const double *y, const double *z, int nm, int nm_pad,
+                                 const double c[3], float4 *m32, float *mperm, float *mm, hipStream_t st);
 // *diff += points of the AoS cloud that differ bit for bit from the resident SoA cloud
 void launch_model_compare(const double *aos, int n, const double *x, const double *y, const double *z, int *diff,
                           hipStream_t st);

@@ -121,7 +121,12 @@ __global__ __launch_bounds__(kBlock) void stats_fold_kernel(const double *__rest
 // The fp32 operand images (the host statement was icp_set_model's loops, same arithmetic):
 // m32[P] = (float)(m - c) (padding: 1e18), mm[P] = (float)(|v|^2 in fp64) (padding 1e30), and
 // the MFMA permutation: component k of point P = 64 g + 16 t + i at float g*256 + k*64 + 4 i + t.
-__global__ __launch_bounds__(kBlock) void model_f32_images_kernel(const double *__restrict__ aos, int nm, int nm_pad,
+// SOA: from the resident SoA model (x, y, z streams; aos is x) instead of the uploaded AoS copy --
+// the same values (ensure_m32: the images at their first reader, when the caller's array may be gone)
+template <bool SOA>
+__global__ __launch_bounds__(kBlock) void model_f32_images_kernel(const double *__restrict__ aos,
+                                                                  const double *__restrict__ sy,
+                                                                  const double *__restrict__ sz, int nm, int nm_pad,
                                                                   double cx, double cy, double cz,
                                                                   float4 *__restrict__ m32, float *__restrict__ mperm,
                                                                   float *__restrict__ mm)
@@ -131,9 +136,9 @@ __global__ __launch_bounds__(kBlock) void model_f32_images_kernel(const double *
     const bool real = P < nm;
     float4 v = make_float4(1.0e18f, 1.0e18f, 1.0e18f, 0.f);
     if (real) {
-        v.x = (float)(aos[3 * (size_t)P] - cx);
-        v.y = (float)(aos[3 * (size_t)P + 1] - cy);
-        v.z = (float)(aos[3 * (size_t)P + 2] - cz);
+        v.x = (float)((SOA ? aos[P] : aos[3 * (size_t)P]) - cx);
+        v.y = (float)((SOA ? sy[P] : aos[3 * (size_t)P + 1]) - cy);
+        v.z = (float)((SOA ? sz[P] : aos[3 * (size_t)P + 2]) - cz);
     }
     m32[P] = v;
     const float mmv = real ? (float)((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z) : 1.0e30f;
@@ -442,8 +447,15 @@ void launch_model_stats(const double *aos, int n, double *scratch, double *out, 
 void launch_model_f32_images(const double *aos, int nm, int nm_pad, const double c[3], float4 *m32, float *mperm,
                              float *mm, hipStream_t st)
 {
-    model_f32_images_kernel<<<(nm_pad + kBlock - 1) / kBlock, kBlock, 0, st>>>(aos, nm, nm_pad, c[0], c[1], c[2], m32,
-                                                                              mperm, mm);
+    model_f32_images_kernel<false><<<(nm_pad + kBlock - 1) / kBlock, kBlock, 0, st>>>(aos, nullptr, nullptr, nm, nm_pad,
+                                                                                     c[0], c[1], c[2], m32, mperm, mm);
+}
+
+void launch_model_f32_images_soa(const double *x, const double *y, const double *z, int nm, int nm_pad,
+                                 const double c[3], float4 *m32, float *mperm, float *mm, hipStream_t st)
+{
+    model_f32_images_kernel<true><<<(nm_pad + kBlock - 1) / kBlock, kBlock, 0, st>>>(x, y, z, nm, nm_pad, c[0], c[1],
+                                                                                    c[2], m32, mperm, mm);
 }
 
 void launch_model_compare(const double *aos, int n, const double *x, const double *y, const double *z, int *diff,

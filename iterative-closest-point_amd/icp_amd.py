@@ -67,7 +67,7 @@ EXPORTED = [
     "icp_ensure_model", "icp_subtract_col", "icp_get_indices", "icp_set_index_digest",
     "icp_get_index_digest", "icp_set_cert_audit", "icp_set_run_mode", "icp_set_nn_rule",
     "icp_get_comm_info", "icp_set_bundle_counters", "icp_get_bundle_counters", "icp_get_model_order",
-    "icp_bundle_audit", "icp_sort_pairs",
+    "icp_bundle_audit", "icp_sort_pairs", "icp_get_grid",
     "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
 ]
 
@@ -165,6 +165,8 @@ def lib() -> C.CDLL:
     L.icp_subtract_col.argtypes = [vp, dp, sz, dp, dp]
     L.icp_get_indices.argtypes = [vp, C.POINTER(C.c_int32)]
     L.icp_get_model_order.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.icp_get_grid.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.icp_sort_pairs.argtypes = [C.c_int, C.POINTER(C.c_uint32), sz, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.icp_set_index_digest.argtypes = [vp, sz]
     L.icp_get_index_digest.argtypes = [vp, C.POINTER(C.c_uint64), sz]
@@ -460,6 +462,20 @@ class Context:
         kd = np.empty(nm, dtype=np.int32)
         self._check(lib().icp_get_model_order(self._h, kd.ctypes.data_as(C.POINTER(C.c_int32))))
         return kd
+
+    def get_grid(self, nm: int) -> dict:
+        """The resident model's grid (icp_get_grid): g (3 ints), lo (3 doubles), inv_h, start
+        (ncell + 1 int32), order (nm int32: each sorted position's model index)."""
+        g = (C.c_int * 3)()
+        lo = (C.c_double * 3)()
+        inv_h = C.c_double()
+        self._check(lib().icp_get_grid(self._h, g, lo, C.byref(inv_h), None, None))
+        ncell = g[0] * g[1] * g[2]
+        start = np.empty(ncell + 1, dtype=np.int32)
+        order = np.empty(nm, dtype=np.int32)
+        self._check(lib().icp_get_grid(self._h, g, lo, C.byref(inv_h), start.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       order.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(g=np.array(g[:]), lo=np.array(lo[:]), inv_h=inv_h.value, start=start, order=order)
 
     def set_index_digest(self, cap: int):
         self._check(lib().icp_set_index_digest(self._h, cap))
