@@ -1,0 +1,451 @@
+// icp_engine.h — private to the engine's two translation units: icp_engine.hip (the context, the
+// model and scene set-up, the searches, the per-operation surface) and icp_run.hip (icp_run's
+// loops).  The context, the few types the two share, the error macros, the run path's knob table
+// and the declarations of the helpers one file calls in the other.  The helpers are icp::engine
+// and hidden: the shared library exports the C ABI (include/icp_capi.h) and nothing of this.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <string>
+#include <vector>
+
+#include "icp_canon.h"
+#include "icp_kernels.h"
+
+namespace icp {
+namespace engine {
+
+struct DevCloud {
+    double *x = nullptr, *y = nullptr, *z = nullptr;
+    float4 *f = nullptr;
+    size_t n = 0, cap = 0;
+};
+
+} // namespace engine
+} // namespace icp
+
+// (a private header: both files that include it work in these namespaces)
+using namespace icp;
+using namespace icp::engine;
+
+struct icp_ctx {
+    int device = 0;
+    int nn_mode = ICP_NN_CERTIFIED;
+    int rank = 0, world = 1;
+    bool allow_unequal = false;
+    hipStream_t st = nullptr;
+    ncclComm_t comm = nullptr;
+    icp_allreduce_fn host_reduce = nullptr; // alternative to RCCL (icp_ctx_create_sharded)
+    void *host_reduce_user = nullptr;
+    icp_progress_fn progress_fn = nullptr; // (icp_set_progress: each recorded iteration's error, as it ends)
+    void *progress_user = nullptr;
+    int progress_next = 0; // (the next iteration of the current run to report)
+
+    // model (replicated)
+    DevCloud model;
+    float4 *m32 = nullptr;   // centred fp32 model, padded to nm_pad with far points
+    float4 *mperm = nullptr; // same, (mm, x, y, z) permuted for the MFMA operands
+    float *mm = nullptr;     // |m~|^2 rounded to fp32 (the MFMA's k = 0 operand)
+    char *mimg16 = nullptr;  // f16 split image for the 32x32x16 f16 MFMA (1 KiB / 32 points)
+    bool mimg16_pending = false; // (built at the first search that reads it: ensure_mimage16)
+    bool m32_pending = false;    // (m32, mperm, mm: built at their first reader, ensure_m32)
+    float *mms16 = nullptr;  // |b_s|^2 (scaled) per model point, fp32
+    double scale16 = 1.0;    // power of two: max |b_s| in [2^11, 2^12)
+    size_t nm = 0, nm_pad = 0, m32_cap = 0, mperm_cap = 0, mm_cap = 0, mimg16_cap = 0, mms16_cap = 0;
+    int nn_variant = ICP_NN_VARIANT_AUTO;
+    double c[3] = {0, 0, 0}; // centring point = model centroid
+    // host copy of the model (AoS): kept when the one-launch paths can take it (small models),
+    // downloaded on demand for the CPU rule's host fix-up, else empty (0.2 GB at 2^23 points)
+    std::vector<double> model_host;
+    double rm = 0.0;         // max |centred fp32 model coordinate|
+    // the model's preparation on the device (icp_model.hip): stats scratch, results (device and
+    // pinned host), the kd builder's plan and scratch, the compare counter of icp_ensure_model
+    double *mstat_part = nullptr, *mstat_out = nullptr, *h_mstat = nullptr;
+    int *cmp_diff = nullptr;
+    KdPlan kd_plan;
+    char *kd_scratch = nullptr;
+    size_t kd_scratch_cap = 0;
+    bool has_model = false;
+
+    // scene (this rank's shard), its correspondences
+    DevCloud scene, Y;
+    size_t np_total = 0;
+    bool has_scene = false;
+
+    // scratch clouds for the per-operation surface
+    DevCloud qa, qb;
+
+    // NN workspace
+    int *idx = nullptr;
+    size_t idx_cap = 0;
+    void *part = nullptr, *part2 = nullptr;
+    size_t part_cap = 0, part2_cap = 0;
+    int *amb1 = nullptr;           // queue of the MFMA certificate
+    size_t amb1_cap = 0;
+    int *amb_count = nullptr, *amb_list = nullptr;
+    double *amb_T = nullptr;
+    size_t amb_cap = 0;
+    // exact grid resolver (icp_grid.hip): model grid + the queues around it
+    GridParams grid{};
+    int *g_start = nullptr;
+    char *g_sort = nullptr; // the build's sort scratch (launch_grid_build)
+    size_t g_sort_cap = 0;
+    double4 *g_pts = nullptr;
+    float4 *g_pts32 = nullptr; // (the fp32 image of g_pts: the seeded grid search's prefilter)
+    size_t g_pts32_cap = 0;
+    size_t g_start_cap = 0, g_pts_cap = 0;
+    IterState *iter_state = nullptr; // device-resident loop state (icp_iter.hip)
+    size_t iter_state_cap = 0;
+    IterState *h_iter = nullptr;     // mapped host mirror of the last recorded iteration's state
+    IterState *d_iter_mirror = nullptr; // its device address
+    double *h_trace = nullptr, *d_trace = nullptr; // mapped host error trace
+    size_t trace_cap = 0;
+    int *h_sig = nullptr, *d_sig = nullptr; // mapped completion word of the per-operation calls
+    int sig_ticket = 0;
+    double *h_few = nullptr;         // mapped host staging of the few-query path: q (3 x kFewQueries),
+    double *d_few = nullptr;         //   y (3 x kFewQueries), idx (kFewQueries ints); device address
+    int *h_flags = nullptr;          // mapped host (done, iter, ticket, -) per in-flight iteration
+    int *d_flags = nullptr;          // its device address (err_step writes it directly)
+    int flag_ticket = 0;             // last ticket handed to an iteration
+    double *err_trace_dev = nullptr;
+    size_t err_trace_cap = 0;
+    std::vector<hipEvent_t> iter_ev; // per ring slot: (nn begin, nn end, -, all-reduce begin, all-reduce end)
+    unsigned long long *digest = nullptr; // icp_set_index_digest: 3 x digest_cap per-iteration digests
+    unsigned *cert_audit = nullptr;       // icp_set_cert_audit: (max err ratio, min margin) float bits, count
+    size_t digest_cap = 0;
+    double4 *m4 = nullptr;      // model as (x, y, z, 0) doubles: one read per random gather
+    size_t m4_cap = 0;
+    // the next model's SoA copy and double4 rows, built while its checks are read back and
+    // swapped with model / m4 when they pass (set_model_staged)
+    DevCloud model_alt;
+    double4 *m4_alt = nullptr;
+    size_t m4_alt_cap = 0;
+    hipEvent_t mstat_ev = nullptr; // (the checks' read-back)
+    unsigned *seed16 = nullptr; // seeded f16 filter: per-query shift (icp_run iterations >= 2)
+    size_t seed16_cap = 0;
+    bool last_search_timed = false; // the per-operation search recorded its events
+    bool seeds_valid = false;   // idx holds the previous search over the resident scene
+    // seedd_valid: b_seedd holds D64(p_j, m[idx_j]) of the resident scene (the last icp_run took
+    // the search policy, whose every transform writes it), and last_far that run's last far count
+    // (SeedArgs::far_acc): the next run's policy starts from them instead of two bundle searches
+    bool seedd_valid = false;
+    int last_far = -1;
+    // second_pass_items (icp_run's policy searches): the grid of the seeded search's second pass
+    // is sized for this many queued queries (0: min(n, 4096)) -- the far count the host last saw
+    int second_pass_items = 0;
+    int last_q2 = -1; // the last run's last observed second-pass queue (IterState::queued2)
+    int *amb1_hint = nullptr, *amb_hint = nullptr;    // candidates of the level-1 / level-2 queues
+    int *fb_list = nullptr;                           // queries the grid hands back
+    double *fb_T = nullptr;
+    size_t amb1_hint_cap = 0, amb_hint_cap = 0, fb_list_cap = 0, fb_T_cap = 0;
+
+    // reductions
+    double *partials = nullptr;
+    double *err_part = nullptr; // (multi-rank icp_run: the transform's residual partials, icp_run.hip)
+    size_t err_part_cap = 0;
+    double *canon_rowbuf = nullptr; // (icp_run over a scene in slot order: the canonical rows, icp_canon.h)
+    int *canon_ticket = nullptr;    // (the fold's workgroup ticket, CanonStep::fold_ticket)
+    size_t canon_rowbuf_cap = 0;
+    int *h_far = nullptr; // (pinned: a far count read back once, canon_path's hold_first)
+    double *sums = nullptr;
+    double *h_sums = nullptr; // pinned
+    int *h_amb = nullptr;     // pinned
+    double *stage = nullptr;
+    size_t stage_cap = 0;
+    // small host <-> device transfers: a mapped pinned buffer the conversion kernels read and
+    // write directly (no pageable-copy staging); bump-allocated, recycled after a sync
+    double *h_io = nullptr, *d_io = nullptr;
+    size_t io_cap = 0, io_off = 0;
+    bool io_pending = false; // a queued kernel may still read h_io
+
+    // ICP_NN_RULE_CPU_SQRT: the near-tie window of every search (launch_nn_cpu_rule_window)
+    int nn_rule = ICP_NN_RULE_SQUARED;
+    CpuRuleEntry *cr_entries = nullptr;
+    int *cr_count = nullptr;
+    int *cr_fix = nullptr; // the fix-up's (query, index) pairs
+    size_t cr_cap = 0, cr_count_cap = 0, cr_fix_cap = 0;
+
+    // one-launch registration of small clouds (icp_iter.hip, launch_icp_persistent)
+    int run_mode = ICP_RUN_AUTO;
+    int n_cu = 0;                    // compute units
+    size_t lds_per_cu = 0, lds_per_block = 0;
+    double *pers_part = nullptr;     // 2 x kBlock x kNumSums published partials
+    unsigned *pers_sync = nullptr;   // arrival counter, abort word (+ padding to 16 B)
+    size_t pers_part_cap = 0, pers_sync_cap = 0;
+    double *tail_part = nullptr;     // fused mid-size tail: published partials (18 x kTailMaxBlocks)
+    unsigned *tail_sync = nullptr;   // its barrier words
+    double *mid_q4 = nullptr;        // mid-size one-launch loop: published queries (4 per point)
+    int *mid_res = nullptr;          // and their correspondences
+    int *mid_perm = nullptr;         // its search order (each point's row)
+    char *mid_cnt = nullptr;         // the order's scratch (radix sort)
+    double m_lo[3] = {0, 0, 0}, m_hi[3] = {0, 0, 0}; // the model's box
+    double pm_seed_big = 0.0;        // PersistArgs::seed_big for this model
+    size_t mid_q4_cap = 0, mid_res_cap = 0, mid_perm_cap = 0, mid_cnt_cap = 0;
+    size_t tail_part_cap = 0, tail_sync_cap = 0;
+    bool pers_sync_valid = false;    // the barrier words hold pers_epoch_base barriers of grid pers_grid
+    unsigned pers_epoch_base = 0;
+    int pers_grid = 0;
+    unsigned long long *pers_stamps = nullptr; // ICP_PERSIST_STAMPS=1: phase stamps
+    size_t pers_stamps_cap = 0;
+    // the model in Morton order for the one-launch NN (models <= kPersistMaxModel points):
+    // x[nm] | y[nm] | z[nm] | 64-point block boxes (lo xyz, hi xyz) | original index (int32)
+    double *pm_img = nullptr;
+    size_t pm_img_cap = 0, pm_blocks = 0;
+    // bundle-bound filter (icp_bundle.hip): the model's kd-ordered bundle and pair images, built
+    // per model of >= kBundleMinModel points; the query order of the scene it searches
+    char *b_img = nullptr, *b_pimg = nullptr; // 1 KiB per 32 bundles; 1 KiB per bundle
+    int *b_kd_orig = nullptr;                 // original index per kd position (nm: padding)
+    double4 *b_bctr = nullptr, *b_blk = nullptr; // per bundle / per 32-bundle block: centre, radius
+    int *b_kd = nullptr;                      // the kd order (upload staging)
+    int nb_pad = 0;                           // bundles (whole LDS tiles)
+    // the bundle filter's kd order and images are built at their first use (ensure_bundle):
+    // pending from icp_set_model on until then (a run whose searches all take the grid never
+    // builds them)
+    bool bundle_pending = false;
+    size_t b_img_cap = 0, b_pimg_cap = 0, b_kd_orig_cap = 0, b_bctr_cap = 0, b_blk_cap = 0, b_kd_cap = 0;
+    int *q_order = nullptr;                   // the bundle filter's query order (launch_query_order)
+    int *q_pos = nullptr;                     // its inverse (query j's slot)
+    size_t q_pos_cap = 0;
+    char *q_order_tmp = nullptr;
+    size_t q_order_cap = 0, q_order_tmp_cap = 0;
+    const double *q_order_src = nullptr;      // the cloud q_order was computed for (its x array)
+    size_t q_order_n = 0;
+    unsigned long long *b_counters = nullptr; // icp_set_bundle_counters: the filter's executed work
+    char *b_qop = nullptr, *b_gop = nullptr;  // v2: per-slot query operands, per-group bounds
+    double4 *b_qraw = nullptr;                // v2: per-slot query coordinates, index, seed
+    int *b_glist = nullptr;                   // v2: fired-block list overflow
+    double *b_seedd = nullptr;                // v2: per point, D64 to its seed (icp_run's transform)
+    size_t b_seedd_cap = 0;
+    // the fused grid iteration's exclusion certificate (CertArgs): per point in slot order the
+    // bound and the pair; counts = (certified, walked) summed over the run (device)
+    hipEvent_t order_ev = nullptr; // icp_set_*_device_stream: the producer stream's point to wait for
+    int4 *cert_state = nullptr;
+    size_t cert_state_cap = 0;
+    unsigned long long *cert_counts = nullptr; // (2 per strand: certified, walked -- CertArgs::counts)
+    size_t cert_counts_cap = 0;
+    int cert_counts_rows = 0; // (strands the runs since the last fold counted into cert_counts, not yet in stats)
+    char *tail_backup = nullptr;              // icp_run with the fused tail: the starting scene / idx
+    size_t tail_backup_cap = 0;
+    double4 *b_gctr = nullptr;                // v2: per-group (centre, D)
+    int *b_cand = nullptr, *b_cand_n = nullptr; // v2: per filter workgroup, its candidate blocks
+    int *b_wsplit = nullptr, *b_tctl = nullptr; // v2: per filter workgroup its tasks; (count, counter)
+    int2 *b_tasks = nullptr;                  // v2: the task list
+    size_t b_gctr_cap = 0, b_cand_cap = 0, b_cand_n_cap = 0, b_wsplit_cap = 0, b_tctl_cap = 0, b_tasks_cap = 0;
+    size_t b_qop_cap = 0, b_gop_cap = 0, b_qraw_cap = 0, b_glist_cap = 0, b_counters_rows = 0;
+    // The resident scene in slot order (scene_in_slot_order): point s of the scene (and idx[s]
+    // while seeds_valid) is the caller's point s_order[s].  icp_get_scene / icp_get_indices and
+    // the index digests map back; every other per-point pass is order-agnostic.
+    // the local pair test (icp_bundle_rec.h): the pair image in block frames, the frames (c_B,
+    // R_B) and max R_B (-1: not built)
+    char *b_pimg_l = nullptr;
+    float4 *b_frame = nullptr;
+    size_t b_pimg_l_cap = 0, b_frame_cap = 0;
+    double b_rlmax = -1.0;
+    // the model in kd order and the kd order's inverse (launch_build_kd_tables), and per query
+    // its correspondence's kd position (kpos_valid: the last search over the resident scene kept it)
+    double4 *m4kd = nullptr;
+    int *kd_of = nullptr, *kpos = nullptr;
+    size_t m4kd_cap = 0, kd_of_cap = 0, kpos_cap = 0;
+    bool kpos_valid = false;
+    // y_ready: the last search over the resident scene also wrote Y = m[idx] (the shifted moments
+    // then stream it instead of gathering)
+    bool y_ready = false;
+    // arrival counters of the passes that end in their own last workgroup (StepFold): [0] the
+    // moments + Horn step, [1] the transform + error step; zero between launches
+    unsigned *fold_ticket = nullptr;
+    bool scene_slot = false;
+    unsigned runs = 0; // (icp_run calls: the timing sample's phase)
+    // scene_revert: the scene is in the slot order of a model since replaced -- icp_run puts it
+    // back into file order (and sorts it by the new model's box) unless a new scene comes first
+    bool scene_revert = false;
+    bool p32_stale = false; // the scene's fp32 copy was not kept by the last icp_run (its path never read it)
+    int *s_order = nullptr;
+    size_t s_order_cap = 0;
+    DevCloud s_tmp;                           // the permutation's second buffer
+    int *s_tmp_idx = nullptr;
+    size_t s_tmp_idx_cap = 0;
+
+    // the max-correspondence-distance gate (icp_set_max_distance; icp_gated.hip): dmax (0: off),
+    // the last gated run's mask words (the scene's order), its flags in the caller's order, the
+    // gate's device state with its mapped host mirror, and the mapped K trace
+    double gate_dmax = 0.0;
+    unsigned long long *gate_mask = nullptr;
+    unsigned char *gate_flags = nullptr;
+    double *gate_part = nullptr; // (the gated moments' partial rows: kGateSums a workgroup)
+    size_t gate_mask_cap = 0, gate_flags_cap = 0, gate_part_cap = 0;
+    GateState *gate_state = nullptr, *h_gate = nullptr, *d_gate_mirror = nullptr;
+    long long *h_ktrace = nullptr, *d_ktrace = nullptr;
+    size_t ktrace_cap = 0;
+    bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
+    int gate_iters = 0;     // ... and recorded this many iterations
+
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    icp_stats stats{};
+    std::string err;
+};
+
+#define HIPCHK(expr)                                                                          \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(ctx, ICP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+#define LAUNCHCHK(what)                                                                       \
+    do {                                                                                      \
+        hipError_t e_ = hipGetLastError();                                                    \
+        if (e_ != hipSuccess)                                                                 \
+            return fail(ctx, ICP_E_HIP, std::string(what) + ": " + hipGetErrorString(e_));    \
+    } while (0)
+
+#define TRY(expr)                                                                             \
+    do {                                                                                      \
+        int rc_ = (expr);                                                                     \
+        if (rc_ != ICP_OK) return rc_;                                                        \
+    } while (0)
+
+#pragma GCC visibility push(hidden)
+namespace icp {
+namespace engine {
+
+// What icp_run's last enqueued transform wrote for the next search (transform_err_kernel, SeedArgs).
+// The next search may use each output only in the form it was written in: the bundle filter's
+// slot records exist in a global and a local pair-test form (local_r, icp_bundle_rec.h), and
+// seed16 holds either the f16 seed (mfma16_seed_value) or the local form's shift s0.
+struct SeedState {
+    bool seedd = false;      // b_seedd: each point's seed distance D64(p', y)
+    int seed16 = 0;          // seed16: 0 not written, 1 the f16 seeds, 2 the local shifts s0
+    bool records = false;    // b_qop / b_gop / b_gctr: the slot records and group bounds
+    double rec_local = -1.0; // the records' local_r (-1: the global form)
+};
+
+// The run path's environment switches, each read ONCE per process (run_knobs, icp_run.hip: at the
+// first call that asks for any of them).  Parse: "!=0" on unless atoi(value) == 0; "=1" on only if
+// atoi(value) == 1; "[0]" by the value's first character; "set" on if the variable exists.
+//
+//   field              variable                default  parse / clamp          what it switches
+//   grid_budget        ICP_GRID_BUDGET         0        max(1, atoi); 0: the   cells a query box may span (grid_budget)
+//                                                       rule of grid_budget
+//   grid_auto          ICP_GRID_AUTO           on       !=0                    icp_run's search policy for AUTO at the bundle
+//                                                                              filter's sizes; 0: every seeded search on the
+//                                                                              bundle cascade (A/B)
+//   grid_iter          ICP_GRID_ITER           on       !=0                    the grid iterations over a scene in slot order as
+//                                                                              ONE launch each (nn_grid_iter_kernel: the
+//                                                                              transform, the seeded search with the task's boxes
+//                                                                              staged in LDS, the moments); 0: the separate
+//                                                                              passes (A/B; measured at C4 0.167 against 0.162 ms
+//                                                                              an iteration, the W = 8 shard 0.058 against 0.055,
+//                                                                              profiles/r05g)
+//   grid_xcd           ICP_GRID_XCD            1        atoi                   the seeded grid search of a sparse scene in slot
+//                                                                              order, each XCD on a contiguous eighth of it
+//                                                                              (launch_nn_grid_resolve_all); 0: the plain block
+//                                                                              order, 2: every scene (A/B)
+//   bundle_order_off   ICP_BUNDLE_ORDER        off      set and atoi == 0      the bundle filter's queries in file order (A/B)
+//   scene_order_off    ICP_SCENE_ORDER         off      set and atoi == 0      the resident scene stays in file order (A/B)
+//   cell_seed          ICP_CELL_SEED           on       !=0                    an unseeded search of a scene in slot order takes
+//                                                                              the seeded grid pass from cell seeds
+//                                                                              (grid_unseeded_slot); 0: the ring search (A/B)
+//   first_k1           ICP_FIRST_K1            off      =1                     the canonical first iteration's search and moments
+//                                                                              as one fused launch (A/B; measured slower,
+//                                                                              enqueue_canon_first_k1)
+//   run_mode           ICP_RUN_MODE            -1       "launches" |           forces the run mode over icp_set_run_mode (A/B);
+//                                                       "persistent", else -1  the fused tail obeys "launches" only
+//   persist_mid_off    ICP_PERSIST_MID         off      value == "0"           mid-size runs keep the launch loop (A/B)
+//   persist_stamps     ICP_PERSIST_STAMPS      off      set                    the one-launch loop's phase stamps, to stderr
+//   persist_cull       ICP_PERSIST_NN          1        "all": 0               0: every model point for every query (A/B)
+//   mid_prepass        ICP_MID_PREPASS         off      [0] == '1'             the mid-size loop's first search seeded by one pass
+//                                                                              of the exact cascade (A/B)
+//   transform_records  ICP_TRANSFORM_RECORDS   on       !=0                    0: the prep kernel writes the slot records (A/B)
+//   far_shift          ICP_GRID_FAR_SHIFT      5        atoi in [0, 20]        the far threshold n >> shift (A/B)
+//   far_dist           ICP_GRID_FAR            off      value == "dist"        the far count by the round-4 distance rule (A/B)
+//   fused_steps        ICP_FUSED_STEPS         0        atoi & 3               bit 0: the moments, bit 1: the transform fold their
+//                                                                              partials in their own last workgroup (run_setup_steps)
+//   err_pair           ICP_ERR_PAIR            on       [0] != '0'             0: the separate residual fold (A/B)
+//   timing_stride      ICP_NN_TIMING_STRIDE    0        max(1, atoi); 0: 8     every how many iterations the search is timed
+//   canon              ICP_CANON               on       [0] != '0'             0: the round-4 schedule for a scene in slot order (A/B)
+//   cert               ICP_CERT                on       [0] != '0'             the fused grid iteration's exclusion certificate;
+//                                                                              0: every query walks (A/B)
+//   cert_two           ICP_CERT_TWO            1        [0] == '0': 0          0: the certificate's one-point form
+//   cert_skin          ICP_CERT_SKIN           0.25     atof in [0, 4]         the walk's extra radius in grid cells
+//   cert_skin1         ICP_CERT_SKIN1          = skin   atof in [0, 4]         the skin of a launch with no state to read (A/B)
+//   iter_debug         ICP_ITER_DEBUG          0        set: 1; atoi == 2: 2   nn_grid_iter_kernel's phase clocks and counts, summed
+//                                                                              over the run, to stderr; 2: each launch's (synchronises)
+//   tail_split_err     ICP_TAIL_SPLIT_ERR      off      set                    the fused tail's error step as its own launch (A/B)
+//   debug_policy       ICP_DEBUG_POLICY        off      set                    the policy's far counts, to stderr
+struct RunKnobs {
+    int grid_budget;
+    bool grid_auto, grid_iter;
+    int grid_xcd;
+    bool bundle_order_off, scene_order_off, cell_seed, first_k1;
+    int run_mode;
+    bool persist_mid_off, persist_stamps;
+    int persist_cull;
+    bool mid_prepass, transform_records;
+    int far_shift;
+    bool far_dist;
+    int fused_steps;
+    bool err_pair;
+    int timing_stride;
+    bool canon, cert;
+    int cert_two;
+    double cert_skin, cert_skin1;
+    int iter_debug;
+    bool tail_split_err, debug_policy;
+};
+const RunKnobs &run_knobs();
+
+// The switches the tests set between two runs of one process: read again at every run (run_test_knobs).
+//   enqueue_delay_us    ICP_TEST_ENQUEUE_DELAY_US  0    max(0, atoi)   the host sleeps this long before each enqueue attempt
+//                                                                      (the path sequence must not depend on the host's lead)
+//   tail_test_abort     ICP_TAIL_TEST_ABORT        off  [0] == '1'     fails the fused tail's first barrier (the rerun path)
+//   persist_test_abort  ICP_PERSIST_TEST_ABORT     off  [0] == '1'     makes the one-launch loop's first barrier fail as if a
+//                                                                      workgroup never came
+struct RunTestKnobs {
+    int enqueue_delay_us;
+    bool tail_test_abort, persist_test_abort;
+};
+RunTestKnobs run_test_knobs();
+
+// ---- icp_engine.hip --------------------------------------------------------------------
+constexpr int kSeededBox = 125; // cells of the box a seeded grid search walks with a few lanes (grid_seeded_search)
+
+int fail(icp_ctx *ctx, int code, const std::string &msg);
+
+template <class T> int grow(icp_ctx *ctx, T **p, size_t *cap, size_t count)
+{
+    if (*cap >= count && *p) return ICP_OK;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    size_t bytes = sizeof(T) * (count ? count : 1);
+    HIPCHK(hipMalloc((void **)p, bytes));
+    *cap = count;
+    return ICP_OK;
+}
+
+int check_ready(icp_ctx *ctx, bool need_scene);
+int allreduce(icp_ctx *ctx, double *buf, size_t count);
+int global_count(icp_ctx *ctx, int *v);
+double *red_target(icp_ctx *ctx, size_t n, double *out);
+void red_finish(icp_ctx *ctx, size_t n, int K, double *out);
+int level1_kind(const icp_ctx *ctx, size_t n);
+GridView grid_view(const icp_ctx *ctx);
+int grid_budget(const icp_ctx *ctx);
+bool want_slot_order(const icp_ctx *ctx, size_t n);
+int scene_revert_now(icp_ctx *ctx);
+int scene_to_slot_order(icp_ctx *ctx);
+int fold_cert_counts(icp_ctx *ctx);
+int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipEvent_t ev0, hipEvent_t ev1,
+                    bool zero_counts = true, const SeedState *ws = nullptr, const int *stop = nullptr,
+                    bool slot_order = false, bool grid_seeded = false, const double *seedd = nullptr);
+int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop);
+int moments_phase(icp_ctx *ctx, size_t n);
+
+// ---- icp_run.hip -----------------------------------------------------------------------
+int wait_flag(icp_ctx *ctx, const int *flag, int ticket);
+
+} // namespace engine
+} // namespace icp
+#pragma GCC visibility pop

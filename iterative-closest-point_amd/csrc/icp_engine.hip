@@ -10,12 +10,8 @@
 //  * per iteration only 18 fp64 sums cross PCIe (the reference round-trips whole clouds
 //    ~30 times per iteration);
 //  * multi-GPU: the scene is sharded across ranks, the sums are all-reduced with RCCL.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
+// icp_run's loops are icp_run.hip; what the two files share is icp_engine.h.
 #include <algorithm>
-#include <chrono>
-#include <thread>
 #include <cmath>
 #include <cstdio>
 #include <climits>
@@ -24,10 +20,7 @@
 #include <vector>
 
 #include "icp_horn.h"
-#include "icp_canon.h"
-#include "icp_kernels.h"
-
-using namespace icp;
+#include "icp_engine.h"
 
 // The one-launch loops' model image: points in the order of a kd split -- a range of more
 // than 1,024 points splits at a multiple of 1,024, one of more than 64 at a multiple of 64, one
@@ -131,299 +124,14 @@ std::vector<double> icp::persist_model_image(const double *m, size_t nm, size_t 
     return img;
 }
 
-namespace {
-
-struct DevCloud {
-    double *x = nullptr, *y = nullptr, *z = nullptr;
-    float4 *f = nullptr;
-    size_t n = 0, cap = 0;
-};
-
-} // namespace
-
-struct icp_ctx {
-    int device = 0;
-    int nn_mode = ICP_NN_CERTIFIED;
-    int rank = 0, world = 1;
-    bool allow_unequal = false;
-    hipStream_t st = nullptr;
-    ncclComm_t comm = nullptr;
-    icp_allreduce_fn host_reduce = nullptr; // alternative to RCCL (icp_ctx_create_sharded)
-    void *host_reduce_user = nullptr;
-    icp_progress_fn progress_fn = nullptr; // (icp_set_progress: each recorded iteration's error, as it ends)
-    void *progress_user = nullptr;
-    int progress_next = 0; // (the next iteration of the current run to report)
-
-    // model (replicated)
-    DevCloud model;
-    float4 *m32 = nullptr;   // centred fp32 model, padded to nm_pad with far points
-    float4 *mperm = nullptr; // same, (mm, x, y, z) permuted for the MFMA operands
-    float *mm = nullptr;     // |m~|^2 rounded to fp32 (the MFMA's k = 0 operand)
-    char *mimg16 = nullptr;  // f16 split image for the 32x32x16 f16 MFMA (1 KiB / 32 points)
-    bool mimg16_pending = false; // (built at the first search that reads it: ensure_mimage16)
-    bool m32_pending = false;    // (m32, mperm, mm: built at their first reader, ensure_m32)
-    float *mms16 = nullptr;  // |b_s|^2 (scaled) per model point, fp32
-    double scale16 = 1.0;    // power of two: max |b_s| in [2^11, 2^12)
-    size_t nm = 0, nm_pad = 0, m32_cap = 0, mperm_cap = 0, mm_cap = 0, mimg16_cap = 0, mms16_cap = 0;
-    int nn_variant = ICP_NN_VARIANT_AUTO;
-    double c[3] = {0, 0, 0}; // centring point = model centroid
-    // host copy of the model (AoS): kept when the one-launch paths can take it (small models),
-    // downloaded on demand for the CPU rule's host fix-up, else empty (0.2 GB at 2^23 points)
-    std::vector<double> model_host;
-    double rm = 0.0;         // max |centred fp32 model coordinate|
-    // the model's preparation on the device (icp_model.hip): stats scratch, results (device and
-    // pinned host), the kd builder's plan and scratch, the compare counter of icp_ensure_model
-    double *mstat_part = nullptr, *mstat_out = nullptr, *h_mstat = nullptr;
-    int *cmp_diff = nullptr;
-    KdPlan kd_plan;
-    char *kd_scratch = nullptr;
-    size_t kd_scratch_cap = 0;
-    bool has_model = false;
-
-    // scene (this rank's shard), its correspondences
-    DevCloud scene, Y;
-    size_t np_total = 0;
-    bool has_scene = false;
-
-    // scratch clouds for the per-operation surface
-    DevCloud qa, qb;
-
-    // NN workspace
-    int *idx = nullptr;
-    size_t idx_cap = 0;
-    void *part = nullptr, *part2 = nullptr;
-    size_t part_cap = 0, part2_cap = 0;
-    int *amb1 = nullptr;           // queue of the MFMA certificate
-    size_t amb1_cap = 0;
-    int *amb_count = nullptr, *amb_list = nullptr;
-    double *amb_T = nullptr;
-    size_t amb_cap = 0;
-    // exact grid resolver (icp_grid.hip): model grid + the queues around it
-    GridParams grid{};
-    int *g_start = nullptr;
-    char *g_sort = nullptr; // the build's sort scratch (launch_grid_build)
-    size_t g_sort_cap = 0;
-    double4 *g_pts = nullptr;
-    float4 *g_pts32 = nullptr; // (the fp32 image of g_pts: the seeded grid search's prefilter)
-    size_t g_pts32_cap = 0;
-    size_t g_start_cap = 0, g_pts_cap = 0;
-    IterState *iter_state = nullptr; // device-resident loop state (icp_iter.hip)
-    size_t iter_state_cap = 0;
-    IterState *h_iter = nullptr;     // mapped host mirror of the last recorded iteration's state
-    IterState *d_iter_mirror = nullptr; // its device address
-    double *h_trace = nullptr, *d_trace = nullptr; // mapped host error trace
-    size_t trace_cap = 0;
-    int *h_sig = nullptr, *d_sig = nullptr; // mapped completion word of the per-operation calls
-    int sig_ticket = 0;
-    double *h_few = nullptr;         // mapped host staging of the few-query path: q (3 x kFewQueries),
-    double *d_few = nullptr;         //   y (3 x kFewQueries), idx (kFewQueries ints); device address
-    int *h_flags = nullptr;          // mapped host (done, iter, ticket, -) per in-flight iteration
-    int *d_flags = nullptr;          // its device address (err_step writes it directly)
-    int flag_ticket = 0;             // last ticket handed to an iteration
-    double *err_trace_dev = nullptr;
-    size_t err_trace_cap = 0;
-    std::vector<hipEvent_t> iter_ev; // per ring slot: (nn begin, nn end, -, all-reduce begin, all-reduce end)
-    unsigned long long *digest = nullptr; // icp_set_index_digest: 3 x digest_cap per-iteration digests
-    unsigned *cert_audit = nullptr;       // icp_set_cert_audit: (max err ratio, min margin) float bits, count
-    size_t digest_cap = 0;
-    double4 *m4 = nullptr;      // model as (x, y, z, 0) doubles: one read per random gather
-    size_t m4_cap = 0;
-    // the next model's SoA copy and double4 rows, built while its checks are read back and
-    // swapped with model / m4 when they pass (set_model_staged)
-    DevCloud model_alt;
-    double4 *m4_alt = nullptr;
-    size_t m4_alt_cap = 0;
-    hipEvent_t mstat_ev = nullptr; // (the checks' read-back)
-    unsigned *seed16 = nullptr; // seeded f16 filter: per-query shift (icp_run iterations >= 2)
-    size_t seed16_cap = 0;
-    bool last_search_timed = false; // the per-operation search recorded its events
-    bool seeds_valid = false;   // idx holds the previous search over the resident scene
-    // seedd_valid: b_seedd holds D64(p_j, m[idx_j]) of the resident scene (the last icp_run took
-    // the search policy, whose every transform writes it), and last_far that run's last far count
-    // (SeedArgs::far_acc): the next run's policy starts from them instead of two bundle searches
-    bool seedd_valid = false;
-    int last_far = -1;
-    // second_pass_items (icp_run's policy searches): the grid of the seeded search's second pass
-    // is sized for this many queued queries (0: min(n, 4096)) -- the far count the host last saw
-    int second_pass_items = 0;
-    int last_q2 = -1; // the last run's last observed second-pass queue (IterState::queued2)
-    int *amb1_hint = nullptr, *amb_hint = nullptr;    // candidates of the level-1 / level-2 queues
-    int *fb_list = nullptr;                           // queries the grid hands back
-    double *fb_T = nullptr;
-    size_t amb1_hint_cap = 0, amb_hint_cap = 0, fb_list_cap = 0, fb_T_cap = 0;
-
-    // reductions
-    double *partials = nullptr;
-    double *err_part = nullptr; // (multi-rank icp_run: the transform's residual partials, run_loop)
-    size_t err_part_cap = 0;
-    double *canon_rowbuf = nullptr; // (icp_run over a scene in slot order: the canonical rows, icp_canon.h)
-    int *canon_ticket = nullptr;    // (the fold's workgroup ticket, CanonStep::fold_ticket)
-    size_t canon_rowbuf_cap = 0;
-    int *h_far = nullptr; // (pinned: a far count read back once, run_loop's hold_first)
-    double *sums = nullptr;
-    double *h_sums = nullptr; // pinned
-    int *h_amb = nullptr;     // pinned
-    double *stage = nullptr;
-    size_t stage_cap = 0;
-    // small host <-> device transfers: a mapped pinned buffer the conversion kernels read and
-    // write directly (no pageable-copy staging); bump-allocated, recycled after a sync
-    double *h_io = nullptr, *d_io = nullptr;
-    size_t io_cap = 0, io_off = 0;
-    bool io_pending = false; // a queued kernel may still read h_io
-
-    // ICP_NN_RULE_CPU_SQRT: the near-tie window of every search (launch_nn_cpu_rule_window)
-    int nn_rule = ICP_NN_RULE_SQUARED;
-    CpuRuleEntry *cr_entries = nullptr;
-    int *cr_count = nullptr;
-    int *cr_fix = nullptr; // the fix-up's (query, index) pairs
-    size_t cr_cap = 0, cr_count_cap = 0, cr_fix_cap = 0;
-
-    // one-launch registration of small clouds (icp_iter.hip, launch_icp_persistent)
-    int run_mode = ICP_RUN_AUTO;
-    int n_cu = 0;                    // compute units
-    size_t lds_per_cu = 0, lds_per_block = 0;
-    double *pers_part = nullptr;     // 2 x kBlock x kNumSums published partials
-    unsigned *pers_sync = nullptr;   // arrival counter, abort word (+ padding to 16 B)
-    size_t pers_part_cap = 0, pers_sync_cap = 0;
-    double *tail_part = nullptr;     // fused mid-size tail: published partials (18 x kTailMaxBlocks)
-    unsigned *tail_sync = nullptr;   // its barrier words
-    double *mid_q4 = nullptr;        // mid-size one-launch loop: published queries (4 per point)
-    int *mid_res = nullptr;          // and their correspondences
-    int *mid_perm = nullptr;         // its search order (each point's row)
-    char *mid_cnt = nullptr;         // the order's scratch (radix sort)
-    double m_lo[3] = {0, 0, 0}, m_hi[3] = {0, 0, 0}; // the model's box
-    double pm_seed_big = 0.0;        // PersistArgs::seed_big for this model
-    size_t mid_q4_cap = 0, mid_res_cap = 0, mid_perm_cap = 0, mid_cnt_cap = 0;
-    size_t tail_part_cap = 0, tail_sync_cap = 0;
-    bool pers_sync_valid = false;    // the barrier words hold pers_epoch_base barriers of grid pers_grid
-    unsigned pers_epoch_base = 0;
-    int pers_grid = 0;
-    unsigned long long *pers_stamps = nullptr; // ICP_PERSIST_STAMPS=1: phase stamps
-    size_t pers_stamps_cap = 0;
-    // the model in Morton order for the one-launch NN (models <= kPersistMaxModel points):
-    // x[nm] | y[nm] | z[nm] | 64-point block boxes (lo xyz, hi xyz) | original index (int32)
-    double *pm_img = nullptr;
-    size_t pm_img_cap = 0, pm_blocks = 0;
-    // bundle-bound filter (icp_bundle.hip): the model's kd-ordered bundle and pair images, built
-    // per model of >= kBundleMinModel points; the query order of the scene it searches
-    char *b_img = nullptr, *b_pimg = nullptr; // 1 KiB per 32 bundles; 1 KiB per bundle
-    int *b_kd_orig = nullptr;                 // original index per kd position (nm: padding)
-    double4 *b_bctr = nullptr, *b_blk = nullptr; // per bundle / per 32-bundle block: centre, radius
-    int *b_kd = nullptr;                      // the kd order (upload staging)
-    int nb_pad = 0;                           // bundles (whole LDS tiles)
-    // the bundle filter's kd order and images are built at their first use (ensure_bundle):
-    // pending from icp_set_model on until then (a run whose searches all take the grid never
-    // builds them)
-    bool bundle_pending = false;
-    size_t b_img_cap = 0, b_pimg_cap = 0, b_kd_orig_cap = 0, b_bctr_cap = 0, b_blk_cap = 0, b_kd_cap = 0;
-    int *q_order = nullptr;                   // the bundle filter's query order (launch_query_order)
-    int *q_pos = nullptr;                     // its inverse (query j's slot)
-    size_t q_pos_cap = 0;
-    char *q_order_tmp = nullptr;
-    size_t q_order_cap = 0, q_order_tmp_cap = 0;
-    const double *q_order_src = nullptr;      // the cloud q_order was computed for (its x array)
-    size_t q_order_n = 0;
-    unsigned long long *b_counters = nullptr; // icp_set_bundle_counters: the filter's executed work
-    char *b_qop = nullptr, *b_gop = nullptr;  // v2: per-slot query operands, per-group bounds
-    double4 *b_qraw = nullptr;                // v2: per-slot query coordinates, index, seed
-    int *b_glist = nullptr;                   // v2: fired-block list overflow
-    double *b_seedd = nullptr;                // v2: per point, D64 to its seed (icp_run's transform)
-    size_t b_seedd_cap = 0;
-    // the fused grid iteration's exclusion certificate (CertArgs): per point in slot order the
-    // bound and the pair; counts = (certified, walked) summed over the run (device)
-    hipEvent_t order_ev = nullptr; // icp_set_*_device_stream: the producer stream's point to wait for
-    int4 *cert_state = nullptr;
-    size_t cert_state_cap = 0;
-    unsigned long long *cert_counts = nullptr; // (2 per strand: certified, walked -- CertArgs::counts)
-    size_t cert_counts_cap = 0;
-    int cert_counts_rows = 0; // (strands the runs since the last fold counted into cert_counts, not yet in stats)
-    char *tail_backup = nullptr;              // icp_run with the fused tail: the starting scene / idx
-    size_t tail_backup_cap = 0;
-    double4 *b_gctr = nullptr;                // v2: per-group (centre, D)
-    int *b_cand = nullptr, *b_cand_n = nullptr; // v2: per filter workgroup, its candidate blocks
-    int *b_wsplit = nullptr, *b_tctl = nullptr; // v2: per filter workgroup its tasks; (count, counter)
-    int2 *b_tasks = nullptr;                  // v2: the task list
-    size_t b_gctr_cap = 0, b_cand_cap = 0, b_cand_n_cap = 0, b_wsplit_cap = 0, b_tctl_cap = 0, b_tasks_cap = 0;
-    size_t b_qop_cap = 0, b_gop_cap = 0, b_qraw_cap = 0, b_glist_cap = 0, b_counters_rows = 0;
-    // The resident scene in slot order (scene_in_slot_order): point s of the scene (and idx[s]
-    // while seeds_valid) is the caller's point s_order[s].  icp_get_scene / icp_get_indices and
-    // the index digests map back; every other per-point pass is order-agnostic.
-    // the local pair test (icp_bundle_rec.h): the pair image in block frames, the frames (c_B,
-    // R_B) and max R_B (-1: not built)
-    char *b_pimg_l = nullptr;
-    float4 *b_frame = nullptr;
-    size_t b_pimg_l_cap = 0, b_frame_cap = 0;
-    double b_rlmax = -1.0;
-    // the model in kd order and the kd order's inverse (launch_build_kd_tables), and per query
-    // its correspondence's kd position (kpos_valid: the last search over the resident scene kept it)
-    double4 *m4kd = nullptr;
-    int *kd_of = nullptr, *kpos = nullptr;
-    size_t m4kd_cap = 0, kd_of_cap = 0, kpos_cap = 0;
-    bool kpos_valid = false;
-    // y_ready: the last search over the resident scene also wrote Y = m[idx] (the shifted moments
-    // then stream it instead of gathering)
-    bool y_ready = false;
-    // arrival counters of the passes that end in their own last workgroup (StepFold): [0] the
-    // moments + Horn step, [1] the transform + error step; zero between launches
-    unsigned *fold_ticket = nullptr;
-    bool scene_slot = false;
-    unsigned runs = 0; // (icp_run calls: the timing sample's phase)
-    // scene_revert: the scene is in the slot order of a model since replaced -- icp_run puts it
-    // back into file order (and sorts it by the new model's box) unless a new scene comes first
-    bool scene_revert = false;
-    bool p32_stale = false; // the scene's fp32 copy was not kept by the last icp_run (its path never read it)
-    int *s_order = nullptr;
-    size_t s_order_cap = 0;
-    DevCloud s_tmp;                           // the permutation's second buffer
-    int *s_tmp_idx = nullptr;
-    size_t s_tmp_idx_cap = 0;
-
-    // the max-correspondence-distance gate (icp_set_max_distance; icp_gated.hip): dmax (0: off),
-    // the last gated run's mask words (the scene's order), its flags in the caller's order, the
-    // gate's device state with its mapped host mirror, and the mapped K trace
-    double gate_dmax = 0.0;
-    unsigned long long *gate_mask = nullptr;
-    unsigned char *gate_flags = nullptr;
-    double *gate_part = nullptr; // (the gated moments' partial rows: kGateSums a workgroup)
-    size_t gate_mask_cap = 0, gate_flags_cap = 0, gate_part_cap = 0;
-    GateState *gate_state = nullptr, *h_gate = nullptr, *d_gate_mirror = nullptr;
-    long long *h_ktrace = nullptr, *d_ktrace = nullptr;
-    size_t ktrace_cap = 0;
-    bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
-    int gate_iters = 0;     // ... and recorded this many iterations
-
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    icp_stats stats{};
-    std::string err;
-};
-
-namespace {
+namespace icp {
+namespace engine {
 
 int fail(icp_ctx *ctx, int code, const std::string &msg)
 {
     if (ctx) ctx->err = msg;
     return code;
 }
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ctx, ICP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
-#define LAUNCHCHK(what)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ctx, ICP_E_HIP, std::string(what) + ": " + hipGetErrorString(e_));    \
-    } while (0)
-
-#define TRY(expr)                                                                             \
-    do {                                                                                      \
-        int rc_ = (expr);                                                                     \
-        if (rc_ != ICP_OK) return rc_;                                                        \
-    } while (0)
 
 #define RCCLCHK(expr)                                                                         \
     do {                                                                                      \
@@ -432,19 +140,7 @@ int fail(icp_ctx *ctx, int code, const std::string &msg)
             return fail(ctx, ICP_E_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
-template <class T> int grow(icp_ctx *ctx, T **p, size_t *cap, size_t count)
-{
-    if (*cap >= count && *p) return ICP_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    size_t bytes = sizeof(T) * (count ? count : 1);
-    HIPCHK(hipMalloc((void **)p, bytes));
-    *cap = count;
-    return ICP_OK;
-}
-
-int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
+static int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
 {
     if (c.cap < n || !c.x || (with_f32 && !c.f)) {
         for (void *p : {(void *)c.x, (void *)c.y, (void *)c.z, (void *)c.f})
@@ -461,7 +157,7 @@ int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
     return ICP_OK;
 }
 
-void free_cloud(DevCloud &c)
+static void free_cloud(DevCloud &c)
 {
     for (void *p : {(void *)c.x, (void *)c.y, (void *)c.z, (void *)c.f})
         if (p) (void)hipFree(p);
@@ -475,7 +171,7 @@ constexpr int kBundleMinModel = 8192; // models from this size get the bundle fi
 // `count` (<= 2 x kMappedIo) doubles of the mapped buffer: host pointer (*h) and device pointer
 // (*d).  When the buffer is used up it is recycled from the start, after a sync if a kernel
 // may still read it.
-int io_take(icp_ctx *ctx, size_t count, double **h, double **d)
+static int io_take(icp_ctx *ctx, size_t count, double **h, double **d)
 {
     if (count > 2 * kMappedIo) // callers gate on this; a larger region would run past the buffer
         return fail(ctx, ICP_E_ARG, "io_take: " + std::to_string(count) + " doubles exceed the mapped buffer");
@@ -497,7 +193,7 @@ int io_take(icp_ctx *ctx, size_t count, double **h, double **d)
 }
 
 // host AoS (3 x n col-major) -> device SoA fp64 (+ centred fp32 copy)
-int upload_cloud(icp_ctx *ctx, DevCloud &c, const double *xyz, size_t n, bool make_f32)
+static int upload_cloud(icp_ctx *ctx, DevCloud &c, const double *xyz, size_t n, bool make_f32)
 {
     TRY(grow_cloud(ctx, c, n, true));
     if (!n) return ICP_OK;
@@ -522,7 +218,7 @@ int upload_cloud(icp_ctx *ctx, DevCloud &c, const double *xyz, size_t n, bool ma
     return ICP_OK;
 }
 
-int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
+static int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
 {
     if (!n) return ICP_OK;
     if (3 * n <= kMappedIo) { // small: the conversion kernel writes the host copy directly
@@ -544,7 +240,7 @@ int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
 }
 
 // The model's host copy (AoS), downloaded once if set_model did not keep it.
-int model_host_copy(icp_ctx *ctx, const double **out)
+static int model_host_copy(icp_ctx *ctx, const double **out)
 {
     if (ctx->model_host.size() != 3 * ctx->nm) {
         ctx->model_host.resize(3 * ctx->nm);
@@ -554,7 +250,7 @@ int model_host_copy(icp_ctx *ctx, const double **out)
     return ICP_OK;
 }
 
-int ensure_reduction_space(icp_ctx *ctx)
+static int ensure_reduction_space(icp_ctx *ctx)
 {
     if (ctx->partials) return ICP_OK;
     HIPCHK(hipMalloc((void **)&ctx->partials, sizeof(double) * kRedMaxBlocksCap * kRedMaxK));
@@ -577,7 +273,7 @@ void red_finish(icp_ctx *ctx, size_t n, int K, double *out)
 }
 
 // queue of queries the fp32 certificate could not settle (list + window T + counter)
-int ensure_queue(icp_ctx *ctx, size_t n)
+static int ensure_queue(icp_ctx *ctx, size_t n)
 {
     if (ctx->amb_cap >= n && ctx->amb_list) return ICP_OK;
     if (ctx->amb_list) HIPCHK(hipFree(ctx->amb_list));
@@ -592,7 +288,7 @@ int ensure_queue(icp_ctx *ctx, size_t n)
     return ICP_OK;
 }
 
-int ensure_bundle(icp_ctx *ctx); // (the bundle filter's images at their first use; below)
+static int ensure_bundle(icp_ctx *ctx); // (the bundle filter's images at their first use; below)
 
 // level-1 filter of a certified search: 0 = none (VALU filter only), 1 = f32 MFMA, 2 = f16 MFMA
 int level1_kind(const icp_ctx *ctx, size_t n)
@@ -636,63 +332,20 @@ GridView grid_view(const icp_ctx *ctx)
 // fallback nm.  Measured (profiles/r01dr/, cells): horse (48,485 points, 25,840 cells) 1,024 ->
 // 6,060 -> 12,000 took the grid variant 3,700 -> 4,277 -> 5,003 it/s and the default 5,560 ->
 // 5,977 -> 6,012, with no gain beyond; bunny likewise.  ICP_GRID_BUDGET overrides.
-static int grid_budget(const icp_ctx *ctx)
+int grid_budget(const icp_ctx *ctx)
 {
-    static const int forced = [] {
-        const char *e = getenv("ICP_GRID_BUDGET");
-        return e ? std::max(1, atoi(e)) : 0;
-    }();
-    if (forced) return forced;
+    if (run_knobs().grid_budget) return run_knobs().grid_budget;
     return (int)std::min<size_t>(std::max<size_t>(kGridBudget, ctx->nm / 4), (size_t)1 << 16);
-}
-
-// icp_run's search policy for AUTO at the bundle filter's sizes (run_loop); ICP_GRID_AUTO=0 keeps
-// every seeded search on the bundle cascade (A/B)
-static bool grid_auto()
-{
-    static const bool on = [] {
-        const char *e = getenv("ICP_GRID_AUTO");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
-}
-
-// icp_run's grid iterations over a scene in slot order as ONE launch each (nn_grid_iter_kernel:
-// the transform, the seeded search with the task's boxes staged in LDS, the moments);
-// ICP_GRID_ITER=0: the separate transform, seeded search and moments passes (A/B; measured at
-// C4 0.167 against 0.162 ms an iteration, the W = 8 shard 0.058 against 0.055, profiles/r05g)
-static bool grid_iter_on()
-{
-    static const bool on = [] {
-        const char *e = getenv("ICP_GRID_ITER");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
-}
-
-// the seeded grid search of a sparse scene in slot order, each XCD on a contiguous eighth of it
-// (launch_nn_grid_resolve_all); ICP_GRID_XCD=0: the plain block order, =2: every scene (A/B)
-static int grid_xcd()
-{
-    static const int mode = [] {
-        const char *e = getenv("ICP_GRID_XCD");
-        return e ? atoi(e) : 1;
-    }();
-    return mode;
 }
 
 // The bundle filter's processing order of the n queries in q (a Morton order over the model's
 // box, launch_query_order): computed once per cloud -- an icp_run's scene moves rigidly, so its
 // first order stays spatially coherent -- and again after set_scene / closest_matrix uploads.
 // ICP_BUNDLE_ORDER=0: file order (A/B).
-int query_order(icp_ctx *ctx, const DevCloud &q, size_t n, const int **order)
+static int query_order(icp_ctx *ctx, const DevCloud &q, size_t n, const int **order)
 {
-    static const bool off = [] {
-        const char *e = getenv("ICP_BUNDLE_ORDER");
-        return e && atoi(e) == 0;
-    }();
     *order = nullptr;
-    if (off) return ICP_OK;
+    if (run_knobs().bundle_order_off) return ICP_OK;
     if (ctx->q_order_src != q.x || ctx->q_order_n != n) {
         TRY(grow(ctx, &ctx->q_order, &ctx->q_order_cap, n));
         TRY(grow(ctx, &ctx->q_pos, &ctx->q_pos_cap, n));
@@ -716,19 +369,15 @@ int query_order(icp_ctx *ctx, const DevCloud &q, size_t n, const int **order)
 // NN variant, so that every variant runs the same per-point order and the same reductions
 // (their trajectories stay bitwise equal); below it (n <= 49,152) the one-launch paths keep
 // their own orders.  ICP_SCENE_ORDER=0: file order (A/B).
-static bool want_slot_order(const icp_ctx *ctx, size_t n)
+bool want_slot_order(const icp_ctx *ctx, size_t n)
 {
-    static const bool off = [] {
-        const char *e = getenv("ICP_SCENE_ORDER");
-        return e && atoi(e) == 0;
-    }();
-    return !off && n > (size_t)kTailMaxBlocks * kBlock && ctx->nm >= (size_t)kBundleMinModel &&
+    return !run_knobs().scene_order_off && n > (size_t)kTailMaxBlocks * kBlock && ctx->nm >= (size_t)kBundleMinModel &&
            (double)n * (double)ctx->nm >= 2147483648.0;
 }
 
 // A pending scene_revert (set_model while the scene was in slot order): the scene back into
 // file order, its fp32 copy around the new model's c
-static int scene_revert_now(icp_ctx *ctx)
+int scene_revert_now(icp_ctx *ctx)
 {
     if (!ctx->scene_revert) return ICP_OK;
     DevCloud &P = ctx->scene;
@@ -747,7 +396,7 @@ static int scene_revert_now(icp_ctx *ctx)
 
 // The resident scene (and its correspondences while seeds_valid) into slot order, once per
 // uploaded scene: gathered into the second buffer, which then becomes the scene.
-static int scene_to_slot_order(icp_ctx *ctx)
+int scene_to_slot_order(icp_ctx *ctx)
 {
     if (ctx->scene_slot || !ctx->scene.n) return ICP_OK;
     DevCloud &P = ctx->scene;
@@ -800,7 +449,7 @@ static int sum_cert_counts(const icp_ctx *ctx, long long out[2])
     return ICP_OK;
 }
 
-static int fold_cert_counts(icp_ctx *ctx)
+int fold_cert_counts(icp_ctx *ctx)
 {
     long long c[2];
     TRY(sum_cert_counts(ctx, c));
@@ -810,7 +459,6 @@ static int fold_cert_counts(icp_ctx *ctx)
     return ICP_OK;
 }
 
-constexpr int kSeededBox = 125;
 static int grid_seeded_search(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop, const double *seedd,
                               hipEvent_t ev1)
 {
@@ -827,7 +475,7 @@ static int grid_seeded_search(icp_ctx *ctx, const DevCloud &q, size_t n, const i
     }
     // (an XCD a contiguous eighth of the slot order: measured faster for sparse shards, slower
     // for a whole scene -- C4 W = 8 shard 36.8 against 41.5 us, W = 1 140 against 126 us, r04k)
-    const bool xcd = grid_xcd() == 2 || (grid_xcd() == 1 && 4 * n <= ctx->nm);
+    const bool xcd = run_knobs().grid_xcd == 2 || (run_knobs().grid_xcd == 1 && 4 * n <= ctx->nm);
     // with the seed distances (the policy's searches): every level also writes each answered
     // query's correspondence y = m[idx] (the moments then stream y: no gather)
     const DevCloud &Y = ctx->Y;
@@ -910,15 +558,6 @@ static int ensure_m32(icp_ctx *ctx)
 // point, then the complete box).  Both end in the exact first minimum over a complete box; the
 // seeded pass is the tuned one (its lanes, loads in flight, y written for the moments).
 // ICP_CELL_SEED=0: the ring search (A/B).
-static bool cell_seed_on()
-{
-    static const bool on = [] {
-        const char *e = getenv("ICP_CELL_SEED");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
-}
-
 static int grid_unseeded_slot(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop, hipEvent_t ev1)
 {
     TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
@@ -926,17 +565,6 @@ static int grid_unseeded_slot(icp_ctx *ctx, const DevCloud &q, size_t n, const i
     LAUNCHCHK("nn_grid_cell_seed");
     return grid_seeded_search(ctx, q, n, stop, ctx->b_seedd, ev1);
 }
-
-// What icp_run's last enqueued transform wrote for the next search (transform_err_kernel, SeedArgs).
-// The next search may use each output only in the form it was written in: the bundle filter's
-// slot records exist in a global and a local pair-test form (local_r, icp_bundle_rec.h), and
-// seed16 holds either the f16 seed (mfma16_seed_value) or the local form's shift s0.
-struct SeedState {
-    bool seedd = false;      // b_seedd: each point's seed distance D64(p', y)
-    int seed16 = 0;          // seed16: 0 not written, 1 the f16 seeds, 2 the local shifts s0
-    bool records = false;    // b_qop / b_gop / b_gctr: the slot records and group bounds
-    double rec_local = -1.0; // the records' local_r (-1: the global form)
-};
 
 // Launches the complete NN search of the n queries in q against the resident model ->
 // ctx->idx, with no host synchronisation: every level is sized on the device.  Queue sizes:
@@ -947,8 +575,8 @@ struct SeedState {
 // what icp_run's previous transform wrote (SeedState); each part is used only if its form is
 // the one this search runs, else rebuilt here.
 int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipEvent_t ev0, hipEvent_t ev1,
-                    bool zero_counts = true, const SeedState *ws = nullptr, const int *stop = nullptr,
-                    bool slot_order = false, bool grid_seeded = false, const double *seedd = nullptr)
+                    bool zero_counts, const SeedState *ws, const int *stop, bool slot_order, bool grid_seeded,
+                    const double *seedd)
 {
     const SeedState none;
     const SeedState &w = ws ? *ws : none;
@@ -977,7 +605,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         LAUNCHCHK("nn_fp64");
     } else if (seeded && slot_order && (grid_seeded || ctx->nn_variant == ICP_NN_VARIANT_GRID)) {
         // (icp_run's seeded search of a scene in slot order; AUTO takes it by icp_run's policy,
-        // run_loop)
+        // icp_run.hip)
         ctx->stats.last_filter = ICP_FILTER_GRID;
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
         // (seedd: the last transform wrote each point's seed distance -- the policy's searches, and
@@ -989,14 +617,14 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         ctx->stats.last_filter = ICP_FILTER_GRID;
         TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
         TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
-        const bool cell_seeds = !seeded && slot_order && cell_seed_on();
+        const bool cell_seeds = !seeded && slot_order && run_knobs().cell_seed;
         if (!cell_seeds) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
         if (cell_seeds) return grid_unseeded_slot(ctx, q, n, stop, ev1);
         if (seeded) // (icp_run: the previous correspondence is each query's candidate; no ring search)
             launch_nn_grid_resolve_all((int)n, q.x, q.y, q.z, ctx->m4, grid_view(ctx), grid_budget(ctx), ctx->idx,
                                        ctx->amb_count + 1, ctx->fb_list, ctx->fb_T, ctx->st, stop, 0,
-                                       slot_order && grid_xcd() != 0);
+                                       slot_order && run_knobs().grid_xcd != 0);
         else
             launch_nn_grid_search((int)n, q.x, q.y, q.z, grid_view(ctx), grid_budget(ctx), ctx->idx,
                                   ctx->amb_count + 1, ctx->fb_list, ctx->fb_T, ctx->st);
@@ -1023,9 +651,9 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
             ctx->stats.last_filter = ICP_FILTER_GRID;
             TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
             TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
-            if (!cell_seed_on()) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
+            if (!run_knobs().cell_seed) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
             if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
-            if (cell_seed_on()) return grid_unseeded_slot(ctx, q, n, stop, ev1);
+            if (run_knobs().cell_seed) return grid_unseeded_slot(ctx, q, n, stop, ev1);
             launch_nn_grid_search((int)n, q.x, q.y, q.z, grid_view(ctx), grid_budget(ctx), ctx->idx, ctx->amb_count + 1,
                                   ctx->fb_list, ctx->fb_T, ctx->st);
             if (ev1) HIPCHK(hipEventRecord(ev1, ctx->st));
@@ -1195,7 +823,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
 }
 
 // queue sizes of the last search -> pinned h_amb (the caller synchronises)
-int nn_counts_to_host(icp_ctx *ctx)
+static int nn_counts_to_host(icp_ctx *ctx)
 {
     HIPCHK(hipMemcpyAsync(ctx->h_amb, ctx->amb_count, sizeof(int) * 4, hipMemcpyDeviceToHost, ctx->st));
     return ICP_OK;
@@ -1206,7 +834,7 @@ int nn_counts_to_host(icp_ctx *ctx)
 // searches below this many pairs are not timed: two event markers cost the stream ~9 us
 constexpr double kTimedPairs = 4294967296.0;
 
-int nn_search(icp_ctx *ctx, const DevCloud &q, size_t n)
+static int nn_search(icp_ctx *ctx, const DevCloud &q, size_t n)
 {
     ctx->last_search_timed = n && (double)n * (double)ctx->nm >= kTimedPairs;
     TRY(nn_search_begin(ctx, q, n, false, ctx->last_search_timed ? ctx->ev[0] : nullptr,
@@ -1298,7 +926,7 @@ int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop)
 
 // after the stream has been synchronised (h_amb holds the last search's final counts): fold
 // the NN events and queue sizes into the stats
-void account_nn(icp_ctx *ctx, size_t n)
+static void account_nn(icp_ctx *ctx, size_t n)
 {
     float ms = 0.f;
     if (ctx->last_search_timed) {
@@ -1339,7 +967,7 @@ int allreduce(icp_ctx *ctx, double *buf, size_t count)
 }
 
 // an int summed over the ranks (several ranks: through the all-reduce; one: as it is), synchronous
-static int global_count(icp_ctx *ctx, int *v)
+int global_count(icp_ctx *ctx, int *v)
 {
     if (!ctx->comm && ctx->world <= 1) return ICP_OK;
     double x = (double)*v;
@@ -1410,12 +1038,30 @@ static int build_bundle(icp_ctx *ctx, size_t nm, const int *kd_h)
 }
 
 // the bundle filter's images, built now if they are pending (the first search that needs them)
-int ensure_bundle(icp_ctx *ctx)
+static int ensure_bundle(icp_ctx *ctx)
 {
     return ctx->bundle_pending ? build_bundle(ctx, ctx->nm, nullptr) : ICP_OK;
 }
 
-} // namespace
+// moments of one iteration, all on the device: Y = m[idx]; sum p, sum y [all-reduce 6];
+// centred S, d_caps, sp around the all-reduced centroids [all-reduce 11]
+int moments_phase(icp_ctx *ctx, size_t n)
+{
+    const DevCloud &P = ctx->scene, &Y = ctx->Y;
+    launch_gather_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, red_target(ctx, n, ctx->sums + kSumP),
+                          ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd);
+    red_finish(ctx, n, 6, ctx->sums + kSumP);
+    LAUNCHCHK("moments");
+    TRY(allreduce(ctx, ctx->sums + kSumP, 6));
+    launch_centred_moments(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, ctx->sums, (double)ctx->np_total, red_target(ctx, n, ctx->sums + kSumS),
+                           ctx->st);
+    red_finish(ctx, n, 11, ctx->sums + kSumS);
+    LAUNCHCHK("centred_moments");
+    return allreduce(ctx, ctx->sums + kSumS, 11);
+}
+
+} // namespace engine
+} // namespace icp
 
 // ===================================================================================
 extern "C" {
@@ -2065,7 +1711,7 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
     // ICP_EAGER_BUNDLE=1: a shard against a model of at least twice its points (C5's 8-way shards)
     // gets the bundle images here instead of at their first use.  Round 4 built them here always:
     // its far rule sent a C5 shard's first searches to the bundle cascade.  With the box rule
-    // (run_loop: the queries whose clamped box the grid walk cannot take) the same shard stays on
+    // (icp_run.hip run_setup_policy: the queries whose clamped box the grid walk cannot take) the same shard stays on
     // the grid (0.9% of its points against the n/32 threshold), and a scene that does need the
     // cascade builds the images between two iterations (the same results, tests/test_gpu_lazy_bundle.py).
     // Only for a scene the bundle filter would search (level1_kind == 3, the slot order)
@@ -2092,1405 +1738,6 @@ int icp_get_scene(icp_ctx *ctx, double *p_xyz_out)
         return download_cloud(ctx, ctx->s_tmp, P.n, p_xyz_out);
     }
     return download_cloud(ctx, ctx->scene, ctx->scene.n, p_xyz_out);
-}
-
-// moments of one iteration, all on the device: Y = m[idx]; sum p, sum y [all-reduce 6];
-// centred S, d_caps, sp around the all-reduced centroids [all-reduce 11]
-static int moments_phase(icp_ctx *ctx, size_t n)
-{
-    const DevCloud &P = ctx->scene, &Y = ctx->Y;
-    launch_gather_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, red_target(ctx, n, ctx->sums + kSumP),
-                          ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd);
-    red_finish(ctx, n, 6, ctx->sums + kSumP);
-    LAUNCHCHK("moments");
-    TRY(allreduce(ctx, ctx->sums + kSumP, 6));
-    launch_centred_moments(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, ctx->sums, (double)ctx->np_total, red_target(ctx, n, ctx->sums + kSumS),
-                           ctx->st);
-    red_finish(ctx, n, 11, ctx->sums + kSumS);
-    LAUNCHCHK("centred_moments");
-    return allreduce(ctx, ctx->sums + kSumS, 11);
-}
-
-// Spin until err_step has written `ticket` (system-scope release after (done, iter)).  No
-// event per iteration: an event marker costs the stream a ~6 us bubble.  If the stream
-// drains without the ticket (an earlier failure), report instead of spinning forever.
-static int wait_flag(icp_ctx *ctx, const int *flag, int ticket)
-{
-    // The stream is queried (a drained stream without the flag is a failure) only once a wait has
-    // lasted 20 ms, then every 20 ms: hipStreamQuery puts a marker at the stream's tail, right
-    // behind the last error step enqueued, and the next search then started 5.6 us late -- every
-    // iteration, with the spin's query every 1,024 pauses (profiles/r04z/gaps*)
-    auto next = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-    for (unsigned spin = 1;; ++spin) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == ticket) return ICP_OK;
-        if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() >= next) {
-            next = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-            const hipError_t q = hipStreamQuery(ctx->st);
-            if (q == hipErrorNotReady) continue;
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == ticket) return ICP_OK;
-            if (q != hipSuccess) return fail(ctx, ICP_E_HIP, std::string("icp_run: ") + hipGetErrorString(q));
-            return fail(ctx, ICP_E_HIP, "icp_run: the stream drained without the iteration's flag");
-        }
-        __builtin_ia32_pause();
-    }
-}
-
-// icp_set_progress: iterations [progress_next, upto) of the running icp_run, from the mapped
-// error trace (each entry written before its iteration's ticket was released)
-static void report_progress(icp_ctx *ctx, int upto)
-{
-    if (!ctx->progress_fn) return;
-    for (; ctx->progress_next < upto; ++ctx->progress_next)
-        ctx->progress_fn(ctx->progress_next, ctx->h_trace[ctx->progress_next], ctx->progress_user);
-}
-
-static int finish_run(icp_ctx *ctx, double threshold, double *err_trace, icp_result *res,
-                      std::chrono::steady_clock::time_point wall0);
-
-
-// the run all-reduces its sums (ranks > 1 or a communicator): error test one iteration late
-static bool lag_run(const icp_ctx *ctx) { return ctx->comm != nullptr || ctx->world > 1; }
-
-// Workgroups of the one-launch registration for this run, or 0 if it does not apply: one
-// rank, no communicator, no per-iteration instrumentation, and either
-//  - n <= kRedSingle (the single-workgroup passes it reproduces bit for bit), the model in
-//    LDS, >= 64 co-resident workgroups (icp_persistent_kernel), or
-//  - kRedSingle < n <= kTailMaxBlocks * 256, red_blocks(n) workgroups co-resident with a
-//    quarter of the CUs to spare, nm <= kPersistMidMaxModel (icp_persistent_mid_kernel; *mid_out).
-static int persistent_grid(const icp_ctx *ctx, size_t n, int max_iter, size_t *lds_out, bool *mid_out)
-{
-    *mid_out = false;
-    static const int forced = [] { // ICP_RUN_MODE=launches|persistent (A/B runs)
-        const char *e = getenv("ICP_RUN_MODE");
-        if (!e) return -1;
-        return std::strcmp(e, "launches") == 0 ? ICP_RUN_LAUNCHES
-               : std::strcmp(e, "persistent") == 0 ? ICP_RUN_PERSISTENT : -1;
-    }();
-    const int mode = forced >= 0 ? forced : ctx->run_mode;
-    if (mode == ICP_RUN_LAUNCHES) return 0;
-    if (mode == ICP_RUN_AUTO && ctx->nn_variant != ICP_NN_VARIANT_AUTO) return 0; // explicit variants run their cascade
-    if (ctx->world != 1 || ctx->comm || ctx->host_reduce || ctx->digest_cap || max_iter < 1) return 0;
-    if (ctx->nn_rule != ICP_NN_RULE_SQUARED) return 0; // (the host resolves the CPU rule's near ties)
-    if (n > (size_t)kRedSingle) {
-        static const bool mid_off = [] { // ICP_PERSIST_MID=0: mid-size runs keep the launch loop (A/B)
-            const char *e = getenv("ICP_PERSIST_MID");
-            return e && std::strcmp(e, "0") == 0;
-        }();
-        if (mid_off || n > (size_t)kTailMaxBlocks * kBlock || ctx->nm < 1 || ctx->nm > (size_t)kPersistMidMaxModel ||
-            !ctx->pm_img)
-            return 0;
-        // the classic red_blocks(n) workgroups, widened to the whole co-resident grid: the extra
-        // ones own no point and only search (their partial rows are +0.0, which leaves
-        // reduce_kernel's tree bit for bit unchanged)
-        const int classic = red_blocks(n), wide = std::min(kTailMaxBlocks, ctx->n_cu * 3 / 4);
-        const int grid = std::max(classic, wide);
-        if (grid > ctx->n_cu * 3 / 4 || grid > kTailMaxBlocks || (size_t)classic * kBlock < n) return 0;
-        const size_t lds = 24 * (ctx->pm_blocks + (ctx->nm + 15) / 16);
-        if (lds > kPersistMidLdsMax || lds + persistent_mid_static_lds() > ctx->lds_per_cu) return 0;
-        *lds_out = lds;
-        *mid_out = true;
-        return grid;
-    }
-    if (n < 4 || ctx->nm < 1 || ctx->nm > (size_t)kPersistMaxModel) return 0;
-    const size_t lds = 24 * ctx->nm + 48 * ctx->pm_blocks, statics = persistent_static_lds();
-    if (!ctx->pm_img) return 0;
-    if (lds + statics > ctx->lds_per_cu) return 0; // (gfx950: one workgroup may take the whole 160 KiB)
-    const int per_cu = (int)std::min<size_t>(2, ctx->lds_per_cu / (lds + statics)); // (<= 2: 199 VGPRs)
-    // residency margin: a quarter of the admissible slots left free (a barrier over a grid that
-    // is not fully resident would only time out, but it would be an error, not a slow run);
-    // 256 / 128 / 64 workgroups, so that every one owns the same number of virtual threads
-    const int slots = ctx->n_cu * per_cu * 3 / 4;
-    const int grid = slots >= kBlock ? kBlock : slots >= kBlock / 2 ? kBlock / 2 : kBlock / 4;
-    if (grid < 64) return 0;
-    *lds_out = lds;
-    return grid;
-}
-
-// icp_run as ONE launch (launch_icp_persistent): same results, bit for bit, as the loop below.
-// kPersistFallback: the launch gave up at its first grid barrier, before writing any state
-// (some workgroups were not co-resident); the caller runs the launch loop instead.
-constexpr int kPersistFallback = 1;
-static int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, double threshold,
-                          double *err_trace, icp_result *res, std::chrono::steady_clock::time_point wall0)
-{
-    static_assert(2 * kTailMaxBlocks <= 2 * kBlock, "pers_part holds the mid kernel's rows");
-    const size_t n = ctx->scene.n;
-    DevCloud &P = ctx->scene, &Y = ctx->Y;
-    TRY(grow(ctx, &ctx->idx, &ctx->idx_cap, n)); // (a fresh context has run no search yet)
-    TRY(grow(ctx, &ctx->pers_part, &ctx->pers_part_cap, (size_t)2 * kBlock * kNumSums));
-    static const bool stamps = getenv("ICP_PERSIST_STAMPS") != nullptr;
-    if (stamps) {
-        const size_t ns = (size_t)2 * kPersistMaxStamps + 2 * kBlock + 8 * kBlock + 2 * kBlock;
-        TRY(grow(ctx, &ctx->pers_stamps, &ctx->pers_stamps_cap, ns));
-        HIPCHK(hipMemsetAsync(ctx->pers_stamps, 0, sizeof(unsigned long long) * ns, ctx->st));
-    }
-    TRY(grow(ctx, &ctx->pers_sync, &ctx->pers_sync_cap, kPersistSyncWords));
-    // the barrier words count on from the previous launch of the same grid (no memset launch);
-    // zeroed on the first launch, when the grid changes and after an aborted launch
-    if (!ctx->pers_sync_valid || ctx->pers_grid != grid) {
-        HIPCHK(hipMemsetAsync(ctx->pers_sync, 0, kPersistSyncWords * sizeof(unsigned), ctx->st));
-        ctx->pers_epoch_base = 0;
-        ctx->pers_grid = grid;
-    }
-    ctx->pers_sync_valid = false; // (until this launch has completed cleanly)
-    ctx->h_flags[3] = 0; // abort word (mapped host)
-    ctx->h_flags[7] = 0; // barriers used (mapped host)
-    PersistArgs a{};
-    a.img = ctx->pm_img;
-    a.nblk = (int)ctx->pm_blocks;
-    a.nm = (int)ctx->nm;
-    a.n = (int)n;
-    a.px = P.x;
-    a.py = P.y;
-    a.pz = P.z;
-    a.yx = Y.x;
-    a.yy = Y.y;
-    a.yz = Y.z;
-    a.p32 = P.f;
-    a.idx = ctx->idx;
-    a.part = ctx->pers_part;
-    a.sync = ctx->pers_sync;
-    a.h_abort = ctx->d_flags + 3;
-    a.N = (double)ctx->np_total;
-    a.c0 = ctx->c[0];
-    a.c1 = ctx->c[1];
-    a.c2 = ctx->c[2];
-    a.threshold = threshold;
-    a.max_iter = max_iter;
-    a.err_trace = ctx->err_trace_dev;
-    a.s_glob = ctx->iter_state;
-    a.h_state = ctx->d_iter_mirror;
-    a.h_trace = ctx->d_trace;
-    a.stamps = stamps ? ctx->pers_stamps : nullptr;
-    static const int cull = [] { // ICP_PERSIST_NN=all: every model point for every query (A/B)
-        const char *e = getenv("ICP_PERSIST_NN");
-        return e && std::strcmp(e, "all") == 0 ? 0 : 1;
-    }();
-    a.cull = cull;
-    a.epoch_base = ctx->pers_epoch_base;
-    a.h_epochs = ctx->d_flags + 7;
-    { // tests: ICP_PERSIST_TEST_ABORT=1 makes the first barrier fail as if a workgroup never came
-        const char *e = getenv("ICP_PERSIST_TEST_ABORT");
-        a.test_abort = e && e[0] == '1';
-    }
-    for (int k = 0; k < 3; ++k) a.m0[k] = ctx->model_host[k];
-    if (mid) {
-        // the first search is seeded by the resident correspondences if they pair this scene
-        // already; else every query descends to its nearest-box block (ICP_MID_PREPASS=1: one
-        // pass of the exact cascade instead, for A/B runs)
-        static const bool prepass = [] {
-            const char *e = getenv("ICP_MID_PREPASS");
-            return e && e[0] == '1';
-        }();
-        if (!ctx->seeds_valid && prepass) {
-            launch_run_init(ctx->iter_state, ctx->amb_count, ctx->st);
-            TRY(nn_search_begin(ctx, P, n, false, nullptr, nullptr, false, nullptr, &ctx->iter_state->done));
-        }
-        TRY(grow(ctx, &ctx->mid_q4, &ctx->mid_q4_cap, 4 * n));
-        TRY(grow(ctx, &ctx->mid_res, &ctx->mid_res_cap, n));
-        TRY(grow(ctx, &ctx->mid_perm, &ctx->mid_perm_cap, n));
-        const size_t ob = mid_order_scratch_bytes((int)n);
-        TRY(grow(ctx, (char **)&ctx->mid_cnt, &ctx->mid_cnt_cap, ob));
-        if (launch_mid_order(P.x, P.y, P.z, (int)n, ctx->m_lo, ctx->m_hi, ctx->mid_cnt, ob, ctx->mid_perm, ctx->st))
-            return fail(ctx, ICP_E_HIP, "icp_run: the mid-size search order (radix sort) failed");
-        LAUNCHCHK("mid_order");
-        a.perm = ctx->mid_perm;
-        a.seed_big = ctx->pm_seed_big;
-        a.seed_idx = ctx->seeds_valid || prepass ? ctx->idx : nullptr;
-        a.m4 = ctx->m4;
-        a.q4 = ctx->mid_q4;
-        a.res = ctx->mid_res;
-        launch_icp_persistent_mid(a, grid, lds, ctx->st);
-    } else {
-        launch_icp_persistent(a, grid, lds, ctx->st);
-    }
-    LAUNCHCHK("icp_persistent");
-    if (stamps) { // (the timers of every workgroup: the whole grid must have finished)
-        HIPCHK(hipStreamSynchronize(ctx->st));
-    } else { // workgroup 0's last store (h_flags[7] = barriers used, a release after the run's
-             // mirrored state); an aborted launch never writes it and ends with the stream
-        // (the stream queried after 2 ms, then every 2 ms: each query leaves a marker behind the
-        // launch, which the next launch waits for -- see wait_flag)
-        auto next = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-        for (unsigned spin = 1; __atomic_load_n(ctx->h_flags + 7, __ATOMIC_ACQUIRE) == 0; ++spin) {
-            if ((spin & 1023u) == 0 && std::chrono::steady_clock::now() >= next) {
-                next = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-                const hipError_t q = hipStreamQuery(ctx->st);
-                if (q == hipErrorNotReady) continue;
-                if (q != hipSuccess) return fail(ctx, ICP_E_HIP, std::string("icp_run: ") + hipGetErrorString(q));
-                break; // (finished: aborted, or the word landed just now)
-            }
-            __builtin_ia32_pause();
-        }
-    }
-    if (stamps) { // phase durations of workgroup 0 (tags: 0 NN begin, 1 NN end, 2 published,
-                  // 3 barrier passed, 8 partials loaded, 4 folded, 5 Horn done, 6 transformed, 7 end)
-        std::vector<unsigned long long> h(2 * kPersistMaxStamps + 2 * kBlock + 8 * kBlock + 2 * kBlock);
-        HIPCHK(hipMemcpy(h.data(), ctx->pers_stamps, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-        double acc[9] = {0}, cntp[9] = {0};
-        for (int k = 1; k < kPersistMaxStamps && h[2 * k + 1]; ++k) {
-            const int tag = (int)h[2 * k];
-            acc[tag] += (double)(h[2 * k + 1] - h[2 * k - 1]) * 0.01; // 100 MHz -> us
-            cntp[tag] += 1;
-        }
-        if (mid) { // workgroup 0's NN phase (tag 0 -> 1, its barrier wait included) per iteration
-            fprintf(stderr, "[persist-mid] NN per iteration (us):");
-            for (int k = 1; k < kPersistMaxStamps && h[2 * k + 1]; ++k)
-                if (h[2 * k] == 1 && h[2 * k - 2] == 0) fprintf(stderr, " %.0f", (double)(h[2 * k + 1] - h[2 * k - 1]) * 0.01);
-            fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "[persist] grid %d lds %zu: us ending at tag (calls):", grid, lds);
-        for (int t = 0; t < 9; ++t) fprintf(stderr, " %d:%.2f(%g)", t, acc[t], cntp[t]);
-        double nmin = 1e30, nmax = 0, nsum = 0, bmin = 1e30, bmax = 0, bsum = 0;
-        for (int w = 0; w < grid; ++w) {
-            const double tn = h[2 * kPersistMaxStamps + 2 * w] * 0.01, tb = h[2 * kPersistMaxStamps + 2 * w + 1] * 0.01;
-            nmin = std::min(nmin, tn), nmax = std::max(nmax, tn), nsum += tn;
-            bmin = std::min(bmin, tb), bmax = std::max(bmax, tb), bsum += tb;
-        }
-        fprintf(stderr, " | per-wg NN min/mean/max %.1f/%.1f/%.1f barrier %.1f/%.1f/%.1f us\n", nmin, nsum / grid, nmax,
-                bmin, bsum / grid, bmax);
-        if (mid) { // per workgroup: NN us (all iterations, first), superblocks / tile rounds / blocks per query
-            const unsigned long long *w = h.data() + 2 * kPersistMaxStamps + 2 * kBlock;
-            double mx[5] = {0}, sm[5] = {0};
-            for (int g = 0; g < grid; ++g) {
-                const double q = std::max<double>(1.0, (double)w[8 * g + 5]);
-                const double v[5] = {w[8 * g] * 0.01, w[8 * g + 1] * 0.01, w[8 * g + 2] / q, w[8 * g + 3] / q, w[8 * g + 4] / q};
-                for (int k = 0; k < 5; ++k) mx[k] = std::max(mx[k], v[k]), sm[k] += v[k];
-            }
-            double tph[4] = {0, 0, 0, 0}, cnt[3] = {0, 0, 0};
-            for (int g = 0; g < grid; ++g) {
-                tph[0] += (double)(w[8 * g + 6] & 0xffffffffu) * 0.01;
-                tph[1] += (double)(w[8 * g + 6] >> 32) * 0.01;
-                tph[2] += (double)(w[8 * g + 7] & 0xffffffffu) * 0.01;
-                tph[3] += (double)(w[8 * g + 7] >> 32) * 0.01;
-                for (int k = 0; k < 3; ++k) cnt[k] += (double)w[8 * g + 2 + k];
-            }
-            const double nbat = (double)((ctx->scene.n + 3) / 4) * std::max(1, ctx->h_iter->iter);
-            double wsum = 0, wmax = 0; // per-wave busy time, summed over the iterations (max: of one iteration)
-            for (int g = 0; g < grid; ++g) {
-                wsum += (double)w[8 * kBlock + 2 * g] * 0.01;
-                wmax = std::max(wmax, (double)w[8 * kBlock + 2 * g + 1] * 0.01);
-            }
-            const int iters = std::max(1, ctx->h_iter->iter);
-            fprintf(stderr, "[persist-mid] wave busy per NN: mean %.1f us, slowest wave of any NN %.1f us\n",
-                    wsum / (grid * 8.0 * iters), wmax);
-            fprintf(stderr, "[persist-mid] per wg NN mean/max %.1f/%.1f us (first %.1f/%.1f) | per batch: superblocks %.2f "
-                            "tile rounds %.2f blocks %.2f | per batch us: query loads %.2f tests %.2f gathers %.2f reduce+store %.2f\n",
-                    sm[0] / grid, mx[0], sm[1] / grid, mx[1], cnt[0] / nbat, cnt[1] / nbat, cnt[2] / nbat, tph[0] / nbat,
-                    tph[1] / nbat, tph[2] / nbat, tph[3] / nbat);
-        }
-    }
-    const int aborted = __atomic_load_n(ctx->h_flags + 3, __ATOMIC_ACQUIRE);
-    if (aborted == 1) { // at the first barrier: not co-resident, nothing written -> the launch loop
-        ctx->stats.persistent_fallbacks += 1;
-        return kPersistFallback;
-    }
-    if (aborted != 0)
-        return fail(ctx, ICP_E_HIP, "icp_run: a grid barrier of the one-launch loop timed out (workgroups not co-resident)");
-    ctx->pers_epoch_base += (unsigned)__atomic_load_n(ctx->h_flags + 7, __ATOMIC_ACQUIRE);
-    ctx->pers_sync_valid = true;
-    ctx->seeds_valid = true;
-    ctx->seedd_valid = false; // (the one-launch loop keeps no seed distances)
-    const int iters = ctx->h_iter->iter;
-    ctx->stats.nn_pairs += (long long)iters * (long long)n * (long long)ctx->nm;
-    ctx->stats.persistent_runs += 1;
-    ctx->stats.last_filter = ICP_FILTER_ONE_LAUNCH;
-    return finish_run(ctx, threshold, err_trace, res, wall0);
-}
-
-// The loop of GPU::ICP::find_corresponding_opti (gpu.cc:52-83), device-resident: every
-// iteration is enqueued without waiting on the previous one -- NN search, moments and their
-// all-reduces, the Horn solve (horn_step, the host's own code), transform + residual and its
-// all-reduce, the error test (err_step).  The host runs one iteration ahead: it enqueues
-// iteration i+1, then waits for iteration i's completion event and its (done, iter) flag.
-// After the iteration whose err < threshold the device flag freezes the state (the one
-// iteration already enqueued behind it changes nothing), which is exactly where the
-// reference's loop breaks (gpu.cc:79-80).
-static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool no_tail);
-static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
-                     std::chrono::steady_clock::time_point wall0);
-constexpr int kTailAborted = -1000; // run_loop: a fused tail's grid barrier timed out (state restored)
-
-int icp_run(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res)
-{
-    // (icp_set_progress: reset once per icp_run -- a rerun below replays the same iterations bit for
-    // bit, and report_progress skips the ones the aborted attempt already reported)
-    if (ctx) ctx->progress_next = 0;
-    const int r = run_loop(ctx, max_iter, threshold, err_trace, res, false);
-    if (r != kTailAborted) return r;
-    // A grid barrier of the fused mid-size tail timed out (its workgroups were not all resident:
-    // another process's persistent kernel on the same GPU).  The scene and correspondences the
-    // run started from were restored; the same registration again with the separate launches
-    // (bit-identical, icp_iter.hip) -- the stats count both attempts.
-    return run_loop(ctx, max_iter, threshold, err_trace, res, true);
-}
-
-// ICP_FIRST_K1=1: the canonical first iteration's search and moments as one fused launch (A/B)
-static bool first_k1_env()
-{
-    static const bool on = [] {
-        const char *e = getenv("ICP_FIRST_K1");
-        return e && atoi(e) == 1;
-    }();
-    return on;
-}
-
-static int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool no_tail)
-{
-    TRY(check_ready(ctx, true));
-    TRY(scene_revert_now(ctx));
-    // alignement_check (gpu.cc:54-62)
-    if (ctx->np_total != ctx->nm && !ctx->allow_unequal)
-        return fail(ctx, ICP_E_SIZE_MISMATCH, "Point sets need to have the same number of points.");
-    if (ctx->np_total < 4) return fail(ctx, ICP_E_TOO_FEW_POINTS, "Need at least 4 point pairs");
-
-    const auto wall0 = std::chrono::steady_clock::now();
-    const size_t n = ctx->scene.n;
-    const double N = (double)ctx->np_total;
-    DevCloud &P = ctx->scene, &Y = ctx->Y;
-    constexpr int kAhead = 1, kRing = 4; // iterations in flight beyond the one waited on
-    TRY(grow(ctx, &ctx->iter_state, &ctx->iter_state_cap, 1));
-    if (!ctx->h_iter) {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_iter, sizeof(IterState), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_iter_mirror, ctx->h_iter, 0));
-    }
-    if (ctx->trace_cap < (size_t)std::max(max_iter, 1)) { // (the previous run ended with a sync)
-        if (ctx->h_trace) HIPCHK(hipHostFree(ctx->h_trace));
-        ctx->trace_cap = (size_t)std::max(max_iter, 64);
-        HIPCHK(hipHostMalloc((void **)&ctx->h_trace, sizeof(double) * ctx->trace_cap,
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_trace, ctx->h_trace, 0));
-    }
-    std::memset(ctx->h_iter, 0, sizeof(IterState));
-    if (!ctx->h_flags) {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_flags, sizeof(int) * 4 * kRing,
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(ctx->h_flags, 0, sizeof(int) * 4 * kRing);
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_flags, ctx->h_flags, 0));
-    }
-    // seeded f16 searches: each transform writes the next search's seeds (no seed kernel)
-    const bool fuse_seeds = ctx->nn_mode == ICP_NN_CERTIFIED && level1_kind(ctx, n) >= 2;
-    SeedArgs sa;
-    if (fuse_seeds) {
-        TRY(grow(ctx, &ctx->seed16, &ctx->seed16_cap, n));
-        sa.seed16 = ctx->seed16;
-        for (int a = 0; a < 3; ++a) sa.c[a] = ctx->c[a];
-        sa.scale = ctx->scale16;
-        if (level1_kind(ctx, n) == 3 && bundle_v2()) { // the bundle filter's seed distances too
-            TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
-            sa.seedd = ctx->b_seedd;
-        }
-    }
-    static const bool transform_records = [] { // ICP_TRANSFORM_RECORDS=0: the prep kernel writes them (A/B)
-        const char *e = getenv("ICP_TRANSFORM_RECORDS");
-        return !(e && atoi(e) == 0);
-    }();
-    int slot_ticket[kRing] = {};
-    TRY(grow(ctx, &ctx->err_trace_dev, &ctx->err_trace_cap, (size_t)(max_iter > 0 ? max_iter : 1)));
-    while (ctx->iter_ev.size() < 5 * (size_t)kRing) { // (nn begin, nn end, -, all-reduce begin, end) per slot
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-        ctx->iter_ev.push_back(e);
-    }
-    // the scene's fp32 copy is read only by the fp32 filters (level 1 VALU / f32 MFMA), their
-    // windowed resolve and the one-launch paths: other runs let the transform skip it (16 B a
-    // point) and leave it to be refreshed here when a later run needs it
-    const bool need_p32 = (ctx->nn_mode == ICP_NN_CERTIFIED && level1_kind(ctx, n) <= 1 &&
-                           ctx->nn_variant != ICP_NN_VARIANT_GRID) ||
-                          n <= (size_t)kTailMaxBlocks * kBlock;
-    if (need_p32 && ctx->p32_stale) {
-        if (n) launch_make_f32(P.x, P.y, P.z, n, ctx->c[0], ctx->c[1], ctx->c[2], P.f, ctx->st);
-        LAUNCHCHK("make_f32");
-        ctx->p32_stale = false;
-    }
-    // icp_set_max_distance: the gated loop (never the one-launch kernels or the fused iterations)
-    if (ctx->gate_dmax > 0.0) return run_gated(ctx, max_iter, threshold, err_trace, res, need_p32, wall0);
-    {
-        size_t lds = 0;
-        bool mid = false;
-        const int grid = persistent_grid(ctx, n, max_iter, &lds, &mid);
-        if (grid) {
-            const int r = run_persistent(ctx, grid, lds, mid, max_iter, threshold, err_trace, res, wall0);
-            if (r != kPersistFallback) return r;
-        }
-    }
-    if (want_slot_order(ctx, n)) TRY(scene_to_slot_order(ctx));
-    if (ctx->scene_slot && ctx->nn_variant == ICP_NN_VARIANT_GRID && ctx->nn_mode == ICP_NN_CERTIFIED && !sa.seedd) {
-        // the grid variant's seeded searches read the transform's seed distances too
-        TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
-        sa.seedd = ctx->b_seedd;
-    }
-    const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
-    // The search policy of AUTO at the bundle filter's sizes (the scene in slot order): a seeded
-    // search takes the grid (grid_seeded_search) instead of the bundle cascade when the last
-    // transform the host has seen left at most n/32 points farther than 1.5 grid cells from their
-    // correspondence (the queries whose box exceeds kSeededBox cells: the second, per-wave pass).  The decision for
-    // iteration k + 1 is taken when k is enqueued (k's transform writes the bundle's records and
-    // seeds only if k + 1 is a bundle search), on the count of an iteration one or two behind.
-    // Before any count is seen: the count the last run ended with when this run continues it
-    // (carry), else the grid while the bundle images are still unbuilt (bundle_pending: the
-    // first search is then the unseeded grid search, nn_search_begin), else the bundle cascade.
-    // A far count above the threshold builds the bundle images (ensure_bundle).  Both paths return the exact first
-    // minimum, so the trajectory is the same whichever runs.  ICP_GRID_AUTO=0: always the bundle.
-    const bool grid_policy = ctx->scene_slot && ctx->nn_mode == ICP_NN_CERTIFIED &&
-                             ctx->nn_variant == ICP_NN_VARIANT_AUTO && level1_kind(ctx, n) == 3 && grid_auto();
-    static const int far_shift = [] { // ICP_GRID_FAR_SHIFT: the threshold n >> shift (A/B)
-        const char *e = getenv("ICP_GRID_FAR_SHIFT");
-        const int v = e ? atoi(e) : 5;
-        return v >= 0 && v <= 20 ? v : 5;
-    }();
-    const int far_thr = std::max(16, (int)(n >> far_shift));
-    // a run that continues the last one (the same resident scene, its seed distances written by
-    // that run's last transform) starts from that run's last far count: its first searches need
-    // not be the bundle cascade's
-    const bool carry = grid_policy && ctx->seeds_valid && ctx->seedd_valid;
-    int far_obs = carry ? ctx->last_far : -1; // far_acc of the last iteration the host has seen
-    int q2_obs = carry ? ctx->last_q2 : -1;   // queued2 of the last iteration the host has seen
-    bool grid_next = carry && far_obs >= 0 && far_obs <= far_thr; // the path of the next search
-    SeedArgs sa_grid;       // a transform before a grid search: its seed distances only
-    // The far count's rule: a moved point whose complete box around its seed distance, clamped to
-    // the grid, exceeds kSeededBox cells -- the queries the seeded grid search could not take in
-    // its walk.  Round 4 counted points farther than 1.5 cells from their correspondence, which
-    // also counted the points outside the model's box whose clamped box is small: a C5 shard (3.9%
-    // of its points outside, 0.9% with a big box) then built the bundle images for its first
-    // iterations (15 ms of a 31 ms registration).  ICP_GRID_FAR=dist: the distance rule (A/B).
-    static const bool far_dist = [] {
-        const char *e = getenv("ICP_GRID_FAR");
-        return e && std::string(e) == "dist";
-    }();
-    if (grid_policy) {
-        const double h = 1.0 / ctx->grid.inv_h;
-        sa.far_acc = sa_grid.far_acc = &ctx->iter_state->far_acc;
-        sa.far_d2 = sa_grid.far_d2 = 2.25 * h * h;
-        if (!far_dist) {
-            sa.far_gv = sa_grid.far_gv = grid_view(ctx);
-            sa.far_box = sa_grid.far_box = kSeededBox;
-        }
-        sa_grid.seedd = sa.seedd; // (grid_seeded_search reads them: no gather of the seed point)
-    }
-    // What the last enqueued transform wrote for the next search (nn_search_begin uses each part
-    // only in the form it was written in).  A carried-over run starts from the last run's seed
-    // distances (seedd_valid); everything else is rebuilt by the first search.
-    SeedState ws;
-    ws.seedd = carry;
-    // The transform before a bundle search writes that search's slot records (the prep's output,
-    // in order) once the images exist and a bundle search of this size has sized the buffers --
-    // decided per transform, in the form the next search will run: the local pair test's with the
-    // current frames' R, else the global one.  (It was decided once at the start of the run:
-    // after icp_set_model the images are pending, b_rlmax is -1, and a run whose policy turned to
-    // the bundle mid-run then wrote global-form records for a search that, its images built in
-    // between, ran the local form -- the C5 registration stall)
-    auto records_args = [&](SeedArgs &s) {
-        if (!transform_records || !ctx->scene_slot || !fuse_seeds || !s.seed16 || !s.seedd || ctx->bundle_pending ||
-            ctx->nb_pad <= 0 || level1_kind(ctx, n) != 3 || !bundle_v2())
-            return;
-        const size_t nslots = bundle2_slots(plan_nn_bundle2(n, ctx->nb_pad));
-        if (!ctx->b_qop || ctx->b_qop_cap < nslots * 64 || ctx->b_gop_cap < nslots || ctx->b_gctr_cap < nslots / 32)
-            return;
-        s.qop = ctx->b_qop;
-        s.gop = ctx->b_gop;
-        s.gctr = ctx->b_gctr;
-        s.nslots = (int)nslots;
-        s.local_r = ctx->b_rlmax >= 0.0 && bundle_local() ? ctx->b_rlmax : -1.0; // (as the search decides)
-    };
-    launch_run_init(ctx->iter_state, ctx->amb_count, ctx->st, ctx->c);
-    // partials over several workgroups: the moments and / or the transform may fold their
-    // partials in their own last workgroup (StepFold), and on one rank go on there to the Horn
-    // step / the error step -- one launch fewer each, bit-identical.  ICP_FUSED_STEPS = bit 0:
-    // the moments, bit 1: the transform; 0 (the default): the separate launches.  Measured at C4
-    // (profiles/r04r): both fused 0.183 ms per iteration against 0.164 separate -- the last
-    // workgroup's fold reads the rows coherently (sc1: past L2), and the moments kernel with the
-    // Horn solve inlined holds 128 VGPRs
-    static const int fused_steps_env = [] {
-        const char *e = getenv("ICP_FUSED_STEPS");
-        return e ? atoi(e) & 3 : 0;
-    }();
-    const bool fused_moments = (fused_steps_env & 1) && red_blocks(n) > 1;
-    const bool fused_steps = (fused_steps_env & 2) && red_blocks(n) > 1; // (the transform's)
-    // multi-rank runs: the transform's residual partials wait in err_part, and the next
-    // iteration's moments fold folds them too (launch_reduce_pair: one launch fewer an iteration,
-    // the same bits); the last iteration folds its own before the final all-reduce
-    static const bool err_pair_env = [] { // ICP_ERR_PAIR=0: the separate residual fold (A/B)
-        const char *e = getenv("ICP_ERR_PAIR");
-        return !(e && e[0] == '0');
-    }();
-    const bool err_pair = err_pair_env && lag_run(ctx) && red_blocks(n) > 1 && !fused_steps && !fused_moments;
-    if (err_pair) TRY(grow(ctx, &ctx->err_part, &ctx->err_part_cap, (size_t)kRedMaxBlocksCap));
-    if ((fused_steps || fused_moments) && !ctx->fold_ticket) {
-        HIPCHK(hipMalloc((void **)&ctx->fold_ticket, 2 * sizeof(unsigned)));
-        HIPCHK(hipMemsetAsync(ctx->fold_ticket, 0, 2 * sizeof(unsigned), ctx->st));
-    }
-    // mid-size single-rank runs: iterations >= 2 end in ONE fused launch (moments ... error step)
-    static const int forced_mode = [] {
-        const char *e = getenv("ICP_RUN_MODE");
-        return e && std::strcmp(e, "launches") == 0 ? ICP_RUN_LAUNCHES : -1;
-    }();
-    const int tail_blocks = red_blocks(n);
-    const bool fused_tail = !no_tail && (forced_mode < 0 ? ctx->run_mode : forced_mode) != ICP_RUN_LAUNCHES &&
-                            !lag_run(ctx) && n > (size_t)kRedSingle && tail_blocks <= kTailMaxBlocks &&
-                            tail_blocks <= ctx->n_cu * 3 / 4;
-    unsigned tail_epoch = 0;
-    const bool seeds_at_start = ctx->seeds_valid;
-    if (fused_tail) {
-        TRY(grow(ctx, &ctx->tail_part, &ctx->tail_part_cap, (size_t)19 * kTailMaxBlocks));
-        TRY(grow(ctx, &ctx->tail_sync, &ctx->tail_sync_cap, kPersistSyncWords));
-        HIPCHK(hipMemsetAsync(ctx->tail_sync, 0, kPersistSyncWords * sizeof(unsigned), ctx->st));
-        ctx->h_flags[11] = 0; // its barriers' abort word (mapped host)
-        // the state the run starts from (n <= kTailMaxBlocks * kBlock points: a few MB), for
-        // the separate-launch rerun should a tail barrier time out
-        TRY(grow(ctx, &ctx->tail_backup, &ctx->tail_backup_cap, n * (3 * sizeof(double) + sizeof(float4) + sizeof(int))));
-        char *bk = ctx->tail_backup;
-        HIPCHK(hipMemcpyAsync(bk, P.x, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(bk + n * 8, P.y, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(bk + n * 16, P.z, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        if (P.f) HIPCHK(hipMemcpyAsync(bk + n * 24, P.f, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->st));
-        if (seeds_at_start) HIPCHK(hipMemcpyAsync(bk + n * 40, ctx->idx, n * sizeof(int), hipMemcpyDeviceToDevice, ctx->st));
-    }
-    if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
-    bool ar_timed[kRing] = {};
-    IterState *sd = ctx->iter_state;
-    int enqueued = 0, waited = 0, recorded = 0;
-    bool stop = false;
-    // With an all-reduce (ranks > 1, or a 1-rank communicator) each iteration has ONE: the
-    // moments' 17 sums plus the previous iteration's residual e, whose err_step therefore runs
-    // one iteration late (before this iteration's Horn solve, so a converged state is still
-    // frozen at the same point).  Without one, err_step follows its own transform.
-    const bool lag = ctx->comm != nullptr || ctx->world > 1;
-    // The O(N*M) kernel is timed (two events; on multi-rank runs two more around the
-    // all-reduce) every 8th iteration: each event marker leaves a ~4.4 us gap in the stream,
-    // which at the bundle filter's C4 iteration (~0.25 ms) is 3.5% per iteration for the filter's
-    // pair and ~11% of a W = 8 shard's 0.15 ms iteration for all four (profiles/r03bf/ kernel
-    // trace).  stats.nn_ms / nn_launches stays the mean of the timed launches.
-    // ICP_NN_TIMING_STRIDE overrides (1: every iteration, as before for searches of >= 2^32 pairs).
-    static const int forced_stride = [] {
-        const char *e = getenv("ICP_NN_TIMING_STRIDE");
-        return e ? std::max(1, atoi(e)) : 0;
-    }();
-    const int timing_stride = forced_stride ? forced_stride : 8;
-    // the sampled iterations rotate from run to run (run r: those = r mod the stride), so that over
-    // a stride's worth of registrations every iteration index is timed once -- the mean of the timed
-    // launches is then the mean of all of them, as a kernel trace of the same runs gives it (a fixed
-    // phase sampled iterations 1, 9, 17, 25 only, the slower early ones among them); iteration 0
-    // (its search unseeded) is never sampled
-    const int timing_phase = timing_stride > 1 ? (int)(ctx->runs++ % (unsigned)timing_stride) : 0;
-    // (partials: the residual's unreduced rows, folded in the same launch)
-    // (horn: this iteration's Horn step in the same single-thread launch, right after it)
-    auto enqueue_err_step = [&](int it, const double *partials = nullptr, bool horn = false) -> int {
-        const int sl = it % kRing;
-        // (done, iter) straight into mapped host memory, then the slot's ticket
-        slot_ticket[sl] = ++ctx->flag_ticket;
-        if (horn)
-            launch_err_horn_step(ctx->sums, N, threshold, max_iter, ctx->err_trace_dev, sd, ctx->d_flags + 4 * sl,
-                                 slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace, ctx->c, 1, ctx->amb_count,
-                                 ctx->st);
-        else
-            launch_err_step(ctx->sums, N, threshold, max_iter, ctx->err_trace_dev, sd, ctx->d_flags + 4 * sl,
-                            slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace, ctx->st, partials, red_blocks(n));
-        LAUNCHCHK("err_step");
-        return ICP_OK;
-    };
-    // A run that starts with the bundle images pending and nothing carried over has no far count
-    // until its first iteration completes: the host waits for it before enqueuing the second, so
-    // that the second search's path is decided on a count (a blind grid search right after the
-    // first alignment scans boxes as big as the first transform's moves)
-    // (only a shard against a model of at least twice its points, whose first transform leaves more
-    // than n/32 points far -- C5's shards: 40,739 of 2^20 by a CPU model; a scene of
-    // the model's size goes straight on to the grid -- C4: 107 big boxes, searched in the fused
-    // kernel -- without the synchronisation)
-    const bool hold_first = grid_policy && !carry && ctx->bundle_pending && ctx->nm >= 2 * n;
-    // the canonical schedule's path rule (below): fold_far[j] = the far count mirrored with
-    // iteration j's (lagged) error step -- transform j's, counted by iteration j + 1's search kernel
-    // (all ranks'); hold_far = transform 0's, read by hold_first
-    std::vector<int> fold_far((size_t)std::max(max_iter, 1), -1);
-    int hold_far = -1;
-    // ICP_TEST_ENQUEUE_DELAY_US: the host sleeps this long before each enqueue attempt (tests: the
-    // path sequence must not depend on how far the host runs ahead)
-    const int enqueue_delay_us = [] {
-        const char *e = getenv("ICP_TEST_ENQUEUE_DELAY_US");
-        return e ? std::max(0, atoi(e)) : 0;
-    }();
-    ctx->stats.run_path_bits = 0;
-    // A scene in slot order (C4, C5, their shards): the canonical schedule (icp_canon.h).  The
-    // transform of iteration k - 1 is enqueued at the start of iteration k, right before its
-    // search, in the form that search reads; its residual and k's moments go to the canonical
-    // rows, and ONE fold launch ends iteration k with k - 1's error step and k's Horn step (with
-    // ranks: the fold, the all-reduce of the 18 sums, the error + Horn step) -- the error test
-    // runs one iteration late, as the multi-rank loop's always did, and the scene freezes at the
-    // same point.  Every search path adds to the same rows in the same order, so the NN variants'
-    // trajectories stay bitwise equal.  ICP_CANON=0: the round-4 schedule (A/B).
-    static const bool canon_env = [] {
-        const char *e = getenv("ICP_CANON");
-        return !(e && e[0] == '0');
-    }();
-    const bool canon = canon_env && ctx->scene_slot && n > 0;
-    if (canon) {
-        TRY(grow(ctx, &ctx->canon_rowbuf, &ctx->canon_rowbuf_cap, (size_t)canon_strands(n) * kCanonCols)); // (rows, or strands)
-        if (!ctx->h_far) HIPCHK(hipHostMalloc((void **)&ctx->h_far, sizeof(int), hipHostMallocDefault));
-        // the first iteration's shift of p: the scene's centroid (all ranks'), where run_init put the
-        // model's centre c -- a scene far from the model would otherwise cancel (D / sigma)^2 of the
-        // one-pass moments' precision (the shift of y follows the first search: the mean of a sample
-        // of its correspondences, launch_first_shift_y_sample below)
-        launch_sum3(P.x, P.y, P.z, (int)n, red_target(ctx, n, ctx->sums + kSumScene), ctx->st, 1);
-        red_finish(ctx, n, 3, ctx->sums + kSumScene);
-        LAUNCHCHK("scene_sum");
-        TRY(allreduce(ctx, ctx->sums + kSumScene, 3));
-        // (set with the shift of y, after the first search; ICP_FIRST_K1=1 sums its first moments
-        // inside that search's launch and needs it now: its shift of y stays c)
-        if (first_k1_env()) {
-            launch_first_shift(sd, ctx->sums + kSumScene, N, ctx->st);
-            LAUNCHCHK("first_shift");
-        }
-    }
-    const bool lag_sched = lag || canon;
-    // The fused grid iteration's exclusion certificate (icp_grid.hip): the state one fused
-    // iteration writes is read by the next one of this run only (cert_prev); any other search
-    // leaves it stale.  ICP_CERT=0: every query walks (A/B); ICP_CERT_TWO=0: the one-point form;
-    // ICP_CERT_SKIN: the walk's extra radius in grid cells (default 0.25).
-    static const bool cert_env = [] {
-        const char *e = getenv("ICP_CERT");
-        return !(e && e[0] == '0');
-    }();
-    static const int cert_two = [] {
-        const char *e = getenv("ICP_CERT_TWO");
-        return e && e[0] == '0' ? 0 : 1;
-    }();
-    static const double cert_skin = [] {
-        const char *e = getenv("ICP_CERT_SKIN");
-        const double v = e ? atof(e) : 0.25;
-        return v >= 0.0 && v <= 4.0 ? v : 0.25;
-    }();
-    static const double cert_skin1 = [] { // ICP_CERT_SKIN1: the skin of a launch with no state to read (A/B)
-        const char *e = getenv("ICP_CERT_SKIN1");
-        const double v = e ? atof(e) : -1.0;
-        return v >= 0.0 && v <= 4.0 ? v : cert_skin;
-    }();
-    CertArgs cert;
-    bool cert_prev = false;
-    if (canon && cert_env && grid_iter_on() && ctx->g_pts32) {
-        TRY(grow(ctx, &ctx->cert_state, &ctx->cert_state_cap, n));
-        // the counts accumulate on the device over the runs of one scene size (64-bit: no wrap),
-        // read when the stats are; another size folds them into the stats first (a synchronisation
-        // the runs of a registration loop do not pay: 60 us a run at C4, profiles/r06/r06fold3)
-        const int crows = canon_strands(n); // (rows or strands: nn_grid_iter2_kernel NWG)
-        if (ctx->cert_counts_rows != crows) {
-            TRY(fold_cert_counts(ctx));
-            TRY(grow(ctx, &ctx->cert_counts, &ctx->cert_counts_cap, 2 * (size_t)crows));
-            HIPCHK(hipMemsetAsync(ctx->cert_counts, 0, 2 * (size_t)crows * sizeof(ctx->cert_counts[0]), ctx->st));
-            ctx->cert_counts_rows = crows;
-        }
-        cert.state = ctx->cert_state;
-        cert.two = cert_two;
-        cert.skin = cert_skin / ctx->grid.inv_h;
-        cert.counts = ctx->cert_counts;
-    }
-    // ICP_ITER_DEBUG=1: nn_grid_iter_kernel's phase clocks and counts, summed over the run, to stderr
-    static const bool iter_debug = getenv("ICP_ITER_DEBUG") != nullptr;
-    static const bool iter_debug_each = iter_debug && atoi(getenv("ICP_ITER_DEBUG")) == 2;
-    unsigned long long *iter_dbg = nullptr;
-    if (iter_debug && canon) {
-        static unsigned long long *buf = nullptr;
-        if (!buf) HIPCHK(hipMalloc((void **)&buf, 16 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(buf, 0, 16 * sizeof(unsigned long long), ctx->st));
-        iter_dbg = buf;
-    }
-    bool xf_pending = false; // (canon: the last Horn step's transform is still to be applied)
-    CanonStep cs;
-    cs.N = N;
-    cs.threshold = threshold;
-    cs.max_iter = max_iter;
-    cs.err_trace = ctx->err_trace_dev;
-    cs.s = sd;
-    cs.h_state = ctx->d_iter_mirror;
-    cs.h_trace = ctx->d_trace;
-    for (int a = 0; a < 3; ++a) cs.c[a] = ctx->c[a];
-    cs.cnt = ctx->amb_count;
-    if (!ctx->canon_ticket) {
-        HIPCHK(hipMalloc((void **)&ctx->canon_ticket, sizeof(int)));
-        HIPCHK(hipMemsetAsync(ctx->canon_ticket, 0, sizeof(int), ctx->st));
-    }
-    cs.fold_ticket = ctx->canon_ticket;
-    int rows_strands = 0; // (> 0: the last fused launch wrote the canonical rows as this many strands)
-    // the canonical transform of the last Horn step's (s, R, t), in the form sa_t (its residual into
-    // the rows' kSumErr column, and what the next search reads)
-    auto canon_transform = [&](SeedArgs sa_t) -> int {
-        launch_canon_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                               ctx->canon_rowbuf, sa_t, ctx->st);
-        LAUNCHCHK("canon_transform");
-        if (!need_p32) ctx->p32_stale = true;
-        ws = SeedState{};
-        ws.seedd = sa_t.seedd != nullptr;
-        ws.seed16 = !sa_t.seed16 ? 0 : sa_t.qop && sa_t.local_r >= 0.0 ? 2 : 1;
-        ws.records = sa_t.qop != nullptr;
-        ws.rec_local = sa_t.qop ? sa_t.local_r : -1.0;
-        xf_pending = false;
-        return ICP_OK;
-    };
-    // canon: the error step of iteration `it` (ticket of its slot) after the fold of the rows --
-    // with the Horn step of the current iteration (horn) or alone (the run's last residual)
-    auto canon_end = [&](int it, bool horn, int slot) -> int {
-        const int sl = it % kRing;
-        slot_ticket[sl] = ++ctx->flag_ticket;
-        cs.hflag = ctx->d_flags + 4 * sl;
-        cs.ticket = slot_ticket[sl];
-        const int strands = rows_strands; // (the fused kernel wrote the rows as strands)
-        rows_strands = 0;
-        if (!lag) {
-            launch_canon_fold(ctx->canon_rowbuf, (int)n, ctx->sums, horn ? 1 : 2, cs, ctx->st, strands);
-            LAUNCHCHK("canon_fold");
-            return ICP_OK;
-        }
-        launch_canon_fold(ctx->canon_rowbuf, (int)n, ctx->sums, horn ? 0 : 3, cs, ctx->st, strands);
-        LAUNCHCHK("canon_fold");
-        const bool tm = horn && slot >= 0 && ar_timed[slot];
-        if (tm) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 3], ctx->st));
-        // (the policy's runs: the far count rides along as a 19th sum, so every rank decides on the
-        // same global count -- run_loop's path rule)
-        TRY(horn ? allreduce(ctx, ctx->sums, grid_policy ? kNumSums + 1 : kNumSums)
-                 : allreduce(ctx, ctx->sums + kSumErr, 1));
-        if (tm) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 4], ctx->st));
-        if (horn)
-            launch_err_horn_step(ctx->sums, N, threshold, max_iter, ctx->err_trace_dev, sd, cs.hflag, cs.ticket,
-                                 ctx->d_iter_mirror, ctx->d_trace, ctx->c, 1, ctx->amb_count, ctx->st,
-                                 grid_policy ? 1 : 0);
-        else
-            launch_err_step(ctx->sums, N, threshold, max_iter, ctx->err_trace_dev, sd, cs.hflag, cs.ticket,
-                            ctx->d_iter_mirror, ctx->d_trace, ctx->st, nullptr, 0);
-        LAUNCHCHK("err_step");
-        return ICP_OK;
-    };
-    // canon: a run's first iteration ends in the Horn step alone -- its moments in one pass
-    // around the shifts run_init set (c), no error step before it (round 4: the reference's two
-    // passes and an unshifted Horn step, four more launches)
-    auto canon_first = [&]() -> int {
-        const int strands = rows_strands;
-        rows_strands = 0;
-        if (!lag) {
-            launch_canon_fold(ctx->canon_rowbuf, (int)n, ctx->sums, 4, cs, ctx->st, strands);
-            LAUNCHCHK("canon_fold");
-            return ICP_OK;
-        }
-        launch_canon_fold(ctx->canon_rowbuf, (int)n, ctx->sums, 0, cs, ctx->st, strands);
-        LAUNCHCHK("canon_fold");
-        TRY(allreduce(ctx, ctx->sums, kNumSums));
-        launch_horn_step(ctx->sums, N, ctx->c, true, ctx->amb_count, sd, ctx->st);
-        LAUNCHCHK("horn_step");
-        return ICP_OK;
-    };
-    while (!stop && waited < max_iter) {
-        if (enqueue_delay_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(enqueue_delay_us));
-        if (enqueued < max_iter && enqueued - waited <= kAhead + (lag_sched ? 1 : 0) &&
-            !(!canon && hold_first && enqueued == 1 && waited == 0) &&
-            !(canon && grid_policy && enqueued >= 3 && waited < enqueued - 2)) { // (fold_far[enqueued - 3] known)
-            const int slot = enqueued % kRing;
-            // 1. correspondences: compute_Y_w_opti(m, new_p, Y)  (gpu.cc:69)
-            const bool timed = enqueued % timing_stride == timing_phase && (enqueued > 0 || timing_stride == 1);
-            if (canon) {
-                // The path of search k: on the far count of transform k - 3 (counted by iteration
-                // k - 2's search kernel, mirrored with iteration k - 3's lagged error step; all
-                // ranks' on several: kSumFar), which the host has waited for before enqueuing k
-                // (below: iteration k - 1 may still run meanwhile) -- the same count whatever the
-                // host's lead over the device, and on every rank.  Before that count exists:
-                // transform 0's count when hold_first read it, else the count the last run ended
-                // with (carry), else the grid while the bundle images are pending.
-                const int far_dec = enqueued >= 3 ? fold_far[enqueued - 3] : hold_far >= 0 ? hold_far : carry ? ctx->last_far : -1;
-                bool grid_c = grid_policy && (far_dec >= 0 ? far_dec <= far_thr : enqueued == 0 ? grid_next : ctx->bundle_pending);
-                if (xf_pending && hold_first && enqueued == 1 && far_dec < 0) {
-                    // the images pending and no count yet: the first transform, then its far count
-                    // (all ranks'), before the second search's path is chosen (one synchronisation a run)
-                    TRY(canon_transform(sa_grid));
-                    HIPCHK(hipMemcpyAsync(ctx->h_far, &sd->far_acc, sizeof(int), hipMemcpyDeviceToHost, ctx->st));
-                    HIPCHK(hipStreamSynchronize(ctx->st));
-                    hold_far = *ctx->h_far;
-                    if (lag) TRY(global_count(ctx, &hold_far));
-                    far_obs = hold_far;
-                    grid_c = hold_far <= far_thr;
-                }
-                // a fresh run's first iteration on the grid as ONE launch too: cell seeds (their
-                // coordinates as the correspondences), then the fused kernel with no pending
-                // transform -- the search nn_search_begin would run (its unseeded grid path) and the
-                // one-pass moments, into the same rows
-                // (ICP_FIRST_K1=1; measured slower: the cell seeds' big boxes, 0.4% of the queries, are
-                // each the whole owning wave's serial work there, where the seeded pass queues them for
-                // a second pass of one wave each -- first iteration 0.53 against 0.37 ms, profiles/r05ab)
-                static const bool first_k1 = first_k1_env();
-                const bool k1_first =
-                    first_k1 && grid_iter_on() && enqueued == 0 && !xf_pending && !ctx->seeds_valid && cell_seed_on() &&
-                    ctx->nn_mode == ICP_NN_CERTIFIED && ctx->nn_rule == ICP_NN_RULE_SQUARED && ctx->g_pts32 &&
-                    (ctx->nn_variant == ICP_NN_VARIANT_GRID ||
-                     (ctx->nn_variant == ICP_NN_VARIANT_AUTO && ctx->bundle_pending && level1_kind(ctx, n) == 3));
-                if (k1_first) {
-                    TRY(grow(ctx, &ctx->idx, &ctx->idx_cap, n));
-                    launch_nn_grid_cell_seed((int)n, P.x, P.y, P.z, grid_view(ctx), (int)ctx->nm, ctx->idx, nullptr,
-                                             ctx->st, Y.x, Y.y, Y.z);
-                    LAUNCHCHK("nn_grid_cell_seed");
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot], ctx->st));
-                    cert.valid = 0;
-                    cert.skin = cert_skin1 / ctx->grid.inv_h;
-                    cert_prev = launch_nn_grid_iter((int)n, P.x, P.y, P.z, Y.x, Y.y, Y.z, ctx->idx, sd,
-                                                    need_p32 ? P.f : nullptr, grid_view(ctx), kSeededBox,
-                                                    grid_budget(ctx), (int)ctx->nm, ctx->m4, ctx->canon_rowbuf,
-                                                    grid_policy ? &sd->far_acc : nullptr,
-                                                    sa_grid.far_box > 0 ? -1.0 : sa_grid.far_d2, ctx->amb_count + 2,
-                                                    ctx->st, iter_dbg, 0, cert, &rows_strands);
-                    LAUNCHCHK("nn_grid_iter (first)");
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 1], ctx->st));
-                    ws = SeedState{};
-                    ctx->seeds_valid = true;
-                    ctx->stats.last_filter = ICP_FILTER_GRID;
-                    ctx->stats.run_grid_searches += 1;
-                    if (enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
-                    ctx->kpos_valid = false;
-                    ctx->y_ready = true;
-                    ar_timed[slot] = false;
-                    if ((size_t)enqueued < ctx->digest_cap) {
-                        launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st,
-                                          digest_order);
-                        LAUNCHCHK("idx_digest");
-                    }
-                    TRY(canon_first());
-                    xf_pending = true;
-                    ++enqueued;
-                    if (enqueued == max_iter) {
-                        TRY(canon_transform(grid_policy ? sa_grid : SeedArgs{}));
-                        TRY(canon_end(enqueued - 1, false, -1));
-                    }
-                    continue;
-                }
-                // the grid's iterations as ONE launch: the pending transform, the seeded search
-                // of every point and the moments (nn_grid_iter_kernel)
-                const bool k1 = grid_iter_on() && xf_pending && ctx->seeds_valid && enqueued > 0 &&
-                                ctx->nn_mode == ICP_NN_CERTIFIED && ctx->nn_rule == ICP_NN_RULE_SQUARED &&
-                                (grid_c || ctx->nn_variant == ICP_NN_VARIANT_GRID) && ctx->g_pts32;
-                if (k1) {
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot], ctx->st));
-                    cert.valid = cert_prev ? 1 : 0;
-                    cert.skin = (cert_prev ? cert_skin : cert_skin1) / ctx->grid.inv_h;
-                    cert_prev = launch_nn_grid_iter((int)n, P.x, P.y, P.z, Y.x, Y.y, Y.z, ctx->idx, sd,
-                                                    need_p32 ? P.f : nullptr, grid_view(ctx), kSeededBox,
-                                                    grid_budget(ctx), (int)ctx->nm, ctx->m4, ctx->canon_rowbuf,
-                                                    grid_policy ? &sd->far_acc : nullptr,
-                                                    sa_grid.far_box > 0 ? -1.0 : sa_grid.far_d2, ctx->amb_count + 2,
-                                                    ctx->st, iter_dbg, 1, cert, &rows_strands);
-                    if (iter_dbg && iter_debug_each) { // (ICP_ITER_DEBUG=2: each launch's counts, synchronising)
-                        unsigned long long h[16];
-                        HIPCHK(hipStreamSynchronize(ctx->st));
-                        HIPCHK(hipMemcpy(h, iter_dbg, sizeof(h), hipMemcpyDeviceToHost));
-                        fprintf(stderr, "[iter2_debug] it %d tasks %llu walkers %llu batches %llu pair tests %llu (lane 0's)\n",
-                                enqueued, h[0], h[1], h[2], h[3]);
-                        HIPCHK(hipMemset(iter_dbg, 0, sizeof(h)));
-                    }
-                    LAUNCHCHK("nn_grid_iter");
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 1], ctx->st));
-                    if (!need_p32) ctx->p32_stale = true;
-                    ws = SeedState{}; // (no seed distances written: the next grid iteration computes its own)
-                    xf_pending = false;
-                    ctx->stats.last_filter = ICP_FILTER_GRID;
-                    ctx->stats.run_grid_searches += 1;
-                    if (enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
-                    ctx->kpos_valid = false;
-                    ctx->y_ready = true;
-                    ar_timed[slot] = false;
-                    if ((size_t)enqueued < ctx->digest_cap) {
-                        launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st,
-                                          digest_order);
-                        LAUNCHCHK("idx_digest");
-                    }
-                    ar_timed[slot] = timed && lag;
-                    TRY(canon_end(enqueued - 1, true, slot));
-                    xf_pending = true;
-                    ++enqueued;
-                    if (enqueued == max_iter) {
-                        TRY(canon_transform(grid_policy ? sa_grid : SeedArgs{}));
-                        TRY(canon_end(enqueued - 1, false, -1));
-                    }
-                    continue;
-                }
-                cert_prev = false; // (any other search: the certificate's state is stale)
-                if (xf_pending) { // the last Horn step's transform, in the form this search reads
-                    SeedArgs sa_t = grid_c ? sa_grid : sa;
-                    if (!grid_c) records_args(sa_t);
-                    TRY(canon_transform(sa_t));
-                }
-                const double *gs = ws.seedd && (grid_c || ctx->nn_variant == ICP_NN_VARIANT_GRID) ? sa.seedd : nullptr;
-                ctx->second_pass_items = grid_policy && q2_obs >= 0 ? std::max(256, 4 * q2_obs) : 0;
-                TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, timed ? ctx->iter_ev[5 * slot] : nullptr,
-                                    timed ? ctx->iter_ev[5 * slot + 1] : nullptr, false, &ws, &sd->done,
-                                    ctx->scene_slot, grid_c, gs));
-                if (ctx->stats.last_filter == ICP_FILTER_BUNDLE) ctx->stats.run_bundle_searches += 1;
-                else if (ctx->stats.last_filter == ICP_FILTER_GRID) ctx->stats.run_grid_searches += 1;
-                if (ctx->stats.last_filter == ICP_FILTER_GRID && enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
-                ctx->seeds_valid = true;
-                TRY(cpu_rule_fixup(ctx, P, n, &sd->done));
-                ar_timed[slot] = false;
-                if ((size_t)enqueued < ctx->digest_cap) {
-                    launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st,
-                                      digest_order);
-                    LAUNCHCHK("idx_digest");
-                }
-                if (enqueued == 0) { // the first moments in one pass around the first shifts, then the Horn step
-                    // the shift of y: the mean of a sample of these correspondences (all ranks'), where
-                    // run_init put the model's centre c -- matched points that are a small part of the
-                    // model, D from c, would otherwise cancel (D / sigma)^2 of the y moments' precision
-                    launch_first_shift_y_sample(ctx->idx, ctx->m4, Y.x, Y.y, Y.z, (int)n,
-                                                ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready,
-                                                ctx->sums + kSumYSample, lag ? nullptr : sd, ctx->sums + kSumScene, N,
-                                                ctx->st);
-                    LAUNCHCHK("first_shift_y_sample");
-                    if (lag) {
-                        TRY(allreduce(ctx, ctx->sums + kSumYSample, 4));
-                        launch_first_shifts(sd, ctx->sums + kSumYSample, ctx->sums + kSumScene, N, ctx->st);
-                        LAUNCHCHK("first_shifts");
-                    }
-                    launch_canon_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, ctx->canon_rowbuf,
-                                         ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
-                    LAUNCHCHK("canon_moments");
-                    TRY(canon_first());
-                } else {
-                    launch_canon_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, ctx->canon_rowbuf,
-                                         ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
-                    LAUNCHCHK("canon_moments");
-                    ar_timed[slot] = timed && lag;
-                    TRY(canon_end(enqueued - 1, true, slot));
-                }
-                xf_pending = true;
-                ++enqueued;
-                if (enqueued == max_iter) { // the last transform and its residual's error step
-                    TRY(canon_transform(grid_policy ? sa_grid : SeedArgs{}));
-                    TRY(canon_end(enqueued - 1, false, -1));
-                }
-                continue;
-            }
-            // the path of this search: on the last count the host has seen (the previous transform
-            // wrote for the path predicted when it was enqueued; a different decision here just
-            // rebuilds what this path reads, nn_search_begin), else as predicted (carried over,
-            // or the grid while the bundle images are still pending)
-            const bool grid_cur = grid_policy && (far_obs >= 0 ? far_obs <= far_thr : grid_next);
-            grid_next = grid_policy && (far_obs >= 0 ? far_obs <= far_thr : ctx->bundle_pending);
-            // (the search of an iteration queued behind the converged one returns at once)
-            // (the seed distances the last transform wrote -- of this run, or of the last one when
-            // carried over -- for a grid search)
-            const double *gseedd =
-                ws.seedd && (grid_cur || ctx->nn_variant == ICP_NN_VARIANT_GRID) ? sa.seedd : nullptr;
-            // (the second pass's grid: for four times the last queue seen, at least 256 queries)
-            ctx->second_pass_items = grid_policy && q2_obs >= 0 ? std::max(256, 4 * q2_obs) : 0;
-            TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, timed ? ctx->iter_ev[5 * slot] : nullptr,
-                                timed ? ctx->iter_ev[5 * slot + 1] : nullptr, false, &ws, &sd->done, ctx->scene_slot,
-                                grid_cur, gseedd)); // (run_init zeroed the counters)
-            if (ctx->stats.last_filter == ICP_FILTER_BUNDLE) ctx->stats.run_bundle_searches += 1;
-            else if (ctx->stats.last_filter == ICP_FILTER_GRID) ctx->stats.run_grid_searches += 1;
-            if (ctx->stats.last_filter == ICP_FILTER_GRID && enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
-            ctx->seeds_valid = true; // idx pairs every point of the resident scene
-            TRY(cpu_rule_fixup(ctx, P, n, &sd->done)); // (ICP_NN_RULE_CPU_SQRT only: host near ties)
-            ar_timed[slot] = false;
-            if ((size_t)enqueued < ctx->digest_cap) {
-                launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st,
-                                  digest_order);
-                LAUNCHCHK("idx_digest");
-            }
-            if (!lag && enqueued > 0 && n > 0 && n <= (size_t)kRedSingle) {
-                // small cloud, one rank: steps 2-6 in one workgroup, the same arithmetic in the
-                // same order as the separate launches below (launch latency dominates there)
-                const int sl = enqueued % kRing;
-                slot_ticket[sl] = ++ctx->flag_ticket;
-                launch_iteration_tail_small(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, P.f, ctx->sums,
-                                            N, ctx->c, ctx->amb_count, sd, threshold, max_iter, ctx->err_trace_dev,
-                                            ctx->d_flags + 4 * sl, slot_ticket[sl], ctx->d_iter_mirror,
-                                            ctx->d_trace, ctx->st);
-                LAUNCHCHK("iteration_tail_small");
-                ws = SeedState{}; // (it writes no seeds)
-                ++enqueued;
-                continue;
-            }
-            bool horn_fused = false; // (reduce_horn: the Horn step rode on the moments' fold)
-            // 2-3. centroids, centred cross-covariance and norms (gpu.cc:98-104, :142): the first
-            // iteration two-pass (the reference's order); later ones in one pass around the shifts
-            // the previous Horn step left (its transformed centroid, its correspondence centroid)
-            if (enqueued == 0) {
-                TRY(moments_phase(ctx, n));
-            } else if (fused_tail) {
-                // steps 2-6 in one launch of the same workgroups (bit-identical; see icp_iter.hip)
-                const int sl = enqueued % kRing;
-                slot_ticket[sl] = ++ctx->flag_ticket;
-                TailArgs ta{};
-                ta.idx = ctx->idx;
-                ta.m4 = ctx->m4;
-                ta.px = P.x;
-                ta.py = P.y;
-                ta.pz = P.z;
-                ta.n = (int)n;
-                ta.yx = Y.x;
-                ta.yy = Y.y;
-                ta.yz = Y.z;
-                ta.p32 = P.f;
-                ta.sa = sa;
-                ta.part17 = ctx->tail_part;
-                ta.part1 = ctx->tail_part + (size_t)18 * kTailMaxBlocks;
-                ta.sync = ctx->tail_sync;
-                ta.epoch_base = tail_epoch;
-                ta.h_abort = ctx->d_flags + 11;
-                ta.N = N;
-                ta.c0 = ctx->c[0];
-                ta.c1 = ctx->c[1];
-                ta.c2 = ctx->c[2];
-                ta.cnt = ctx->amb_count;
-                ta.s = sd;
-                ta.threshold = threshold;
-                ta.max_iter = max_iter;
-                ta.err_trace = ctx->err_trace_dev;
-                ta.hflag = ctx->d_flags + 4 * sl;
-                ta.ticket = slot_ticket[sl];
-                ta.h_state = ctx->d_iter_mirror;
-                ta.h_trace = ctx->d_trace;
-                static const bool split_err = getenv("ICP_TAIL_SPLIT_ERR") != nullptr; // (A/B)
-                ta.sums_out = split_err ? ctx->sums : nullptr;
-                { // tests: ICP_TAIL_TEST_ABORT=1 fails the tail's first barrier (the rerun path)
-                    const char *e = getenv("ICP_TAIL_TEST_ABORT");
-                    ta.test_abort = e && e[0] == '1';
-                }
-                launch_iteration_tail_grid(ta, tail_blocks, ctx->st);
-                LAUNCHCHK("iteration_tail_grid");
-                ws = SeedState{}; // (its transform: the f16 seeds and the seed distances, no records)
-                ws.seed16 = sa.seed16 ? 1 : 0;
-                ws.seedd = sa.seedd != nullptr;
-                if (split_err) TRY(enqueue_err_step(enqueued));
-                tail_epoch += 2;
-                ++enqueued;
-                continue;
-            } else {
-                StepFold mf;
-                if (fused_moments) { // (+ the fold, and on one rank the Horn step, in the last workgroup)
-                    mf.ticket = ctx->fold_ticket;
-                    mf.sums = ctx->sums;
-                    mf.step = !lag;
-                    mf.N = N;
-                    for (int a = 0; a < 3; ++a) mf.c[a] = ctx->c[a];
-                    mf.cnt = ctx->amb_count;
-                    mf.s = sd;
-                }
-                launch_shifted_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd,
-                                       red_target(ctx, n, ctx->sums), ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr,
-                                       ctx->m4kd, ctx->y_ready, mf);
-                if (fused_moments) {
-                    horn_fused = !lag; // (multi-rank: the all-reduce, then the lagged error + Horn step below)
-                } else if (!lag && red_blocks(n) > 1) { // the fold and the Horn step in one launch
-                    launch_reduce_horn(ctx->partials, red_blocks(n), ctx->sums, N, ctx->c, 1, ctx->amb_count, sd,
-                                       ctx->st);
-                    horn_fused = true;
-                } else if (err_pair) { // (+ the previous transform's residual, into sums[kSumErr])
-                    launch_reduce_pair(ctx->partials, ctx->err_part, red_blocks(n), ctx->sums, ctx->st);
-                } else {
-                    red_finish(ctx, n, 17, ctx->sums);
-                }
-                LAUNCHCHK("shifted_moments");
-                if (lag) { // + the previous iteration's residual (sums[kSumErr], local until now)
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 3], ctx->st));
-                    TRY(allreduce(ctx, ctx->sums, kNumSums));
-                    if (timed) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 4], ctx->st));
-                    ar_timed[slot] = timed;
-                    // (enqueued > 0 here: the Horn step is the shifted one)
-                    TRY(enqueue_err_step(enqueued - 1, nullptr, true));
-                    horn_fused = true;
-                }
-            }
-            // 4. Horn solve (gpu.cc:106-146) on the device
-            if (!horn_fused) launch_horn_step(ctx->sums, N, ctx->c, enqueued > 0, ctx->amb_count, sd, ctx->st);
-            // 5. apply + residual (gpu.cc:71-74): new_p <- sR new_p + t; e = sum ||Y - new_p||^2
-            SeedArgs sa_t = grid_next ? sa_grid : sa;
-            if (!grid_next) records_args(sa_t); // (a bundle search next: its slot records, when they can be)
-            ws = SeedState{};
-            ws.seedd = sa_t.seedd != nullptr; // (every form writes the seed distances)
-            ws.seed16 = !sa_t.seed16 ? 0 : sa_t.qop && sa_t.local_r >= 0.0 ? 2 : 1;
-            ws.records = sa_t.qop != nullptr;
-            ws.rec_local = sa_t.qop ? sa_t.local_r : -1.0;
-            StepFold ef;
-            const bool err_fused = fused_steps && !sa_t.qop; // (the slot-record form keeps its own launch)
-            if (err_fused && lag) { // (the fold only: the residual rides on the next all-reduce)
-                ef.ticket = ctx->fold_ticket + 1;
-                ef.sums = ctx->sums;
-                ef.step = false;
-            } else if (err_fused) { // (+ reduce_err_kernel's fold and error step, in the last workgroup)
-                const int sl = enqueued % kRing;
-                slot_ticket[sl] = ++ctx->flag_ticket;
-                ef.ticket = ctx->fold_ticket + 1;
-                ef.sums = ctx->sums;
-                ef.N = N;
-                ef.s = sd;
-                ef.threshold = threshold;
-                ef.max_iter = max_iter;
-                ef.err_trace = ctx->err_trace_dev;
-                ef.hflag = ctx->d_flags + 4 * sl;
-                ef.hticket = slot_ticket[sl];
-                ef.h_state = ctx->d_iter_mirror;
-                ef.h_trace = ctx->d_trace;
-            }
-            launch_transform_err_dev(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                     err_pair ? ctx->err_part : red_target(ctx, n, ctx->sums + kSumErr), sa_t,
-                                     ctx->st, ef);
-            if (!need_p32) ctx->p32_stale = true;
-            const bool fold_err = !lag && red_blocks(n) > 1; // (folded by the error step's launch)
-            if (!fold_err && !err_fused && !err_pair) red_finish(ctx, n, 1, ctx->sums + kSumErr);
-            LAUNCHCHK("transform_err");
-            // 6. err = (e + e) / np; stop after the iteration with err < threshold (gpu.cc:76-80)
-            if (!lag && !err_fused) TRY(enqueue_err_step(enqueued, fold_err ? ctx->partials : nullptr));
-            ++enqueued;
-            if (lag && enqueued == max_iter) { // the last residual has no next iteration to ride on
-                if (err_pair) launch_reduce(ctx->err_part, red_blocks(n), 1, ctx->sums + kSumErr, ctx->st);
-                TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
-                TRY(enqueue_err_step(enqueued - 1));
-            }
-            continue;
-        }
-        const int slot = waited % kRing;
-        const int wr = wait_flag(ctx, ctx->h_flags + 4 * slot + 2, slot_ticket[slot]);
-        if (wr != ICP_OK) {
-            if (fused_tail && __atomic_load_n(ctx->h_flags + 11, __ATOMIC_ACQUIRE) != 0) break; // (rerun below)
-            return wr;
-        }
-        ++waited;
-        if (grid_policy) { // (mirrored by the error step of that iteration)
-            far_obs = ctx->h_iter->far_acc;
-            if (waited - 1 < (int)fold_far.size()) fold_far[waited - 1] = far_obs;
-            q2_obs = ctx->h_iter->queued2;
-            static const bool dbg = getenv("ICP_DEBUG_POLICY") != nullptr;
-            if (dbg) fprintf(stderr, "[policy] waited %d far %d thr %d next_grid %d\n", waited, far_obs, far_thr, (int)grid_next);
-        }
-        const int done = ctx->h_flags[4 * slot], iters = ctx->h_flags[4 * slot + 1];
-        report_progress(ctx, iters); // (the iterations recorded so far, as they end)
-        if (iters > recorded) { // this iteration counted: its NN kernel time (if timed)
-            float ms = 0.f;
-            if (n && (waited - 1) % timing_stride == timing_phase && (waited - 1 > 0 || timing_stride == 1)) {
-                // (an empty shard records no events)
-                if (hipEventElapsedTime(&ms, ctx->iter_ev[5 * slot], ctx->iter_ev[5 * slot + 1]) == hipSuccess) {
-                    ctx->stats.nn_ms += ms;
-                    ctx->stats.nn_launches += 1;
-                } else {
-                    (void)hipGetLastError(); // a failed query must not surface at the next launch check
-                }
-            }
-            if (ar_timed[slot]) { // the all-reduce rode on this slot's iteration
-                if (hipEventElapsedTime(&ms, ctx->iter_ev[5 * slot + 3], ctx->iter_ev[5 * slot + 4]) == hipSuccess) {
-                    ctx->stats.allreduce_ms += ms;
-                    ctx->stats.allreduce_calls += 1;
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-            ctx->stats.nn_pairs += (long long)n * (long long)ctx->nm;
-            recorded = iters;
-        }
-        stop = done != 0;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the iterations queued behind the last one drain)
-    if (fused_tail && __atomic_load_n(ctx->h_flags + 11, __ATOMIC_ACQUIRE) != 0) {
-        const char *bk = ctx->tail_backup;
-        HIPCHK(hipMemcpyAsync(P.x, bk, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(P.y, bk + n * 8, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(P.z, bk + n * 16, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->st));
-        if (P.f) HIPCHK(hipMemcpyAsync(P.f, bk + n * 24, n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->st));
-        if (seeds_at_start) HIPCHK(hipMemcpyAsync(ctx->idx, bk + n * 40, n * sizeof(int), hipMemcpyDeviceToDevice, ctx->st));
-        HIPCHK(hipStreamSynchronize(ctx->st));
-        ctx->seeds_valid = seeds_at_start;
-        ctx->seedd_valid = false;
-        return kTailAborted;
-    }
-    if (iter_dbg) {
-        unsigned long long h[16];
-        HIPCHK(hipMemcpy(h, iter_dbg, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[iter_debug] tasks %llu staged %llu pts %llu big %llu flushes %llu rows_over %llu pts_over %llu "
-                        "| wave-us A %.1f BC %.1f D %.1f E %.1f FG %.1f\n",
-                h[0], h[1], h[2], h[3], h[4], h[10], h[11], h[5] * 0.01, h[6] * 0.01, h[7] * 0.01, h[8] * 0.01,
-                h[9] * 0.01);
-        fprintf(stderr, "[iter2_debug] (nn_grid_iter2_kernel, an ICP_ITER2_DBG build) tasks %llu walkers %llu batches %llu "
-                        "pair tests %llu (lane 0's)\n",
-                h[0], h[1], h[2], h[3]);
-    }
-    // (every transform of a policy run wrote the seed distances, whatever its form; the next run
-    // may start from them)
-    // (cert_counts: read with the stats, or folded into them when a run of another size starts)
-    ctx->seedd_valid = grid_policy && ws.seedd;
-    ctx->last_far = far_obs;
-    ctx->last_q2 = q2_obs;
-    ctx->second_pass_items = 0;
-    return finish_run(ctx, threshold, err_trace, res, wall0);
-}
-
-// icp_run with the max-correspondence-distance gate on (icp_set_max_distance; kernels in
-// icp_gated.hip).  run_loop has prepared the loop state, the mapped mirrors and the flag ring.
-// Per iteration: the search as the launch loop's generic path runs it (seeded by the previous
-// correspondences, nothing carried from a transform), the gated moments (gate, mask, 18 sums), the
-// fold and the gated Horn step, the transform of every point with the kept points' residual, the
-// fold and the error step with N = K.  With ranks or a communicator the 18 sums and the residual
-// are each all-reduced before their step (two all-reduces an iteration; the error test is not
-// lagged).  The scene keeps the order it is in (file or slot); on one rank the host does not
-// synchronise inside an iteration.
-static int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
-                     std::chrono::steady_clock::time_point wall0)
-{
-    if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
-    const size_t n = ctx->scene.n;
-    DevCloud &P = ctx->scene, &Y = ctx->Y;
-    constexpr int kAhead = 1, kRing = 4;
-    const double D = ctx->gate_dmax * ctx->gate_dmax; // (fp64, once)
-    const bool ranks = lag_run(ctx);
-    const int nb = red_blocks(n);
-    TRY(grow(ctx, &ctx->gate_mask, &ctx->gate_mask_cap, (n + 63) / 64));
-    TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
-    TRY(grow(ctx, &ctx->gate_part, &ctx->gate_part_cap, (size_t)kRedMaxBlocksCap * kGateSums));
-    if (!ctx->gate_state) HIPCHK(hipMalloc((void **)&ctx->gate_state, sizeof(GateState)));
-    if (!ctx->h_gate) {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_gate, sizeof(GateState), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_gate_mirror, ctx->h_gate, 0));
-    }
-    if (ctx->ktrace_cap < (size_t)std::max(max_iter, 1)) { // (the previous run ended with a sync)
-        if (ctx->h_ktrace) HIPCHK(hipHostFree(ctx->h_ktrace));
-        ctx->h_ktrace = nullptr;
-        ctx->ktrace_cap = 0;
-        const size_t cap = (size_t)std::max(max_iter, 64);
-        HIPCHK(hipHostMalloc((void **)&ctx->h_ktrace, sizeof(long long) * cap, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_ktrace, ctx->h_ktrace, 0));
-        ctx->ktrace_cap = cap;
-    }
-    std::memset(ctx->h_gate, 0, sizeof(GateState));
-    HIPCHK(hipMemsetAsync(ctx->gate_state, 0, sizeof(GateState), ctx->st));
-    IterState *sd = ctx->iter_state;
-    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first iteration's pre-pass sums around the model's centre)
-    if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
-    const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
-    ctx->stats.run_path_bits = 0;
-    int slot_ticket[kRing] = {};
-    int enqueued = 0, waited = 0, recorded = 0;
-    bool stop = false;
-    while (!stop && waited < max_iter) {
-        if (enqueued < max_iter && enqueued - waited <= kAhead) {
-            // 1. correspondences (a search queued behind the iteration that froze the run returns at once)
-            const SeedState ws;
-            ctx->second_pass_items = 0;
-            TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, nullptr, nullptr, false, &ws, &sd->done, ctx->scene_slot,
-                                false, nullptr));
-            if (ctx->stats.last_filter == ICP_FILTER_BUNDLE) ctx->stats.run_bundle_searches += 1;
-            else if (ctx->stats.last_filter == ICP_FILTER_GRID) ctx->stats.run_grid_searches += 1;
-            if (ctx->stats.last_filter == ICP_FILTER_GRID && enqueued < 64) ctx->stats.run_path_bits |= 1ull << enqueued;
-            ctx->seeds_valid = true;
-            TRY(cpu_rule_fixup(ctx, P, n, &sd->done));
-            if ((size_t)enqueued < ctx->digest_cap) {
-                launch_idx_digest(ctx->idx, (int)n, &sd->done, ctx->digest + 3 * (size_t)enqueued, ctx->st, digest_order);
-                LAUNCHCHK("idx_digest");
-            }
-            // the first iteration's shifts: a pre-pass of the same moments around c gives the kept
-            // pairs' centroids (all ranks'), and the pass below sums around those -- around c a scan
-            // D from the model's centre cancels (D / sigma)^2 of the moments' precision.  Later
-            // iterations get their shifts from the Horn step before them.
-            const bool pre_pass = enqueued == 0;
-            if (pre_pass) {
-                launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
-                                     ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
-                                     ctx->y_ready);
-                launch_gated_horn(ctx->gate_part, nb, ctx->sums, false, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st); // (the fold alone)
-                LAUNCHCHK("gated_moments (first shifts)");
-                if (ranks) TRY(allreduce(ctx, ctx->sums, kGateSums));
-                launch_gated_first_shift(sd, ctx->sums, ctx->st);
-                LAUNCHCHK("gated_first_shift");
-            }
-            // 2-4. the gate, the kept pairs' moments and count, the Horn step with N = K
-            // (after the pre-pass y = m[idx] is stored: the pass streams it)
-            launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
-                                 ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
-                                 ctx->y_ready || pre_pass);
-            launch_gated_horn(ctx->gate_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                              ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
-            LAUNCHCHK("gated_moments");
-            if (ranks) {
-                TRY(allreduce(ctx, ctx->sums, kGateSums));
-                launch_gated_horn(nullptr, 0, ctx->sums, true, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
-                LAUNCHCHK("gated_horn");
-            }
-            // 5-6. every point moves; the kept points' residual; err = (e + e) / K
-            launch_gated_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                   ctx->gate_mask, ctx->partials, ctx->st);
-            if (!need_p32) ctx->p32_stale = true;
-            const int sl = enqueued % kRing;
-            slot_ticket[sl] = ++ctx->flag_ticket;
-            launch_gated_err(ctx->partials, nb, ctx->sums, !ranks, threshold, max_iter, ctx->err_trace_dev, sd,
-                             ctx->gate_state, ctx->d_ktrace, ctx->d_flags + 4 * sl, slot_ticket[sl], ctx->d_iter_mirror,
-                             ctx->d_trace, ctx->st);
-            LAUNCHCHK("gated_transform");
-            if (ranks) {
-                TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
-                launch_gated_err(nullptr, 0, ctx->sums, true, threshold, max_iter, ctx->err_trace_dev, sd, ctx->gate_state,
-                                 ctx->d_ktrace, ctx->d_flags + 4 * sl, slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace,
-                                 ctx->st);
-                LAUNCHCHK("gated_err");
-            }
-            ++enqueued;
-            continue;
-        }
-        const int slot = waited % kRing;
-        TRY(wait_flag(ctx, ctx->h_flags + 4 * slot + 2, slot_ticket[slot]));
-        ++waited;
-        const int done = ctx->h_flags[4 * slot], iters = ctx->h_flags[4 * slot + 1];
-        report_progress(ctx, iters);
-        if (iters > recorded) {
-            ctx->stats.nn_pairs += (long long)n * (long long)ctx->nm;
-            recorded = iters;
-        }
-        stop = done != 0;
-    }
-    // the last gate evaluated, as flags in the caller's point order (icp_get_inliers)
-    if (enqueued > 0) {
-        launch_gated_unpack(ctx->gate_mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
-        LAUNCHCHK("gated_unpack");
-    }
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the iteration queued behind the last one drains)
-    // nothing of a transform is carried to the next run: it starts from the correspondences alone
-    ctx->seedd_valid = false;
-    ctx->last_far = -1;
-    ctx->last_q2 = -1;
-    ctx->second_pass_items = 0;
-    if (enqueued > 0) {
-        ctx->gate_have = true;
-        ctx->gate_iters = ctx->h_iter->iter;
-    }
-    const GateState hg = *ctx->h_gate;
-    TRY(finish_run(ctx, threshold, err_trace, res, wall0));
-    if (hg.status == kGateTooFew)
-        return fail(ctx, ICP_E_TOO_FEW_POINTS,
-                    "icp_run: iteration " + std::to_string(hg.fail_iter) + " kept K = " + std::to_string(hg.K) +
-                        " pairs within the max correspondence distance; need at least 4");
-    return ICP_OK;
-}
-
-// The run's result from the mapped host mirror of the last recorded iteration (both loops).
-static int finish_run(icp_ctx *ctx, double threshold, double *err_trace, icp_result *res,
-                      std::chrono::steady_clock::time_point wall0)
-{
-    const IterState &hs = *ctx->h_iter; // mirrored by the last recorded err step
-    report_progress(ctx, hs.iter); // (the rest: a one-launch run reports here)
-    icp_result r{};
-    r.iterations = hs.iter;
-    r.s = 1.0; // GPU::ICP ctor state (gpu.hh:53-55) when no iteration ran
-    r.R[0] = r.R[4] = r.R[8] = 1.0;
-    if (hs.iter > 0) {
-        const double *tr = ctx->h_trace;
-        if (err_trace) std::memcpy(err_trace, tr, sizeof(double) * (size_t)hs.iter);
-        r.err = tr[hs.iter - 1];
-        r.converged = r.err < threshold ? 1 : 0;
-        r.s = hs.srt[0];
-        for (int k = 0; k < 9; ++k) r.R[k] = hs.srt[1 + k];
-        for (int k = 0; k < 3; ++k) r.t[k] = hs.srt[10 + k];
-    }
-    ctx->stats.iterations += hs.iter;
-    if (ctx->nn_mode == ICP_NN_CERTIFIED) {
-        ctx->stats.ambiguous += hs.nn_counts[0];
-        ctx->stats.grid_fallback += hs.nn_counts[1];
-        ctx->stats.level1_queued += hs.nn_counts[2];
-        ctx->stats.level1_unrecovered += hs.nn_counts[3];
-    }
-    ctx->stats.iter_ms +=
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    if (res) *res = r;
-    return ICP_OK;
 }
 
 // ---- per-operation surface ------------------------------------------------------------

@@ -89,7 +89,7 @@ def test_two_rank_gloo_matches_unsharded(oracle):
 
 
 def _rank_main_one_allreduce(rank, world, port, q, max_iter):
-    """The engine's own multi-rank protocol (icp_engine.hip icp_run, lag mode): the first
+    """The engine's own multi-rank protocol (icp_run.hip icp_run, lag mode): the first
     iteration's two-pass sums (6 + 11 doubles); every later iteration ONE all-reduce of 18
     doubles -- the 17 one-pass moments around the shifts the previous Horn step left
     (cp = sR mu_p + t, cy = mu_y) plus the previous iteration's local residual, whose error

@@ -1,5 +1,5 @@
 """The canonical schedule and the fused grid iteration (icp_canon.h, icp_canon.hip,
-icp_grid.hip nn_grid_iter_kernel, icp_engine.hip run_loop).
+icp_grid.hip nn_grid_iter_kernel, icp_run.hip enqueue_canon).
 
 The loop is src/GPU/gpu.cc:52-83: per iteration the exact NN of every point, the alignment
 (gpu.cc:95-151) and the transform with its residual.  Every path that produces an iteration's
@@ -112,7 +112,7 @@ def test_canonical_matches_round4_schedule(settings, case):
 
 def test_far_scene_first_iteration_matches_two_pass(settings):
     """A scene 1e3 spreads from the model: the canonical first iteration sums its moments around the
-    scene's own centroid (all ranks' sum, icp_engine.hip run_loop), so its (s, R, t) agree with the
+    scene's own centroid (all ranks' sum, icp_run.hip run_setup_canon), so its (s, R, t) agree with the
     reference's two passes (gpu.cc:98-104, the round-4 schedule) to rounding."""
     a, b = settings["fused"], settings["round4"]
     np.testing.assert_allclose(a["far_errs"], b["far_errs"], rtol=1e-12)

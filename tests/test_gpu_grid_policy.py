@@ -1,4 +1,4 @@
-"""icp_run's search policy at the bundle filter's sizes (icp_engine.hip run_loop) and the seeded
+"""icp_run's search policy at the bundle filter's sizes (icp_run.hip run_setup_policy) and the seeded
 grid search it switches to (grid_seeded_search: the per-query walk of boxes up to 125 cells, a
 whole wave per query for bigger ones, fp64 brute force over the cell budget).
 

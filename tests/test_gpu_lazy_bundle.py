@@ -1,5 +1,5 @@
 """The bundle filter's images built at their first use, and what icp_run's transforms hand to the
-next search (icp_engine.hip: build_bundle / ensure_bundle, run_loop's SeedState and records_args;
+next search (icp_engine.hip: build_bundle / ensure_bundle; icp_run.hip: SeedState and records_args;
 icp_step.hip: transform_err_kernel).
 
 The loop is src/GPU/gpu.cc:52-83 (find_corresponding_opti).  Every search returns the exact fp64
