@@ -281,10 +281,117 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_kernel(const double *
 // order, the wave trees, the 8 waves' pairwise tree: the same bits).  MODE 1: the last workgroup
 // to finish (a relaxed ticket after write-through column sums, icp_fold.h's hand-off) runs the error step and
 // the Horn step on the 18 sums.  MODE 0: the sums only (several ranks: the all-reduce follows).
+//
+// Workgroups 18 .. 25 (launched only with a table to build, IterOrder::order): workgroup 18 + k
+// builds XCD k's part of the next fused launch's dispatch order (icp_kernels.h, IterOrder) from
+// the walker counts the launch before this fold left in walk_last.  They take no part in the
+// ticket; the kernel boundary orders their stores before the next launch's loads.
+//
+// XCD k's blocks are b = 8 i + k, slot i taking strand xcd_row(b, S, L) by default.  The slots
+// are cut into segments (form 1, 2 and L > 0: the runs of L; else the XCD's whole list), each
+// segment sorted by one wave: a stable counting sort over the 65 counts, keys 64 - count
+// (heavy-first), 64 slots a pass -- a slot's place is its key's base + the lanes before it with
+// the same key (7 ballots, one a key bit).  Form 2 then places the segments by their totals
+// (stable too).  Every slot is written once whatever walk_last holds (counts are clamped to
+// 0 .. 64), so the table is always a permutation of the XCD's own strands; the blocks past
+// xcd_row's bijection keep their index.
+constexpr int kOrderSlotsMax = kCanonStrandsMax / 8 + 1; // (an XCD's blocks)
+constexpr int kOrderKeys = 65;
+
+__device__ __forceinline__ void order_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ void iter_order_build(const IterOrder &o, int k)
+{
+    constexpr int NW = kFoldThreads / 64;
+    __shared__ unsigned char s_key[kOrderSlotsMax];
+    __shared__ int s_base[NW][kOrderKeys + 1];
+    __shared__ int s_tot[kOrderSlotsMax];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int S = o.S, L = o.L, form = o.form & 3;
+    const bool light = (o.form & 4) != 0;
+    const int nbij = L > 0 ? S / (8 * L) * (8 * L) : S;    // (blocks of xcd_row's bijection)
+    const int nslots = L > 0 ? nbij / 8 : (S - k + 7) / 8; // (this XCD's)
+    if (S > kCanonStrandsMax || nslots > kOrderSlotsMax) return; // (never: S = canon_strands(n))
+    for (int b = nbij + k + 8 * (int)threadIdx.x; b < S; b += 8 * kFoldThreads) o.order[b] = b;
+    if (nslots <= 0) return;
+    const int seglen = L > 0 && form != 3 ? L : nslots, nseg = nslots / seglen;
+    for (int i = threadIdx.x; i < nslots; i += kFoldThreads) {
+        const int c = min(max(o.walk_last[xcd_row(8 * i + k, S, L)], 0), kOrderKeys - 1);
+        s_key[i] = (unsigned char)(light ? c : kOrderKeys - 1 - c);
+    }
+    __syncthreads();
+    if (form == 2) { // (the segments' totals, as sort keys: ascending = first)
+        for (int seg = wave; seg < nseg; seg += NW) {
+            int t = 0;
+            for (int i = lane; i < seglen; i += 64) t += s_key[seg * seglen + i];
+            for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d, 64);
+            if (lane == 0) s_tot[seg] = t;
+        }
+        __syncthreads();
+    }
+    for (int seg = wave; seg < nseg; seg += NW) {
+        int place = seg;
+        if (form == 2) { // (the segments before this one: a smaller total, or the same and an earlier run)
+            const int mine = s_tot[seg];
+            int cnt = 0;
+            for (int j = lane; j < nseg; j += 64) {
+                const int tj = s_tot[j];
+                cnt += tj < mine || (tj == mine && j < seg) ? 1 : 0;
+            }
+            for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+            place = cnt;
+        }
+        const int src = seg * seglen, dst = place * seglen;
+        int *const base = s_base[wave];
+        base[lane] = 0;
+        if (lane < kOrderKeys + 1 - 64) base[64 + lane] = 0;
+        order_wave_sync();
+        for (int i0 = 0; i0 < seglen; i0 += 64)
+            if (i0 + lane < seglen) atomicAdd(&base[s_key[src + i0 + lane]], 1);
+        order_wave_sync();
+        int incl = base[lane]; // (keys 0 .. 63: key 64's base is their sum)
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        order_wave_sync();
+        base[lane + 1] = incl;
+        if (lane == 0) base[0] = 0;
+        order_wave_sync();
+        for (int i0 = 0; i0 < seglen; i0 += 64) {
+            const int i = i0 + lane;
+            const bool act = i < seglen;
+            const int key = act ? (int)s_key[src + i] : 127; // (127: no slot's key)
+            unsigned long long same = ~0ull;
+#pragma unroll
+            for (int bit = 0; bit < 7; ++bit) {
+                const unsigned long long bal = __ballot((key >> bit) & 1);
+                same &= (key >> bit) & 1 ? bal : ~bal;
+            }
+            const int before = __popcll(same & ((1ull << lane) - 1ull));
+            const int pos = act ? base[key] + before : 0;
+            order_wave_sync();
+            if (act && before == 0) base[key] = pos + __popcll(same);
+            order_wave_sync();
+            if (act) o.order[8 * (dst + pos) + k] = xcd_row(8 * (src + i) + k, S, L);
+        }
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const double *__restrict__ rows, int R,
-                                                                       double *__restrict__ sums, CanonStep cs, int S)
+                                                                       double *__restrict__ sums, CanonStep cs, int S,
+                                                                       IterOrder ord)
 {
+    if (blockIdx.x >= kCanonCols) { // (uniform: the whole workgroup)
+        iter_order_build(ord, (int)blockIdx.x - kCanonCols);
+        return;
+    }
     __shared__ double sh[kFoldThreads / 64];
     __shared__ double s_sum[kCanonCols];
     __shared__ int s_last;
@@ -364,8 +471,8 @@ void launch_canon_transform(double *px, double *py, double *pz, const double *yx
         canon_transform_kernel<false><<<R, kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, rows, sa);
 }
 
-void launch_canon_fold(const double *rows, int n, double *sums, int mode, const CanonStep &cs, hipStream_t st,
-                       int strands)
+bool launch_canon_fold(const double *rows, int n, double *sums, int mode, const CanonStep &cs, hipStream_t st,
+                       int strands, const IterOrder &ord)
 {
     const int R = canon_rows((size_t)(n > 0 ? n : 1));
     // (ICP_FOLD_ONE=1: the 18 columns in one workgroup, A/B)
@@ -374,10 +481,13 @@ void launch_canon_fold(const double *rows, int n, double *sums, int mode, const 
         return e && atoi(e) == 1;
     }();
     if (!one && cs.fold_ticket && (mode == 0 || mode == 1 || mode == 4)) {
-        if (mode == 0) canon_fold_cols_kernel<0><<<kCanonCols, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands);
-        else if (mode == 1) canon_fold_cols_kernel<1><<<kCanonCols, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands);
-        else canon_fold_cols_kernel<4><<<kCanonCols, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands);
-        return;
+        // (+ 8 workgroups, one an XCD, when the next fused launch's dispatch order is to be built)
+        const bool build = ord.order && ord.walk_last && ord.form != 0 && ord.S > 0 && ord.S <= kCanonStrandsMax;
+        const int nb = kCanonCols + (build ? 8 : 0);
+        if (mode == 0) canon_fold_cols_kernel<0><<<nb, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands, ord);
+        else if (mode == 1) canon_fold_cols_kernel<1><<<nb, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands, ord);
+        else canon_fold_cols_kernel<4><<<nb, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands, ord);
+        return build;
     }
     switch (mode) {
     case 0: canon_fold_kernel<0, kCanonCols, 0><<<1, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands); break;
@@ -386,6 +496,7 @@ void launch_canon_fold(const double *rows, int n, double *sums, int mode, const 
     case 2: canon_fold_kernel<kSumErr, 1, 2><<<1, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands); break;
     default: canon_fold_kernel<kSumErr, 1, 0><<<1, kFoldThreads, 0, st>>>(rows, R, sums, cs, strands); break;
     }
+    return false;
 }
 
 } // namespace icp

@@ -223,7 +223,9 @@ struct icp_ctx {
     hipEvent_t order_ev = nullptr; // icp_set_*_device_stream: the producer stream's point to wait for
     int4 *cert_state = nullptr;
     size_t cert_state_cap = 0;
-    unsigned long long *cert_counts = nullptr; // (2 per strand: certified, walked -- CertArgs::counts)
+    unsigned long long *cert_counts = nullptr; // (2 per strand: certified, walked -- CertArgs::counts;
+                                               //  then, in the same allocation, a strand's last walker count and the
+                                               //  dispatch order built from it, an int each: CertArgs::walk_last, IterOrder)
     size_t cert_counts_cap = 0;
     int cert_counts_rows = 0; // (strands the runs since the last fold counted into cert_counts, not yet in stats)
     char *tail_backup = nullptr;              // icp_run with the fused tail: the starting scene / idx
@@ -370,6 +372,11 @@ struct SeedState {
 //   cert_two           ICP_CERT_TWO            1        [0] == '0': 0          0: the certificate's one-point form
 //   cert_skin          ICP_CERT_SKIN           0.25     atof in [0, 4]         the walk's extra radius in grid cells
 //   cert_skin1         ICP_CERT_SKIN1          = skin   atof in [0, 4]         the skin of a launch with no state to read (A/B)
+//   iter2_order        ICP_ITER2_ORDER         2        atoi in 1 .. 7 but 4,  the fused iteration's dispatch order (IterOrder,
+//                                                       else 0                 icp_kernels.h): 0 xcd_row; 1 / 2 / 3 the heavy
+//                                                                              strands first (2: runs, then strands -- C4 10,676
+//                                                                              against 10,379 it/s; 1 level, 3 -9.8%,
+//                                                                              profiles/r10/ab_forms.txt); 5 / 6 / 7 light-first (tests)
 //   iter_debug         ICP_ITER_DEBUG          0        set: 1; atoi == 2: 2   nn_grid_iter_kernel's phase clocks and counts, summed
 //                                                                              over the run, to stderr; 2: each launch's (synchronises)
 //   tail_split_err     ICP_TAIL_SPLIT_ERR      off      set                    the fused tail's error step as its own launch (A/B)
@@ -391,6 +398,7 @@ struct RunKnobs {
     bool canon, cert;
     int cert_two;
     double cert_skin, cert_skin1;
+    int iter2_order;
     int iter_debug;
     bool tail_split_err, debug_policy;
 };

@@ -602,20 +602,7 @@ template <int G> __device__ __forceinline__ void group_lex_min_pos(double &best,
     }
 }
 
-// Block b of nb -> row, so that an XCD's blocks (b = k, k + 8, ...: k = b % 8) take runs of L
-// consecutive rows: XCD k's i th block takes row (8 (i / L) + k) L + i % L, a bijection of the
-// first 8 L floor(nb / 8 L) blocks; the rest keep their own index.  L < 0: one run per XCD,
-// [k q + min(k, e), (k + 1) q + min(k + 1, e)) (q = nb / 8, e = nb % 8); L = 0: the identity.
-__device__ __forceinline__ int xcd_row(int b, int nb, int L)
-{
-    const int k = b & 7, i = b >> 3;
-    if (L < 0) {
-        const int q = nb >> 3, e = nb & 7;
-        return k * q + min(k, e) + i;
-    }
-    if (L == 0 || b >= nb / (8 * L) * (8 * L)) return b;
-    return ((i / L) * 8 + k) * L + i % L;
-}
+// (block -> row: xcd_row, icp_kernels.h)
 
 // The seeded search of every query of a scene in slot order (icp_run's grid iterations,
 // grid_seeded_search): each query's box comes from its seed distance seedd[t] -- the last
@@ -1563,13 +1550,30 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
     __shared__ double s_tile[NW][CH * kIter2Tile];
     const Iter2Args &T = iter2_args(); // (the launch's shape; the phases read their own)
     const IterState *const st = T.st;
-    if (iter2_state(st).done) return; // a frozen (converged) ICP iteration: nothing moves, nothing is searched
+    // (ICP_ITER2_DBG: the wave's entry and exit times, 100 MHz -- two reads a wave, none in the phases)
+    const unsigned long long dbg_t0 = kDbg ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    // The dispatch order (IterOrder): this block's strand from the table, one scalar load issued
+    // with `done`'s under the same wait -- a dependent round trip here would be paid by each of a
+    // CU's generations of waves.  No table: the same load from an address that is always valid,
+    // its value unused.
+    const int *const ord = NWG == 1 ? T.ca.order : nullptr;
+    auto *oaddr = ord ? (const ICP_CONST_AS int *)ord + blockIdx.x : (const ICP_CONST_AS int *)&st->done;
+    auto *daddr = (const ICP_CONST_AS int *)&st->done;
+    int s_ord, done;
+    // (both loads, then the one wait, spelled out: left to the compiler, the table's load sinks
+    // below the test of `done` and waits a second time)
+    asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(done), "=&s"(s_ord)
+                 : "s"(daddr), "s"(oaddr)
+                 : "memory");
+    if (done) return; // a frozen (converged) ICP iteration: nothing moves, nothing is searched
     const int n = T.n, xcd_l = T.xcd_l, xform = T.xform;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, u = lane / QL, sub = lane % QL;
     const int C = canon_chunks((size_t)n), S = canon_strands((size_t)n), R = canon_rows((size_t)n);
     // (as nn_grid_iter_kernel: runs of rows an XCD -- for one-strand workgroups runs of 4 L strands)
     const int s = NWG == 4 ? xcd_row((int)blockIdx.x, R, xcd_l) * 4 + wave
-                           : xcd_row((int)blockIdx.x, S, xcd_l > 0 ? 4 * xcd_l : xcd_l);
+                : ord ? ((unsigned)s_ord < (unsigned)S ? s_ord : S) // (S: no strand -- never with a table the fold built)
+                      : xcd_row((int)blockIdx.x, S, xcd_l > 0 ? 4 * xcd_l : xcd_l);
     const int wr = s >> 2;
     double *const tile = s_tile[wave];
     double *const slots = tile;                            // (phases A-D) 32 CH slots of kIter2Slot doubles
@@ -2091,7 +2095,9 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
     }
     const Iter2Args &E = iter2_args();
     unsigned long long *const dbg = E.dbg;
-    if (kDbg && dbg && lane == 0)
+    // (one-strand workgroups: the counts go into the wave's record below -- four atomics a wave on
+    // four addresses, 65,536 a launch at C4, serialise and stretch the launch tenfold)
+    if (kDbg && dbg && lane == 0 && NWG != 1)
         for (int f = 0; f < 4; ++f)
             if (dcnt[f]) atomicAdd(dbg + f, dcnt[f]);
     if constexpr (NWG == 4) { // the workgroup's four strands -> its row (column k from lane k of each wave)
@@ -2117,6 +2123,16 @@ __global__ __launch_bounds__(64 * NWG) __attribute__((amdgpu_waves_per_eu(ICP_IT
         s_cnt[1][wave] = nbig;
         s_cnt[2][wave] = ncert;
         s_cnt[3][wave] = nwalk;
+        // this launch's own walker count of the strand: the next launch's dispatch order (IterOrder)
+        if (NWG == 1 && E.ca.walk_last && s < S) E.ca.walk_last[s] = nwalk;
+        if (kDbg && dbg && NWG == 1) { // (the wave's record: entry, exit, strand / XCD / walkers, lane 0's counts)
+            unsigned long long *const rec = dbg + 16 + 4 * (size_t)blockIdx.x;
+            rec[0] = dbg_t0;
+            rec[1] = __builtin_amdgcn_s_memrealtime();
+            rec[2] = (unsigned long long)(unsigned)s << 32 | (unsigned long long)(blockIdx.x & 7) << 16 |
+                     (unsigned long long)(nwalk & 0xffff);
+            rec[3] = (dcnt[0] & 0xffffull) << 48 | (dcnt[2] & 0xffffull) << 32 | (dcnt[3] & 0xffffffffull);
+        }
     }
     __syncthreads();
     if (threadIdx.x < 4) {
@@ -2140,6 +2156,22 @@ bool iter2_addr32(int n, int nm, const GridView &gv)
 }
 
 } // namespace
+
+// the runs of rows an XCD takes in the fused iteration's launch of n points (see there)
+static int iter_xcd_l(int n)
+{
+    static const int xcd_env = [] {
+        const char *e = getenv("ICP_ITER_XCD_L");
+        return e ? atoi(e) : -2;
+    }();
+    return xcd_env != -2 ? xcd_env : (canon_chunks((size_t)n) >= 8192 ? 32 : -1);
+}
+
+int nn_grid_iter_strand_run(int n)
+{
+    const int xcd_l = iter_xcd_l(n);
+    return xcd_l > 0 ? 4 * xcd_l : xcd_l; // (as nn_grid_iter2_kernel's one-strand workgroups read it)
+}
 
 bool launch_nn_grid_iter(int n, double *px, double *py, double *pz, double *yx, double *yy, double *yz, int *idx,
                          const IterState *st_dev, float4 *p32, const GridView &gv, int box, int budget, int nm,
@@ -2167,11 +2199,7 @@ bool launch_nn_grid_iter(int n, double *px, double *py, double *pz, double *yx, 
     // 0.085 / 0.061 against 0.100 / 0.064 ms an iteration, r05as), one run an XCD below (the W = 8
     // shard: 0.048 against 0.050 ms for runs of 32 and 0.053 round-robin).  ICP_ITER_XCD_L
     // overrides (-1 one run, 0 round-robin).
-    static const int xcd_env = [] {
-        const char *e = getenv("ICP_ITER_XCD_L");
-        return e ? atoi(e) : -2;
-    }();
-    const int xcd_l = xcd_env != -2 ? xcd_env : (canon_chunks((size_t)n) >= 8192 ? 32 : -1);
+    const int xcd_l = iter_xcd_l(n);
     // ICP_ITER_V2=0: the two-lane kernel of round 5 (every query walks; A/B) -- also the form of
     // ICP_ITER_STAGE, ICP_ITER_WIDE and ICP_ITER_DEBUG
     static const bool v2 = [] {

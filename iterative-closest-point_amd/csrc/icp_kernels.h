@@ -525,8 +525,40 @@ void launch_canon_moments(const int *idx, const double4 *m4, const double *px, c
 void launch_canon_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                             int n, const Xform *xf, const int *done, float4 *p32, double *rows, const SeedArgs &sa,
                             hipStream_t st);
-void launch_canon_fold(const double *rows, int n, double *sums, int mode, const CanonStep &cs, hipStream_t st,
-                       int strands = 0); // (strands > 0: rows given as canon_strands(n) strands, canon_row_value)
+// Block b of nb -> row, so that an XCD's blocks (b = k, k + 8, ...: k = b % 8) take runs of L
+// consecutive rows: XCD k's i th block takes row (8 (i / L) + k) L + i % L, a bijection of the
+// first 8 L floor(nb / 8 L) blocks; the rest keep their own index.  L < 0: one run per XCD,
+// [k q + min(k, e), (k + 1) q + min(k + 1, e)) (q = nb / 8, e = nb % 8); L = 0: the identity.
+__host__ __device__ inline int xcd_row(int b, int nb, int L)
+{
+    const int k = b & 7, i = b >> 3;
+    if (L < 0) {
+        const int q = nb >> 3, e = nb & 7;
+        return k * q + (k < e ? k : e) + i;
+    }
+    if (L == 0 || b >= nb / (8 * L) * (8 * L)) return b;
+    return ((i / L) * 8 + k) * L + i % L;
+}
+// The fused grid iteration's dispatch order (nn_grid_iter2_kernel, one-strand workgroups): block
+// b takes strand order[b] instead of xcd_row(b, S, L).  Built from the strands' walker counts of
+// the launch before (walk_last, CertArgs) by 8 extra workgroups of the column fold, one an XCD:
+// each XCD keeps its own strands (and, forms 1 and 2, its runs of L), dispatched heavy-first --
+// the waves that start last, whose length is the launch's tail, are then the lightest.  Which
+// block takes which strand changes no bit of any result.
+//   form 1: each run's strands heavy-first, the runs in place
+//        2: the runs heavy-first by their total, each run's strands heavy-first
+//        3: all of the XCD's strands heavy-first, whatever their run
+//   + 4 (5, 6, 7): light-first -- the adversarial order of the tests
+// Ties keep xcd_row's order (a stable counting sort): the table is reproducible.
+struct IterOrder {
+    const int *walk_last = nullptr;
+    int *order = nullptr; // (null: no table is built)
+    int S = 0, L = 0, form = 0;
+};
+// Returns true when the launch built ord's table (a column fold, modes 0, 1 and 4, with ord.order set).
+bool launch_canon_fold(const double *rows, int n, double *sums, int mode, const CanonStep &cs, hipStream_t st,
+                       int strands = 0, // (strands > 0: rows given as canon_strands(n) strands, canon_row_value)
+                       const IterOrder &ord = IterOrder{});
 // the fused grid iteration (icp_grid.hip, nn_grid_iter_kernel): the previous transform (st->xf) of
 // the scene in slot order, the exact seeded grid search of every point (box: cells a query's own
 // box may have before the whole wave takes it; budget: cells before every model point), and the
@@ -551,6 +583,10 @@ struct CertArgs {
     int two = 1;
     double skin = 0.0;
     unsigned long long *counts = nullptr; // (64-bit: accumulated over the runs of one scene size)
+    // the dispatch order (IterOrder; one-strand workgroups only): walk_last[s] = the queries strand
+    // s walked in this launch; order (null: xcd_row) = the table the fold built from the launch before
+    int *walk_last = nullptr;
+    const int *order = nullptr;
 };
 // Returns true when the launch wrote the certificate state (ca.state non-null, the certificate form).
 bool launch_nn_grid_iter(int n, double *px, double *py, double *pz, double *yx, double *yy, double *yz, int *idx,
@@ -560,6 +596,8 @@ bool launch_nn_grid_iter(int n, double *px, double *py, double *pz, double *yx, 
                          int xform = 1, // (0: no pending transform -- a run's first iteration, seeds in idx / y)
                          const CertArgs &ca = CertArgs{}, // (ca.state null: no certificate, every query walks)
                          int *strands = nullptr); // (out: canon_strands(n) when rows were written as strands, else 0)
+// the run length L of xcd_row for that launch's one-strand workgroups (of S = canon_strands(n))
+int nn_grid_iter_strand_run(int n);
 // One-pass moments around the shifts of *st (identical on every rank): y = m[idx];
 // partial [sum (p - cp) (3), sum (y - cy) (3), sum (p - cp)(y - cy)^T (9), sum ||y - cy||^2,
 // sum ||p - cp||^2] (17, sums slots 0..16; horn_step(shifted) removes the shift)

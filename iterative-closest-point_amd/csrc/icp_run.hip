@@ -20,6 +20,12 @@
 
 namespace {
 
+#ifndef ICP_ITER2_DBG
+#define ICP_ITER2_DBG 0 // (1: the diagnostic build, icp_grid.hip)
+#endif
+// (the diagnostic build's wave records behind ICP_ITER_DEBUG's 16 counters: four words a block)
+constexpr size_t kIterDbgRec = ICP_ITER2_DBG ? 4 * (size_t)icp::kCanonStrandsMax : 0;
+
 bool env_not0(const char *name) // on unless atoi(value) == 0
 {
     const char *e = getenv(name);
@@ -81,6 +87,8 @@ RunKnobs read_run_knobs()
     e = getenv("ICP_CERT_SKIN1");
     const double skin1 = e ? atof(e) : -1.0;
     k.cert_skin1 = skin1 >= 0.0 && skin1 <= 4.0 ? skin1 : k.cert_skin;
+    e = getenv("ICP_ITER2_ORDER");
+    k.iter2_order = !e ? 2 : atoi(e) >= 1 && atoi(e) <= 7 && atoi(e) != 4 ? atoi(e) : 0;
     e = getenv("ICP_ITER_DEBUG");
     k.iter_debug = !e ? 0 : atoi(e) == 2 ? 2 : 1;
     k.tail_split_err = getenv("ICP_TAIL_SPLIT_ERR") != nullptr;
@@ -234,6 +242,14 @@ struct LoopRun {
     // leaves it stale.
     CertArgs cert;
     bool cert_prev = false;
+    // The fused iteration's dispatch order (IterOrder): the table the fold builds from one fused
+    // launch's walker counts is the next fused launch's, and only that one's -- walk_written: the
+    // last launch left counts worth sorting (one-strand workgroups, a certificate state read: in a
+    // run's first fused launch every query walks); order_ok: the fold since built the table.  Any
+    // other search, and the run's end, drop both, so a table never outlives its scene
+    // (icp_set_scene), its size or its path.
+    IterOrder order;
+    bool walk_written = false, order_ok = false;
     bool xf_pending = false; // (canon: the last Horn step's transform is still to be applied)
     int rows_strands = 0;    // (> 0: the last fused launch wrote the canonical rows as this many strands)
     int slot_ticket[kRing] = {};
@@ -979,21 +995,31 @@ int run_setup_canon(LoopRun &r)
         // read when the stats are; another size folds them into the stats first (a synchronisation
         // the runs of a registration loop do not pay: 60 us a run at C4, profiles/r06/r06fold3)
         const int crows = canon_strands(n); // (rows or strands: nn_grid_iter2_kernel NWG)
+        // (3 words a strand: the two counts, then walk_last and the order table, an int each)
         if (ctx->cert_counts_rows != crows) {
             TRY(fold_cert_counts(ctx));
-            TRY(grow(ctx, &ctx->cert_counts, &ctx->cert_counts_cap, 2 * (size_t)crows));
-            HIPCHK(hipMemsetAsync(ctx->cert_counts, 0, 2 * (size_t)crows * sizeof(ctx->cert_counts[0]), ctx->st));
+            TRY(grow(ctx, &ctx->cert_counts, &ctx->cert_counts_cap, 3 * (size_t)crows));
+            HIPCHK(hipMemsetAsync(ctx->cert_counts, 0, 3 * (size_t)crows * sizeof(ctx->cert_counts[0]), ctx->st));
             ctx->cert_counts_rows = crows;
         }
         r.cert.state = ctx->cert_state;
         r.cert.two = k.cert_two;
         r.cert.skin = k.cert_skin / ctx->grid.inv_h;
         r.cert.counts = ctx->cert_counts;
+        if (k.iter2_order) {
+            r.cert.walk_last = (int *)(ctx->cert_counts + 2 * (size_t)crows);
+            r.order.walk_last = r.cert.walk_last;
+            r.order.order = r.cert.walk_last + crows;
+            r.order.S = crows;
+            r.order.L = nn_grid_iter_strand_run((int)n);
+            r.order.form = k.iter2_order;
+        }
     }
     // ICP_ITER_DEBUG=1: nn_grid_iter_kernel's phase clocks and counts, summed over the run, to stderr
     if (k.iter_debug && r.canon) {
         unsigned long long *&buf = knob_owner().iter_dbg;
-        if (!buf) HIPCHK(hipMalloc((void **)&buf, 16 * sizeof(unsigned long long)));
+        // (the diagnostic build, -DICP_ITER2_DBG=1: + four words a wave, nn_grid_iter2_kernel's records)
+        if (!buf) HIPCHK(hipMalloc((void **)&buf, (16 + kIterDbgRec) * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(buf, 0, 16 * sizeof(unsigned long long), ctx->st));
         r.iter_dbg = buf;
     }
@@ -1060,6 +1086,14 @@ int canon_transform(LoopRun &r, const SeedArgs &sa_t)
     return ICP_OK;
 }
 
+// the table the fold after a fused launch is to build (IterOrder), or none; consumes walk_written
+IterOrder fold_order(LoopRun &r)
+{
+    const bool build = r.walk_written;
+    r.walk_written = false;
+    return build ? r.order : IterOrder{};
+}
+
 // canon: the error step of iteration `it` (ticket of its slot) after the fold of the rows --
 // with the Horn step of the current iteration (horn) or alone (the run's last residual)
 int canon_end(LoopRun &r, int it, bool horn, int slot)
@@ -1073,12 +1107,13 @@ int canon_end(LoopRun &r, int it, bool horn, int slot)
     cs.ticket = r.slot_ticket[sl];
     const int strands = r.rows_strands; // (the fused kernel wrote the rows as strands)
     r.rows_strands = 0;
+    const IterOrder ord = fold_order(r);
     if (!r.lag) {
-        launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, horn ? 1 : 2, cs, ctx->st, strands);
+        r.order_ok = launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, horn ? 1 : 2, cs, ctx->st, strands, ord);
         LAUNCHCHK("canon_fold");
         return ICP_OK;
     }
-    launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, horn ? 0 : 3, cs, ctx->st, strands);
+    r.order_ok = launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, horn ? 0 : 3, cs, ctx->st, strands, ord);
     LAUNCHCHK("canon_fold");
     const bool tm = horn && slot >= 0 && r.ar_timed[slot];
     if (tm) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 3], ctx->st));
@@ -1106,12 +1141,13 @@ int canon_first(LoopRun &r)
     icp_ctx *ctx = r.ctx;
     const int strands = r.rows_strands;
     r.rows_strands = 0;
+    const IterOrder ord = fold_order(r);
     if (!r.lag) {
-        launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, 4, r.cs, ctx->st, strands);
+        r.order_ok = launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, 4, r.cs, ctx->st, strands, ord);
         LAUNCHCHK("canon_fold");
         return ICP_OK;
     }
-    launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, 0, r.cs, ctx->st, strands);
+    r.order_ok = launch_canon_fold(ctx->canon_rowbuf, (int)r.n, ctx->sums, 0, r.cs, ctx->st, strands, ord);
     LAUNCHCHK("canon_fold");
     TRY(allreduce(ctx, ctx->sums, kNumSums));
     launch_horn_step(ctx->sums, r.N, ctx->c, true, ctx->amb_count, ctx->iter_state, ctx->st);
@@ -1170,17 +1206,53 @@ int canon_path(LoopRun &r, bool *grid_out)
     return ICP_OK;
 }
 
+// The diagnostic build (-DICP_ITER2_DBG=1) with ICP_ITER_DEBUG=2 and ICP_ITER_TAIL_DUMP=<file>:
+// the last fused launch's wave records (entry time, exit time at 100 MHz, strand << 32 | XCD << 16
+// | walkers, tasks << 48 | walk batches << 32 | pair tests -- four words a block) appended to the
+// file after a header (magic, iteration, blocks, n); tools/iter_tail.py reads it.  The launch's
+// counts, which one-strand workgroups leave in their records, are added to cnt.  The stream is
+// idle here (ICP_ITER_DEBUG=2 synchronises).
+int dump_wave_records(LoopRun &r, unsigned long long cnt[4])
+{
+    if (!ICP_ITER2_DBG || r.rows_strands <= 0) return ICP_OK;
+    icp_ctx *ctx = r.ctx;
+    const size_t nb = (size_t)r.rows_strands;
+    std::vector<unsigned long long> h(4 + 4 * nb);
+    h[0] = 0x4c494154524554ull; // ("ITERTAIL")
+    h[1] = (unsigned long long)r.enqueued;
+    h[2] = nb;
+    h[3] = r.n;
+    HIPCHK(hipMemcpy(h.data() + 4, r.iter_dbg + 16, 4 * nb * sizeof(h[0]), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < nb; ++b) {
+        const unsigned long long w = h[4 + 4 * b + 2], c = h[4 + 4 * b + 3];
+        cnt[0] += c >> 48;
+        cnt[1] += w & 0xffffull;
+        cnt[2] += (c >> 32) & 0xffffull;
+        cnt[3] += c & 0xffffffffull;
+    }
+    const char *path = getenv("ICP_ITER_TAIL_DUMP");
+    if (!path) return ICP_OK;
+    FILE *f = fopen(path, "ab");
+    if (!f) return fail(ctx, ICP_E_HIP, "ICP_ITER_TAIL_DUMP: cannot open the file");
+    fwrite(h.data(), sizeof(h[0]), h.size(), f);
+    fclose(f);
+    return ICP_OK;
+}
+
 // the fused grid iteration's launch (nn_grid_iter_kernel); xform 0: no pending transform
 void launch_fused_iter(LoopRun &r, int xform)
 {
     icp_ctx *ctx = r.ctx;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
     IterState *sd = ctx->iter_state;
+    r.cert.order = r.order_ok ? r.order.order : nullptr;
+    r.order_ok = false; // (the table was this launch's: the next fold builds the next one)
     r.cert_prev = launch_nn_grid_iter((int)r.n, P.x, P.y, P.z, Y.x, Y.y, Y.z, ctx->idx, sd, r.need_p32 ? P.f : nullptr,
                                       grid_view(ctx), kSeededBox, grid_budget(ctx), (int)ctx->nm, ctx->m4,
                                       ctx->canon_rowbuf, r.grid_policy ? &sd->far_acc : nullptr,
                                       r.sa_grid.far_box > 0 ? -1.0 : r.sa_grid.far_d2, ctx->amb_count + 2, ctx->st,
                                       r.iter_dbg, xform, r.cert, &r.rows_strands);
+    r.walk_written = r.cert_prev && r.cert.valid && r.cert.walk_last && r.rows_strands == r.order.S;
 }
 
 // a fresh run's first iteration on the grid as ONE launch too: cell seeds (their
@@ -1224,6 +1296,7 @@ int enqueue_canon_fused(LoopRun &r, int slot, bool timed)
         unsigned long long h[16];
         HIPCHK(hipStreamSynchronize(ctx->st));
         HIPCHK(hipMemcpy(h, r.iter_dbg, sizeof(h), hipMemcpyDeviceToHost));
+        TRY(dump_wave_records(r, h));
         fprintf(stderr, "[iter2_debug] it %d tasks %llu walkers %llu batches %llu pair tests %llu (lane 0's)\n",
                 r.enqueued, h[0], h[1], h[2], h[3]);
         HIPCHK(hipMemset(r.iter_dbg, 0, sizeof(h)));
@@ -1246,6 +1319,7 @@ int enqueue_canon_search(LoopRun &r, int slot, bool timed, bool grid_c)
     DevCloud &P = ctx->scene, &Y = ctx->Y;
     IterState *sd = ctx->iter_state;
     r.cert_prev = false; // (any other search: the certificate's state is stale)
+    r.walk_written = r.order_ok = false; // (and so is the dispatch order)
     if (r.xf_pending) { // the last Horn step's transform, in the form this search reads
         SeedArgs sa_t = grid_c ? r.sa_grid : r.sa;
         if (!grid_c) records_args(r, sa_t);
@@ -1544,6 +1618,8 @@ int run_loop(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                         "| wave-us A %.1f BC %.1f D %.1f E %.1f FG %.1f\n",
                 h[0], h[1], h[2], h[3], h[4], h[10], h[11], h[5] * 0.01, h[6] * 0.01, h[7] * 0.01, h[8] * 0.01,
                 h[9] * 0.01);
+        // (four-wave workgroups only: one-strand workgroups count into their records, read a launch
+        // at a time by ICP_ITER_DEBUG=2)
         fprintf(stderr, "[iter2_debug] (nn_grid_iter2_kernel, an ICP_ITER2_DBG build) tasks %llu walkers %llu batches %llu "
                         "pair tests %llu (lane 0's)\n",
                 h[0], h[1], h[2], h[3]);
