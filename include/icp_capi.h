@@ -36,6 +36,7 @@ extern "C" {
 #define ICP_E_NO_DEVICE (-7)      /* no HIP device / bad device ordinal             */
 #define ICP_E_IO (-8)             /* file could not be opened (src/load.cc:11-14)   */
 #define ICP_E_RANGE (-9)          /* coordinates outside the engine's domain        */
+#define ICP_E_DEGENERATE (-10)    /* point-to-plane: an iteration's 6 x 6 system is singular */
 
 /* ---- nearest-neighbour arithmetic -------------------------------------- */
 /* Both modes return the SAME indices: the first (lowest-index) minimum of the fp64
@@ -72,7 +73,8 @@ typedef struct icp_result {
     int iterations; /* ICP iterations executed                                       */
     int converged;  /* 1 if err < threshold stopped the loop (src/GPU/gpu.cc:79-80)   */
     double err;     /* last err = (e_align + e_apply) / np, as printed (gpu.cc:76)    */
-    double s;       /* last increment's scale       (GPU::ICP::s, gpu.hh:91)          */
+    double s;       /* last increment's scale       (GPU::ICP::s, gpu.hh:91); 1 with
+                       ICP_METRIC_POINT_TO_PLANE                                      */
     double R[9];    /* last increment's rotation, row-major (GPU::ICP::r, gpu.hh:93)  */
     double t[3];    /* last increment's translation (GPU::ICP::t, gpu.hh:92)          */
 } icp_result;
@@ -247,6 +249,38 @@ int icp_get_inliers(icp_ctx *ctx, uint8_t *mask_out, long long *count_out);
  * (counts_out may be NULL when cap is 0) and returns the number of recorded iterations (>= 0),
  * or ICP_E_NO_MODEL as icp_get_inliers. */
 int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap);
+
+/* ---- the point-to-plane metric ------------------------------------------- */
+/* ICP_METRIC_POINT_TO_PLANE: icp_run minimises, in every iteration, the kept pairs' squared
+ * distance along the model's normal (Chen-Medioni; Low 2004) instead of Horn's point-to-point
+ * closed form.  With y_j = m[idx_j] and n_j = N[idx_j] the correspondence and its normal,
+ * c the model's centroid, a_j = [(p_j - c) x n_j ; n_j] and r_j = (p_j - y_j) . n_j, the iteration
+ * solves (sum a_j a_j^T) x = -sum a_j r_j in fp64 (Cholesky of the system scaled to a unit
+ * diagonal) on the device, and moves EVERY point by q = R p + t with R = exp([x[0..2]]x) (Rodrigues)
+ * and t = (c + x[3..5]) - R c; err = (e + e) / K with e = sum ((q_j - y_j) . n_j)^2 over the K kept
+ * pairs.  There is no scale: res->s is 1 in this mode.  The pairs kept are those of
+ * icp_set_max_distance (all of them when the gate is off; icp_get_inliers / icp_get_inlier_trace
+ * then keep reporting the last GATED run).  An iteration with K < 6 stops the run before it
+ * changes anything with ICP_E_TOO_FEW_POINTS, as the gate's K < 4 does; one whose system has a
+ * diagonal entry not > 0 or, scaled, a Cholesky pivot not > 1e-12 (a planar model, a surface of
+ * revolution with exact normals) stops it the same way with ICP_E_DEGENERATE, and icp_last_error
+ * names the iteration and the smallest pivot.  A point-to-plane run always takes the launch loop
+ * (ICP_RUN_LAUNCHES), whatever icp_set_run_mode says; without normals it returns ICP_E_NO_MODEL.
+ * ICP_METRIC_POINT_TO_POINT (the default): icp_run exactly as without this call.  Another value is
+ * ICP_E_ARG.  The setting survives icp_set_scene / icp_set_model. */
+#define ICP_METRIC_POINT_TO_POINT 0
+#define ICP_METRIC_POINT_TO_PLANE 1
+int icp_set_metric(icp_ctx *ctx, int metric);
+/* The resident model's normals: n_xyz is a host array, 3 x nm column-major like a cloud, normal j
+ * belonging to model point j.  They are used AS GIVEN: the engine does not renormalise them, and a
+ * zero normal makes its pairs contribute nothing to the system or the error.  ICP_E_NO_MODEL
+ * without a model, ICP_E_SIZE_MISMATCH if nm differs from the resident model's, ICP_E_ARG for a
+ * null pointer or a non-finite value.  Every icp_set_model* call that changes the model drops
+ * them; icp_ensure_model keeps them when it did not upload. */
+int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm);
+/* The same array already in device memory, read like icp_set_model_device's (after the work of any
+ * stream; valid until the call returns); its values are not checked for finiteness. */
+int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm);
 
 /* ---- the ICP loop: GPU::ICP::find_corresponding_opti (src/GPU/gpu.cc:52-83) -- */
 /* Runs up to max_iter iterations on the resident clouds; stops after the iteration

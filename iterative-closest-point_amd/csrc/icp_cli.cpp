@@ -14,6 +14,8 @@
 //   --threshold X      convergence threshold (default 1e-5, src/cpu.hh:113)
 //   --max-dist X       max correspondence distance: pairs farther apart than X are left out of
 //                      each iteration's alignment and error (partial overlap; default: none)
+//   --normals FILE     the model's normals, a CSV in the clouds' format with one row per model point:
+//                      selects the point-to-plane metric (combines with --max-dist; no scale)
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
 #include <cstdio>
@@ -47,7 +49,7 @@ int main(int argc, char **argv)
     int nn_mode = ICP_NN_CERTIFIED, device = 0;
     int rule = std::strcmp(prog, "icp") == 0 ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
     double threshold = 1e-5, max_dist = 0.0;
-    const char *out = "output.txt";
+    const char *out = "output.txt", *normals = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -58,6 +60,7 @@ int main(int argc, char **argv)
             rule = !std::strcmp(argv[a], "cpu") ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
         } else if (!std::strcmp(argv[a], "--threshold") && a + 1 < argc) threshold = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--max-dist") && a + 1 < argc) max_dist = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
         else {
@@ -69,6 +72,13 @@ int main(int argc, char **argv)
     size_t nm = 0, np = 0;
     double *m = load_or_exit(argv[1], &nm);
     double *p = load_or_exit(argv[2], &np);
+
+    size_t nn = 0;
+    double *nrm = normals ? load_or_exit(normals, &nn) : nullptr;
+    if (normals && nn != nm) {
+        std::fprintf(stderr, "[error] --normals: %zu rows for a model of %zu points\n", nn, nm);
+        return -1;
+    }
 
     // alignement_check (cpu.cc:42-53 / gpu.cc:54-62): message + exit(-1)
     if (np != nm && !allow_unequal) {
@@ -96,6 +106,11 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
     }
+    if (normals && ((rc = icp_set_model_normals(ctx, nrm, nn)) != ICP_OK ||
+                    (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK)) {
+        std::fprintf(stderr, "[error] --normals: %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
+        return 3;
+    }
     double *errs = (double *)std::calloc(max_iter > 0 ? (size_t)max_iter : 1, sizeof(double));
     icp_result res{};
     // each iteration's line as it ends (gpu.cc:65,77), from the engine's progress callback
@@ -120,5 +135,6 @@ int main(int argc, char **argv)
     std::free(errs);
     icp_free(m);
     icp_free(p);
+    icp_free(nrm);
     return 0;
 }

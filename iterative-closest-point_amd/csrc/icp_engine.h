@@ -283,6 +283,22 @@ struct icp_ctx {
     bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
     int gate_iters = 0;     // ... and recorded this many iterations
 
+    // the point-to-plane metric (icp_set_metric; icp_plane.hip): the model's normals as
+    // (nx, ny, nz, 0) by model index (dropped with the model), the moments' partial rows, the kept
+    // pairs' normals by scene point (when the transform streams them), the loop's state with its
+    // mapped host mirror.  With the gate on the run uses the gate's mask and K trace (it is the
+    // last gated run); with it off its own, so that icp_get_inliers keeps the last gated run's.
+    int metric = 0; // ICP_METRIC_*
+    double4 *n4 = nullptr, *plane_nst = nullptr;
+    size_t n4_cap = 0, plane_nst_cap = 0;
+    bool has_normals = false;
+    double *plane_part = nullptr;
+    unsigned long long *plane_mask = nullptr;
+    size_t plane_part_cap = 0, plane_mask_cap = 0;
+    PlaneState *plane_state = nullptr, *h_plane = nullptr, *d_plane_mirror = nullptr;
+    long long *h_pktrace = nullptr, *d_pktrace = nullptr;
+    size_t pktrace_cap = 0;
+
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
     std::string err;
@@ -381,6 +397,9 @@ struct SeedState {
 //                                                                              over the run, to stderr; 2: each launch's (synchronises)
 //   tail_split_err     ICP_TAIL_SPLIT_ERR      off      set                    the fused tail's error step as its own launch (A/B)
 //   debug_policy       ICP_DEBUG_POLICY        off      set                    the policy's far counts, to stderr
+//   plane_stream       ICP_PLANE_NORMALS       off      value == "stream"      the point-to-plane transform streams the normals the
+//                                                                              moments stored by point instead of gathering them
+//                                                                              again (A/B)
 struct RunKnobs {
     int grid_budget;
     bool grid_auto, grid_iter;
@@ -401,6 +420,7 @@ struct RunKnobs {
     int iter2_order;
     int iter_debug;
     bool tail_split_err, debug_policy;
+    bool plane_stream;
 };
 const RunKnobs &run_knobs();
 

@@ -1261,7 +1261,9 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->s_order, (void *)ctx->s_tmp_idx, (void *)ctx->b_pimg_l, (void *)ctx->b_frame,
                     (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
-                    (void *)ctx->gate_mask, (void *)ctx->gate_flags, (void *)ctx->gate_part, (void *)ctx->gate_state})
+                    (void *)ctx->gate_mask, (void *)ctx->gate_flags, (void *)ctx->gate_part, (void *)ctx->gate_state,
+                    (void *)ctx->n4, (void *)ctx->plane_nst, (void *)ctx->plane_part, (void *)ctx->plane_mask,
+                    (void *)ctx->plane_state})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
@@ -1270,6 +1272,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
     if (ctx->h_far) (void)hipHostFree(ctx->h_far);
     if (ctx->h_gate) (void)hipHostFree(ctx->h_gate);
     if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
+    if (ctx->h_plane) (void)hipHostFree(ctx->h_plane);
+    if (ctx->h_pktrace) (void)hipHostFree(ctx->h_pktrace);
     if (ctx->h_few) (void)hipHostFree(ctx->h_few);
     if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
     if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
@@ -1352,6 +1356,53 @@ int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap)
     return ctx->gate_iters;
 }
 
+int icp_set_metric(icp_ctx *ctx, int metric)
+{
+    if (!ctx || (metric != ICP_METRIC_POINT_TO_POINT && metric != ICP_METRIC_POINT_TO_PLANE)) return ICP_E_ARG;
+    ctx->metric = metric;
+    return ICP_OK;
+}
+
+// the normals' double4 rows from their interleaved array in device memory
+static int set_normals_from(icp_ctx *ctx, const double *aos_dev, size_t nm)
+{
+    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, nm));
+    launch_plane_normals4(aos_dev, (int)nm, ctx->n4, ctx->st);
+    LAUNCHCHK("plane_normals4");
+    HIPCHK(hipStreamSynchronize(ctx->st)); // (the caller's array, or the stage, is free again)
+    ctx->has_normals = true;
+    return ICP_OK;
+}
+
+static int normals_args(icp_ctx *ctx, const double *n_xyz, size_t nm)
+{
+    if (!ctx || !n_xyz) return ICP_E_ARG;
+    if (!ctx->has_model) return fail(ctx, ICP_E_NO_MODEL, "icp_set_model_normals: no model (icp_set_model)");
+    if (nm != ctx->nm)
+        return fail(ctx, ICP_E_SIZE_MISMATCH, "icp_set_model_normals: " + std::to_string(nm) + " normals for a model of " +
+                                                  std::to_string(ctx->nm) + " points");
+    HIPCHK(hipSetDevice(ctx->device));
+    return ICP_OK;
+}
+
+int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm)
+{
+    TRY(normals_args(ctx, n_xyz, nm));
+    for (size_t k = 0; k < 3 * nm; ++k)
+        if (!std::isfinite(n_xyz[k]))
+            return fail(ctx, ICP_E_ARG, "icp_set_model_normals: normal " + std::to_string(k / 3) + " is not finite");
+    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * nm));
+    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * nm, hipMemcpyHostToDevice, ctx->st));
+    return set_normals_from(ctx, ctx->stage, nm);
+}
+
+int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm)
+{
+    TRY(normals_args(ctx, n_xyz_dev, nm));
+    HIPCHK(hipDeviceSynchronize()); // (as icp_set_model_device: after the work of any stream)
+    return set_normals_from(ctx, n_xyz_dev, nm);
+}
+
 // The model's AoS copy -> ctx->stage (pageable host memory: the runtime's staged copy).
 static int stage_model(icp_ctx *ctx, const double *m_xyz, size_t nm)
 {
@@ -1426,6 +1477,7 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
         }
     if (rm > 1e15) return fail(ctx, ICP_E_RANGE, "model coordinates exceed 1e15 around the centroid");
     ctx->has_model = false; // (until every image below is built)
+    ctx->has_normals = false; // (the normals belong to the model they were given for)
     for (int k = 0; k < 3; ++k) ctx->c[k] = c[k];
     ctx->rm = rm;
     // 3. the images: SoA fp64, the centred fp32 copy padded to whole LDS tiles with far points

@@ -320,6 +320,7 @@ const char *icp_strerror(int code)
     case ICP_E_NO_DEVICE: return "no HIP device";
     case ICP_E_IO: return "file could not be opened";
     case ICP_E_RANGE: return "coordinates outside the supported range";
+    case ICP_E_DEGENERATE: return "degenerate point-to-plane system";
     default: return "unknown error";
     }
 }

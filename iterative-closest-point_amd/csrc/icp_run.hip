@@ -4,8 +4,8 @@
 //   icp_run -> run_loop: run_setup, then per iteration enqueue_canon (a scene in slot order: the
 //              canonical schedule) or enqueue_launches (every other scene: the launch loop),
 //              wait_one for the ring's oldest iteration, the drain and finish_run
-//   run_setup hands over to run_gated (icp_set_max_distance) or run_persistent (the one-launch
-//              loops of small clouds) where they apply
+//   run_setup hands over to run_plane (icp_set_metric), run_gated (icp_set_max_distance) or
+//              run_persistent (the one-launch loops of small clouds) where they apply
 //   run_knobs / run_test_knobs: every environment switch of the run path (the table in icp_engine.h)
 #include <algorithm>
 #include <chrono>
@@ -93,6 +93,8 @@ RunKnobs read_run_knobs()
     k.iter_debug = !e ? 0 : atoi(e) == 2 ? 2 : 1;
     k.tail_split_err = getenv("ICP_TAIL_SPLIT_ERR") != nullptr;
     k.debug_policy = getenv("ICP_DEBUG_POLICY") != nullptr;
+    e = getenv("ICP_PLANE_NORMALS");
+    k.plane_stream = e && std::strcmp(e, "stream") == 0;
     return k;
 }
 
@@ -649,6 +651,19 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     return finish_run(ctx, threshold, err_trace, res, wall0);
 }
 
+// a mapped K trace of at least max_iter entries (the gated and the point-to-plane loop)
+int grow_ktrace(icp_ctx *ctx, long long **h, long long **d, size_t *cap, int max_iter)
+{
+    if (*cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
+    if (*h) HIPCHK(hipHostFree(*h)); // (the previous run ended with a sync)
+    *h = nullptr;
+    *cap = 0;
+    const size_t want = (size_t)std::max(max_iter, 64);
+    TRY(mapped_alloc(ctx, h, d, sizeof(long long) * want));
+    *cap = want;
+    return ICP_OK;
+}
+
 // icp_run with the max-correspondence-distance gate on (icp_set_max_distance; kernels in
 // icp_gated.hip).  run_setup_buffers has prepared the loop state, the mapped mirrors and the flag ring.
 // Per iteration: the search as the launch loop's generic path runs it (seeded by the previous
@@ -672,14 +687,7 @@ int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
     TRY(grow(ctx, &ctx->gate_part, &ctx->gate_part_cap, (size_t)kRedMaxBlocksCap * kGateSums));
     if (!ctx->gate_state) HIPCHK(hipMalloc((void **)&ctx->gate_state, sizeof(GateState)));
     if (!ctx->h_gate) TRY(mapped_alloc(ctx, &ctx->h_gate, &ctx->d_gate_mirror, sizeof(GateState)));
-    if (ctx->ktrace_cap < (size_t)std::max(max_iter, 1)) { // (the previous run ended with a sync)
-        if (ctx->h_ktrace) HIPCHK(hipHostFree(ctx->h_ktrace));
-        ctx->h_ktrace = nullptr;
-        ctx->ktrace_cap = 0;
-        const size_t cap = (size_t)std::max(max_iter, 64);
-        TRY(mapped_alloc(ctx, &ctx->h_ktrace, &ctx->d_ktrace, sizeof(long long) * cap));
-        ctx->ktrace_cap = cap;
-    }
+    TRY(grow_ktrace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
     std::memset(ctx->h_gate, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->gate_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -772,6 +780,135 @@ int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hg.fail_iter) + " kept K = " + std::to_string(hg.K) +
                         " pairs within the max correspondence distance; need at least 4");
+    return ICP_OK;
+}
+
+// icp_run with the point-to-plane metric (icp_set_metric; kernels in icp_plane.hip): run_gated's
+// loop -- the same search call, ring and bookkeeping -- with the plane moments (gate, mask, 28
+// sums), the fold and the 6 x 6 solve, and the transform with the residual along the normal; the
+// residual's fold and error step are the gated loop's.  No pre-pass: the sums need no shifts.  With
+// ranks or a communicator the 28 sums and the residual are each all-reduced before their step.
+// With the gate on (D finite) the run is the last gated run: it uses the gate's mask and K trace and
+// leaves icp_get_inliers its last gate; with it off (D = +inf) it keeps its own, and the last gated
+// run's stay.  It leaves the state run_gated leaves.
+int run_plane(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
+              std::chrono::steady_clock::time_point wall0)
+{
+    if (!ctx->has_normals)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_run: the point-to-plane metric needs the model's normals (icp_set_model_normals)");
+    if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0);
+    const size_t n = ctx->scene.n;
+    DevCloud &P = ctx->scene, &Y = ctx->Y;
+    const bool gated = ctx->gate_dmax > 0.0;
+    const double D = gated ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
+    const bool ranks = lag_run(ctx);
+    const int nb = red_blocks(n);
+    unsigned long long *mask = nullptr;
+    long long *d_ktrace = nullptr;
+    if (gated) {
+        TRY(grow(ctx, &ctx->gate_mask, &ctx->gate_mask_cap, (n + 63) / 64));
+        TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
+        if (!ctx->h_gate) TRY(mapped_alloc(ctx, &ctx->h_gate, &ctx->d_gate_mirror, sizeof(GateState)));
+        TRY(grow_ktrace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
+        mask = ctx->gate_mask;
+        d_ktrace = ctx->d_ktrace;
+    } else {
+        TRY(grow(ctx, &ctx->plane_mask, &ctx->plane_mask_cap, (n + 63) / 64));
+        TRY(grow_ktrace(ctx, &ctx->h_pktrace, &ctx->d_pktrace, &ctx->pktrace_cap, max_iter));
+        mask = ctx->plane_mask;
+        d_ktrace = ctx->d_pktrace;
+    }
+    TRY(grow(ctx, &ctx->plane_part, &ctx->plane_part_cap, (size_t)kRedMaxBlocksCap * kPlaneSums));
+    double4 *nst = nullptr;
+    if (run_knobs().plane_stream) {
+        TRY(grow(ctx, &ctx->plane_nst, &ctx->plane_nst_cap, n));
+        nst = ctx->plane_nst;
+    }
+    if (!ctx->plane_state) HIPCHK(hipMalloc((void **)&ctx->plane_state, sizeof(PlaneState)));
+    if (!ctx->h_plane) TRY(mapped_alloc(ctx, &ctx->h_plane, &ctx->d_plane_mirror, sizeof(PlaneState)));
+    std::memset(ctx->h_plane, 0, sizeof(PlaneState));
+    HIPCHK(hipMemsetAsync(ctx->plane_state, 0, sizeof(PlaneState), ctx->st));
+    IterState *sd = ctx->iter_state;
+    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c);
+    if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
+    const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
+    ctx->stats.run_path_bits = 0;
+    LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
+    r.ctx = ctx;
+    r.n = n;
+    r.digest_order = digest_order;
+    while (!r.stop && r.waited < max_iter) {
+        if (r.enqueued < max_iter && r.enqueued - r.waited <= kAhead) {
+            // 1. correspondences (a search queued behind the iteration that froze the run returns at once)
+            const SeedState ws;
+            ctx->second_pass_items = 0;
+            TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, nullptr, nullptr, false, &ws, &sd->done, ctx->scene_slot,
+                                false, nullptr));
+            TRY(after_search(r, r.enqueued, false, -1));
+            // 2-6. the gate, the kept pairs' 28 sums, the solve
+            launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c, mask, nst,
+                                 ctx->plane_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
+            launch_plane_solve(ctx->plane_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->plane_state,
+                               ctx->d_plane_mirror, ctx->d_iter_mirror, ctx->st);
+            LAUNCHCHK("plane_moments");
+            if (ranks) {
+                TRY(allreduce(ctx, ctx->sums, kPlaneSums));
+                launch_plane_solve(nullptr, 0, ctx->sums, true, ctx->c, ctx->amb_count, sd, ctx->plane_state,
+                                   ctx->d_plane_mirror, ctx->d_iter_mirror, ctx->st);
+                LAUNCHCHK("plane_solve");
+            }
+            // 7. every point moves; the kept points' residual along the normal; err = (e + e) / K
+            launch_plane_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr, mask,
+                                   ctx->idx, ctx->n4, nst, ctx->partials, ctx->st);
+            if (!need_p32) ctx->p32_stale = true;
+            const int sl = r.enqueued % kRing;
+            r.slot_ticket[sl] = ++ctx->flag_ticket;
+            launch_gated_err(ctx->partials, nb, ctx->sums, !ranks, threshold, max_iter, ctx->err_trace_dev, sd,
+                             &ctx->plane_state->gate, d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror,
+                             ctx->d_trace, ctx->st);
+            LAUNCHCHK("plane_transform");
+            if (ranks) {
+                TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
+                launch_gated_err(nullptr, 0, ctx->sums, true, threshold, max_iter, ctx->err_trace_dev, sd,
+                                 &ctx->plane_state->gate, d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl],
+                                 ctx->d_iter_mirror, ctx->d_trace, ctx->st);
+                LAUNCHCHK("plane_err");
+            }
+            ++r.enqueued;
+            continue;
+        }
+        TRY(wait_one(r));
+    }
+    // with the gate on: the last gate evaluated, as flags in the caller's point order (icp_get_inliers)
+    if (gated && r.enqueued > 0) {
+        launch_gated_unpack(mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
+        LAUNCHCHK("gated_unpack");
+    }
+    HIPCHK(hipStreamSynchronize(ctx->st)); // (the iteration queued behind the last one drains)
+    // nothing of a transform is carried to the next run: it starts from the correspondences alone
+    ctx->seedd_valid = false;
+    ctx->last_far = -1;
+    ctx->last_q2 = -1;
+    ctx->second_pass_items = 0;
+    const PlaneState hp = *ctx->h_plane;
+    if (gated && r.enqueued > 0) {
+        *ctx->h_gate = hp.gate;
+        ctx->gate_have = true;
+        ctx->gate_iters = ctx->h_iter->iter;
+    }
+    TRY(finish_run(ctx, threshold, err_trace, res, wall0));
+    if (hp.gate.status == kGateTooFew)
+        return fail(ctx, ICP_E_TOO_FEW_POINTS,
+                    "icp_run: iteration " + std::to_string(hp.gate.fail_iter) + " kept K = " + std::to_string(hp.gate.K) +
+                        " pairs; the point-to-plane metric needs at least 6");
+    if (hp.gate.status == kPlaneDegenerate) {
+        char piv[32];
+        std::snprintf(piv, sizeof(piv), "%.3g", hp.min_pivot);
+        return fail(ctx, ICP_E_DEGENERATE,
+                    "icp_run: iteration " + std::to_string(hp.gate.fail_iter) +
+                        " has a degenerate point-to-plane system (smallest pivot " + piv + ", K = " +
+                        std::to_string(hp.gate.K) + ")");
+    }
     return ICP_OK;
 }
 
@@ -1050,6 +1187,9 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     r.threshold = threshold;
     TRY(run_setup_buffers(r));
     *handed = true;
+    // icp_set_metric: the point-to-plane loop, gated or not (as the gate: never the one-launch kernels)
+    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE)
+        return run_plane(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     // icp_set_max_distance: the gated loop (never the one-launch kernels or the fused iterations)
     if (ctx->gate_dmax > 0.0) return run_gated(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     {

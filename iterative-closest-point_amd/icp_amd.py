@@ -38,6 +38,7 @@ ICP_E_RCCL = -6
 ICP_E_NO_DEVICE = -7
 ICP_E_IO = -8
 ICP_E_RANGE = -9
+ICP_E_DEGENERATE = -10  # point-to-plane: an iteration's 6 x 6 system is singular
 
 NN_CERTIFIED = 0
 NN_FP64 = 1
@@ -52,6 +53,8 @@ RULE_CPU_SQRT = 1   # the reference CPU path's sqrt(pow) distance (src/cpu.cc:17
 RUN_AUTO = 0        # icp_set_run_mode: one launch for eligible small runs, else the launch loop
 RUN_LAUNCHES = 1
 RUN_PERSISTENT = 2
+METRIC_POINT_TO_POINT = 0  # icp_set_metric: Horn's closed form, scale included (the default)
+METRIC_POINT_TO_PLANE = 1  # the distance along the model's normals (set_model_normals), no scale
 
 # every function include/icp_capi.h declares (checked by tests/test_capi.py)
 EXPORTED = [
@@ -69,6 +72,7 @@ EXPORTED = [
     "icp_get_comm_info", "icp_set_bundle_counters", "icp_get_bundle_counters", "icp_get_model_order",
     "icp_bundle_audit", "icp_sort_pairs", "icp_get_grid",
     "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
+    "icp_set_metric", "icp_set_model_normals", "icp_set_model_normals_device",
 ]
 
 
@@ -181,6 +185,10 @@ def lib() -> C.CDLL:
         L.icp_set_max_distance.argtypes = [vp, C.c_double]
         L.icp_get_inliers.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_longlong)]
         L.icp_get_inlier_trace.argtypes = [vp, C.POINTER(C.c_longlong), sz]
+    if hasattr(L, "icp_set_metric"):
+        L.icp_set_metric.argtypes = [vp, C.c_int]
+        L.icp_set_model_normals.argtypes = [vp, dp, sz]
+        L.icp_set_model_normals_device.argtypes = [vp, vp, sz]
     _lib = L
     return L
 
@@ -412,6 +420,20 @@ class Context:
         """icp_set_max_distance: run() keeps only the pairs no farther apart than d (0 or inf: off)."""
         self._check(lib().icp_set_max_distance(self._h, float(d)))
 
+    def set_metric(self, metric: int):
+        """icp_set_metric: METRIC_POINT_TO_POINT (the default) / METRIC_POINT_TO_PLANE (needs
+        set_model_normals; run() then returns s = 1 and may raise ICP_E_DEGENERATE)."""
+        self._check(lib().icp_set_metric(self._h, int(metric)))
+
+    def set_model_normals(self, n):
+        """icp_set_model_normals: one normal per point of the resident model, used as given."""
+        n = _cloud(n)
+        self._check(lib().icp_set_model_normals(self._h, _dp(n), n.shape[0]))
+
+    def set_model_normals_device(self, ptr: int, nm: int):
+        """icp_set_model_normals_device: the normals' AoS fp64 array already in device memory."""
+        self._check(lib().icp_set_model_normals_device(self._h, C.c_void_p(ptr), nm))
+
     def inliers(self):
         """The last gate of the last gated run() -> (mask: bool (np_local,), caller's order; K over all ranks)."""
         mask = np.zeros(self._np_local, dtype=np.uint8)
@@ -576,6 +598,7 @@ class ICP:
     threshold: float = 1e-5  # src/GPU/gpu.hh:103
     allow_unequal: bool = False
     max_distance: float | None = None  # icp_set_max_distance (None: no gate)
+    normals: np.ndarray | None = None  # the model's normals: the point-to-plane metric (None: point-to-point)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -592,6 +615,9 @@ class ICP:
         if self.max_distance is not None:
             self._ctx.set_max_distance(self.max_distance)
         self._ctx.set_model(self.m)
+        if self.normals is not None:
+            self._ctx.set_model_normals(self.normals)
+            self._ctx.set_metric(METRIC_POINT_TO_PLANE)
         self._ctx.set_scene(self.p)
 
     def find_corresponding_opti(self):
