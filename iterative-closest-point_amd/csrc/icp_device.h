@@ -32,11 +32,12 @@ __device__ __forceinline__ void block_sum_store(double (&a)[K], double *out)
 }
 
 // a[k] += row b's k-th value for this thread's rows b = t, t + kBlock, ... in that order (the
-// reduce_kernel fold), four rows' loads issued before their sums: the same sums in the same
-// order, one memory round trip per four rows instead of one per row
-template <int K> __device__ __forceinline__ void fold_rows(const double *__restrict__ part, int nblocks, double (&a)[K])
+// reduce_kernel fold), kRows rows' loads issued before their sums: the same sums in the same
+// order, one memory round trip per kRows rows instead of one per row (kRows = 1, the plain loop:
+// where kRows x K values in flight are more registers than the kernel has to spare)
+template <int K, int kRows = 4>
+__device__ __forceinline__ void fold_rows(const double *__restrict__ part, int nblocks, double (&a)[K])
 {
-    constexpr int kRows = 4;
     for (int b0 = threadIdx.x; b0 < nblocks; b0 += kRows * kBlock) {
         double v[kRows][K];
 #pragma unroll

@@ -269,35 +269,32 @@ struct icp_ctx {
     int *s_tmp_idx = nullptr;
     size_t s_tmp_idx_cap = 0;
 
-    // the max-correspondence-distance gate (icp_set_max_distance; icp_gated.hip): dmax (0: off),
-    // the last gated run's mask words (the scene's order), its flags in the caller's order, the
-    // gate's device state with its mapped host mirror, and the mapped K trace
-    double gate_dmax = 0.0;
-    unsigned long long *gate_mask = nullptr;
-    unsigned char *gate_flags = nullptr;
-    double *gate_part = nullptr; // (the gated moments' partial rows: kGateSums a workgroup)
-    size_t gate_mask_cap = 0, gate_flags_cap = 0, gate_part_cap = 0;
-    GateState *gate_state = nullptr, *h_gate = nullptr, *d_gate_mirror = nullptr;
+    // The kept-pairs loop (run_kept: the max-correspondence-distance gate, icp_set_max_distance and
+    // icp_gated.hip, and the point-to-plane metric, icp_set_metric and icp_plane.hip).  Scoped to one
+    // run, whichever metric: the mask words (the scene's order), the moments' partial rows (kPlaneSums a
+    // workgroup, the wider of the two), the device state with its mapped host mirror, the mapped K trace.
+    unsigned long long *kept_mask = nullptr;
+    double *kept_part = nullptr;
+    size_t kept_mask_cap = 0, kept_part_cap = 0;
+    GateState *kept_state = nullptr, *h_kept = nullptr, *d_kept_mirror = nullptr;
     long long *h_ktrace = nullptr, *d_ktrace = nullptr;
     size_t ktrace_cap = 0;
+    // The gate: dmax (0: off), and what icp_get_inliers / icp_get_inlier_trace report, saved at the
+    // end of the last gated run (a later ungated plane run leaves it): the flags in the caller's
+    // order, K of the last gate evaluated, the recorded iterations' K.
+    double gate_dmax = 0.0;
+    unsigned char *gate_flags = nullptr;
+    size_t gate_flags_cap = 0;
     bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
-    int gate_iters = 0;     // ... and recorded this many iterations
+    long long gate_K = 0;
+    std::vector<long long> gate_ktrace;
 
-    // the point-to-plane metric (icp_set_metric; icp_plane.hip): the model's normals as
-    // (nx, ny, nz, 0) by model index (dropped with the model), the moments' partial rows, the kept
-    // pairs' normals by scene point (when the transform streams them), the loop's state with its
-    // mapped host mirror.  With the gate on the run uses the gate's mask and K trace (it is the
-    // last gated run); with it off its own, so that icp_get_inliers keeps the last gated run's.
+    // the point-to-plane metric: the model's normals as (nx, ny, nz, 0) by model index (dropped with
+    // the model)
     int metric = 0; // ICP_METRIC_*
-    double4 *n4 = nullptr, *plane_nst = nullptr;
-    size_t n4_cap = 0, plane_nst_cap = 0;
+    double4 *n4 = nullptr;
+    size_t n4_cap = 0;
     bool has_normals = false;
-    double *plane_part = nullptr;
-    unsigned long long *plane_mask = nullptr;
-    size_t plane_part_cap = 0, plane_mask_cap = 0;
-    PlaneState *plane_state = nullptr, *h_plane = nullptr, *d_plane_mirror = nullptr;
-    long long *h_pktrace = nullptr, *d_pktrace = nullptr;
-    size_t pktrace_cap = 0;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
@@ -397,9 +394,6 @@ struct SeedState {
 //                                                                              over the run, to stderr; 2: each launch's (synchronises)
 //   tail_split_err     ICP_TAIL_SPLIT_ERR      off      set                    the fused tail's error step as its own launch (A/B)
 //   debug_policy       ICP_DEBUG_POLICY        off      set                    the policy's far counts, to stderr
-//   plane_stream       ICP_PLANE_NORMALS       off      value == "stream"      the point-to-plane transform streams the normals the
-//                                                                              moments stored by point instead of gathering them
-//                                                                              again (A/B)
 struct RunKnobs {
     int grid_budget;
     bool grid_auto, grid_iter;
@@ -420,7 +414,6 @@ struct RunKnobs {
     int iter2_order;
     int iter_debug;
     bool tail_split_err, debug_policy;
-    bool plane_stream;
 };
 const RunKnobs &run_knobs();
 

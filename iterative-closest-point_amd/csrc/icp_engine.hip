@@ -1261,19 +1261,16 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->s_order, (void *)ctx->s_tmp_idx, (void *)ctx->b_pimg_l, (void *)ctx->b_frame,
                     (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
-                    (void *)ctx->gate_mask, (void *)ctx->gate_flags, (void *)ctx->gate_part, (void *)ctx->gate_state,
-                    (void *)ctx->n4, (void *)ctx->plane_nst, (void *)ctx->plane_part, (void *)ctx->plane_mask,
-                    (void *)ctx->plane_state})
+                    (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
+                    (void *)ctx->n4})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
     if (ctx->h_iter) (void)hipHostFree(ctx->h_iter);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
     if (ctx->h_far) (void)hipHostFree(ctx->h_far);
-    if (ctx->h_gate) (void)hipHostFree(ctx->h_gate);
+    if (ctx->h_kept) (void)hipHostFree(ctx->h_kept);
     if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
-    if (ctx->h_plane) (void)hipHostFree(ctx->h_plane);
-    if (ctx->h_pktrace) (void)hipHostFree(ctx->h_pktrace);
     if (ctx->h_few) (void)hipHostFree(ctx->h_few);
     if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
     if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
@@ -1342,7 +1339,7 @@ int icp_get_inliers(icp_ctx *ctx, uint8_t *mask_out, long long *count_out)
         HIPCHK(hipMemcpyAsync(mask_out, ctx->gate_flags, ctx->scene.n, hipMemcpyDeviceToHost, ctx->st));
         HIPCHK(hipStreamSynchronize(ctx->st));
     }
-    if (count_out) *count_out = ctx->h_gate->K;
+    if (count_out) *count_out = ctx->gate_K;
     return ICP_OK;
 }
 
@@ -1351,9 +1348,9 @@ int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap)
     if (!ctx || (!counts_out && cap)) return ICP_E_ARG;
     if (!ctx->has_scene || !ctx->gate_have)
         return fail(ctx, ICP_E_NO_MODEL, "no gated icp_run since icp_set_scene (icp_set_max_distance)");
-    const size_t k = std::min(cap, (size_t)ctx->gate_iters);
-    if (k) std::memcpy(counts_out, ctx->h_ktrace, sizeof(long long) * k);
-    return ctx->gate_iters;
+    const size_t k = std::min(cap, ctx->gate_ktrace.size());
+    if (k) std::memcpy(counts_out, ctx->gate_ktrace.data(), sizeof(long long) * k);
+    return (int)ctx->gate_ktrace.size();
 }
 
 int icp_set_metric(icp_ctx *ctx, int metric)

@@ -12,17 +12,24 @@
 namespace icp {
 namespace {
 
-__device__ __forceinline__ void horn_step_body(const double *__restrict__ sums, double N, double c0, double c1, double c2,
-                               int shifted, int *__restrict__ cnt, IterState *__restrict__ s)
+// The counters every step kernel keeps for the loop, whatever its metric: the search's queue sizes
+// into the statistics, then zeroed for the next search (always: the next search appends to these
+// counters even after the loop has converged or stopped).  Returns whether the loop still runs.
+__device__ __forceinline__ bool step_counters(int *__restrict__ cnt, IterState *__restrict__ s)
 {
-    // the search's queue sizes: into the statistics, then zeroed for the next search (always:
-    // the next search appends to these counters even after the loop has converged)
     const int qc[4] = {cnt[0], cnt[1], cnt[2], cnt[3]};
     for (int k = 0; k < 4; ++k) cnt[k] = 0;
     s->far_acc = 0; // (this iteration's transform counts afresh)
     s->queued2 = qc[2];
-    if (s->done) return;
+    if (s->done) return false;
     for (int k = 0; k < 4; ++k) s->nn_counts[k] += qc[k];
+    return true;
+}
+
+__device__ __forceinline__ void horn_step_body(const double *__restrict__ sums, double N, double c0, double c1, double c2,
+                               int shifted, int *__restrict__ cnt, IterState *__restrict__ s)
+{
+    if (!step_counters(cnt, s)) return;
     double mu_p[3], mu_y[3], S[9], d_caps, sp;
     if (!shifted) { // two-pass sums (moments_phase): Σp, Σy, then centred S, d_caps, sp
         for (int k = 0; k < 3; ++k) {

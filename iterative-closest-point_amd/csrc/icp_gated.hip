@@ -9,21 +9,24 @@
 //   err = (e + e) / K with e the kept pairs' residual.
 // The gate of an iteration is kept bit-packed, one 64-bit word per wave of points (__ballot), for
 // the transform's residual and for icp_get_inliers.
+// The loop over the pairs with the gate and its mask, the transform's body, the fold and the freeze
+// of a stopped run are icp_kept.h's, shared with the point-to-plane kernels (icp_plane.hip); the
+// residual's fold and error step here (launch_gated_err) and the mask's unpacking serve both.
 // Compiled with IEEE semantics like icp_step.hip (the error step's `err < threshold` and the
 // gate's `d2 <= D` must stay false for a NaN).
 #include <hip/hip_runtime.h>
 
 #include "icp_device.h"
 #include "icp_fold.h"
+#include "icp_kept.h"
 #include "icp_kernels.h"
 
 namespace icp {
 namespace {
 
 // Modelled on shifted_moments_kernel: the 17 one-pass moment terms around the shifts of *st, of
-// the kept pairs only, and the kept count as an 18th sum (a double: exact below 2^53).
-// The loop runs whole waves (its bound is the wave's first point), so that every lane takes part
-// in the ballot; word w of the mask holds points 64 w .. 64 w + 63 and is stored by lane 0.
+// the kept pairs only (kept_pairs_pass: the gate and its mask), and the kept count as an 18th sum
+// (a double: exact below 2^53).
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
 template <bool YIN>
 __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
@@ -40,32 +43,12 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
 #pragma unroll
     for (int k = 0; k < 17; ++k) a[k] = 0.0;
     double kept = 0.0;
-    const int lane = threadIdx.x & 63;
-    const long long G = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i - lane < n; i += G) {
-        bool keep = false;
-        if (i < n) {
-            double4 m;
-            if constexpr (YIN) { // (the search wrote y = m[idx]: the same values, streamed)
-                m = make_double4(yx[i], yy[i], yz[i], 0.0);
-            } else {
-                m = kpos ? m4kd[kpos[i]] : m4[idx[i]]; // (kpos: the same point, kd-ordered copy)
-                yx[i] = m.x;
-                yy[i] = m.y;
-                yz[i] = m.z;
-            }
-            const double q0 = px[i], q1 = py[i], q2 = pz[i];
-            const double dx = q0 - m.x, dy = q1 - m.y, dz = q2 - m.z;
-            const double d2 = (dx * dx + dy * dy) + dz * dz;
-            keep = d2 <= D;
-            if (keep) {
-                shifted_moment_terms(q0, q1, q2, m, cp0, cp1, cp2, cy0, cy1, cy2, a);
-                kept += 1.0;
-            }
-        }
-        const unsigned long long word = __ballot(keep);
-        if (lane == 0) mask[i >> 6] = word;
-    }
+    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+                         [&](long long, double q0, double q1, double q2, const double4 &m, double, double, double)
+                             __attribute__((always_inline)) {
+                                 shifted_moment_terms(q0, q1, q2, m, cp0, cp1, cp2, cy0, cy1, cy2, a);
+                                 kept += 1.0;
+                             });
     double b[kGateSums];
 #pragma unroll
     for (int k = 0; k < 17; ++k) b[k] = a[k];
@@ -73,43 +56,10 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
     block_sum_store<kGateSums>(b, partials + (size_t)blockIdx.x * kGateSums);
 }
 
-// reduce_kernel<K>'s tree over nblocks rows of K doubles: out[k] (global) and res[k] (LDS) for
-// k < K; every thread of the workgroup must call it.  One row folds to itself.
-template <int K>
-__device__ __forceinline__ void fold_to(const double *__restrict__ partials, int nblocks, double *__restrict__ out,
-                                        double *res)
-{
-    __shared__ double sh[kBlock / 64][K];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = 0.0;
-    fold_rows<K>(partials, nblocks, a);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh[wave][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double r = sh[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) r += sh[w][threadIdx.x];
-        out[threadIdx.x] = r;
-        res[threadIdx.x] = r;
-    }
-    __syncthreads();
-}
-
 // The fold of the moments' partial rows into sums[0..17] (nblocks > 0) and / or the gated Horn
 // step on sums (step; nblocks = 0: the sums as they are, all-reduced).  The step decides from the
-// global count K = sums[kGateCount], identical on every rank: K < 4 freezes the run (done) with
-// the too-few status before anything of this iteration is applied, and mirrors the loop state of
-// the last completed iteration to the host; else Horn's closed form over the kept pairs, N = K.
+// global count K = sums[kGateCount], identical on every rank: K < 4 freezes the run with the
+// too-few status (kept_stop); else Horn's closed form over the kept pairs, N = K.
 __global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__restrict__ partials, int nblocks,
                                                             double *__restrict__ sums, int step, double c0, double c1,
                                                             double c2, int *__restrict__ cnt, IterState *__restrict__ s,
@@ -128,16 +78,7 @@ __global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__rest
     if (!s->done) { // (a frozen iteration's sums are stale: its gate was not evaluated)
         g->K = (long long)K;
         h_g->K = (long long)K;
-        if (!(K >= 4.0)) {
-            s->done = 1;
-            g->status = kGateTooFew;
-            g->fail_iter = s->iter;
-            h_g->status = kGateTooFew;
-            h_g->fail_iter = s->iter;
-            const int *src = (const int *)s;
-            int *dst = (int *)h_state;
-            for (size_t k = 0; k < sizeof(IterState) / sizeof(int); ++k) dst[k] = src[k];
-        }
+        if (!(K >= 4.0)) kept_stop(s, g, h_g, h_state, kGateTooFew, 0.0);
     }
     horn_step_body(res, K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
 }
@@ -157,34 +98,17 @@ __global__ void gated_first_shift_kernel(IterState *__restrict__ s, const double
 }
 
 // Modelled on the plain branch of transform_err_kernel: every point moves, the residual is
-// summed over the kept points (the gate's mask words).  A no-op once *done.
+// summed over the kept points (kept_transform).
 __global__ __launch_bounds__(kBlock) void gated_transform_kernel(
     double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, const double *__restrict__ yx,
     const double *__restrict__ yy, const double *__restrict__ yz, int n, const Xform *__restrict__ xfd,
     const int *__restrict__ done, float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
     double *__restrict__ partials)
 {
-    __shared__ Xform sxf;
-    __shared__ int sdone;
-    if (threadIdx.x == 0) {
-        sdone = *done;
-        sxf = *xfd;
-    }
-    __syncthreads();
-    if (sdone) return;
-    const Xform xf = sxf;
-    double a[1] = {0.0};
-    const long long G = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += G) {
-        double q0, q1, q2;
-        transform_point(xf, px[i], py[i], pz[i], q0, q1, q2);
-        if ((mask[i >> 6] >> (i & 63)) & 1ull) a[0] += residual2(yx[i], yy[i], yz[i], q0, q1, q2);
-        px[i] = q0;
-        py[i] = q1;
-        pz[i] = q2;
-        if (p32) p32[i] = make_float4((float)(q0 - xf.c[0]), (float)(q1 - xf.c[1]), (float)(q2 - xf.c[2]), 0.0f);
-    }
-    block_sum_store<1>(a, partials + blockIdx.x);
+    kept_transform(px, py, pz, n, xfd, done, p32, mask, partials,
+                   [&](long long i, double q0, double q1, double q2) __attribute__((always_inline)) {
+                       return residual2(yx[i], yy[i], yz[i], q0, q1, q2);
+                   });
 }
 
 // The fold of the residual's partial rows into sums[kSumErr] (nblocks > 0) and / or the error

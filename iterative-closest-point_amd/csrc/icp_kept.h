@@ -1,0 +1,140 @@
+// icp_kept.h — what the kept-pairs iterations share on the device (icp_gated.hip: point-to-point
+// under the max-distance gate; icp_plane.hip: point-to-plane, gated or not).  Private to those two
+// files, which hold each metric's own arithmetic and are compiled with IEEE semantics (`d2 <= D`
+// must stay false for a NaN):
+//   kept_pairs_pass   the moments kernels' loop: y, the gate, the mask word, a callable per kept pair
+//   kept_transform    the transform kernels' body: every point moves, a callable gives a kept
+//                     point's squared residual
+//   fold_to           the fold of per-workgroup partial rows (reduce_kernel's tree)
+//   kept_stop         the freeze of a run whose iteration cannot be solved
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "icp_device.h"
+#include "icp_kernels.h"
+
+namespace icp {
+namespace {
+
+// For every point i of this thread's grid stride: y_i = m[idx_i] (YIN: streamed from the copy the
+// search or a pre-pass stored; else gathered and stored), d = p_i - y_i, keep = d2 <= D with
+// d2 = (dx*dx + dy*dy) + dz*dz as written, and kept(i, p, y, d) for a kept pair.
+// The loop runs whole waves (its bound is the wave's first point), so that every lane takes part
+// in the ballot; word w of the mask holds points 64 w .. 64 w + 63 and is stored by lane 0.
+template <bool YIN, class Kept>
+__device__ __forceinline__ void kept_pairs_pass(const int *__restrict__ idx, const double4 *__restrict__ m4,
+                                                const double *__restrict__ px, const double *__restrict__ py,
+                                                const double *__restrict__ pz, int n, double *__restrict__ yx,
+                                                double *__restrict__ yy, double *__restrict__ yz, double D,
+                                                unsigned long long *__restrict__ mask, const int *__restrict__ kpos,
+                                                const double4 *__restrict__ m4kd, Kept &&kept)
+{
+    const int lane = threadIdx.x & 63;
+    const long long G = (long long)gridDim.x * kBlock;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i - lane < n; i += G) {
+        bool keep = false;
+        if (i < n) {
+            double4 m;
+            if constexpr (YIN) { // (the search wrote y = m[idx]: the same values, streamed)
+                m = make_double4(yx[i], yy[i], yz[i], 0.0);
+            } else {
+                m = kpos ? m4kd[kpos[i]] : m4[idx[i]]; // (kpos: the same point, kd-ordered copy)
+                yx[i] = m.x;
+                yy[i] = m.y;
+                yz[i] = m.z;
+            }
+            const double q0 = px[i], q1 = py[i], q2 = pz[i];
+            const double dx = q0 - m.x, dy = q1 - m.y, dz = q2 - m.z;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            keep = d2 <= D;
+            if (keep) kept(i, q0, q1, q2, m, dx, dy, dz);
+        }
+        const unsigned long long word = __ballot(keep);
+        if (lane == 0) mask[i >> 6] = word;
+    }
+}
+
+// A transform kernel's body: p <- sR p + t for every point (p32 nullable), and this workgroup's
+// partial [sum over the kept points (the gate's mask words) of residual(i, p')].  A no-op once *done.
+template <class Residual>
+__device__ __forceinline__ void kept_transform(double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz,
+                                               int n, const Xform *__restrict__ xfd, const int *__restrict__ done,
+                                               float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
+                                               double *__restrict__ partials, Residual &&residual)
+{
+    __shared__ Xform sxf;
+    __shared__ int sdone;
+    if (threadIdx.x == 0) {
+        sdone = *done;
+        sxf = *xfd;
+    }
+    __syncthreads();
+    if (sdone) return;
+    const Xform xf = sxf;
+    double a[1] = {0.0};
+    const long long G = (long long)gridDim.x * kBlock;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += G) {
+        double q0, q1, q2;
+        transform_point(xf, px[i], py[i], pz[i], q0, q1, q2);
+        if ((mask[i >> 6] >> (i & 63)) & 1ull) a[0] += residual(i, q0, q1, q2);
+        px[i] = q0;
+        py[i] = q1;
+        pz[i] = q2;
+        if (p32) p32[i] = make_float4((float)(q0 - xf.c[0]), (float)(q1 - xf.c[1]), (float)(q2 - xf.c[2]), 0.0f);
+    }
+    block_sum_store<1>(a, partials + blockIdx.x);
+}
+
+// reduce_kernel<K>'s tree over nblocks rows of K doubles: out[k] (global) and res[k] (LDS) for
+// k < K; every thread of the workgroup must call it.  One row folds to itself.  ROWS: fold_rows'
+// rows in flight.
+template <int K, int ROWS = 4>
+__device__ __forceinline__ void fold_to(const double *__restrict__ partials, int nblocks, double *__restrict__ out,
+                                        double *res)
+{
+    __shared__ double sh[kBlock / 64][K];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = 0.0;
+    fold_rows<K, ROWS>(partials, nblocks, a);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) sh[wave][k] = a[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double r = sh[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) r += sh[w][threadIdx.x];
+        out[threadIdx.x] = r;
+        res[threadIdx.x] = r;
+    }
+    __syncthreads();
+}
+
+// An iteration that cannot be solved freezes the run (done) before anything of it is applied: the
+// status, the iteration and the pivot go to the device state and its host mirror, and the loop
+// state of the last completed iteration is mirrored to the host.  One thread.
+__device__ __forceinline__ void kept_stop(IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                          IterState *__restrict__ h_state, int status, double min_pivot)
+{
+    s->done = 1;
+    g->status = status;
+    g->fail_iter = s->iter;
+    g->min_pivot = min_pivot;
+    h_g->status = status;
+    h_g->fail_iter = s->iter;
+    h_g->min_pivot = min_pivot;
+    const int *src = (const int *)s;
+    int *dst = (int *)h_state;
+    for (size_t k = 0; k < sizeof(IterState) / sizeof(int); ++k) dst[k] = src[k];
+}
+
+} // namespace
+} // namespace icp

@@ -766,12 +766,13 @@ void launch_reduce(const double *partials, int nblocks, int K, double *out, hipS
 // GateState::K); the residual's fold then writes its e there (kSumErr), as in the ungated loop.
 constexpr int kGateSums = 18, kGateCount = 17;
 constexpr int kGateTooFew = 1;
-// Per-run state of the gate, beside IterState (whose layout every other kernel reads): device
-// copy and mapped host mirror.
+// Per-run state of a kept-pairs loop (the gated and the point-to-plane one), beside IterState
+// (whose layout every other kernel reads): device copy and mapped host mirror.
 struct GateState {
-    int status;    // 0, or kGateTooFew: an iteration's K < 4 froze the run
-    int fail_iter; // ... the iteration (0-based) that found it
-    long long K;   // kept pairs, all ranks', of the last gate evaluated
+    int status;       // 0, kGateTooFew or kPlaneDegenerate: an iteration that could not be solved froze the run
+    int fail_iter;    // ... the iteration (0-based) that found it
+    long long K;      // kept pairs, all ranks', of the last gate evaluated
+    double min_pivot; // kPlaneDegenerate: the smallest Cholesky pivot met (0: a diagonal entry was not > 0)
 };
 // y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; mask word w = the ballot of points
 // 64 w ..; partial [17 shifted moment terms of the kept pairs, their count]; a no-op once done
@@ -806,32 +807,24 @@ void launch_gated_unpack(const unsigned long long *mask, const int *order, int n
 // the gated loop (the solve has read the sums by then).
 constexpr int kPlaneSums = 28, kPlaneB = 21, kPlaneCount = 27;
 constexpr int kPlaneDegenerate = 2; // (GateState::status, beside kGateTooFew: here K < 6)
-// Per-run state of the plane loop: the gate's (K of the last gate evaluated, the status and the
-// iteration that froze the run) and the smallest Cholesky pivot of a degenerate iteration (0: a
-// diagonal entry was not > 0).  Device copy and mapped host mirror.
-struct PlaneState {
-    GateState gate;
-    double min_pivot;
-};
 // n4[i] = (n_i, 0) from nm interleaved xyz normals in device memory
 void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t st);
 // y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; the mask as launch_gated_moments;
-// partial [the 27 sums of the kept pairs with their normals n4[idx], their count]; nst (nullable):
-// the kept pairs' normals, stored by point; a no-op once done
+// partial [the 27 sums of the kept pairs with their normals n4[idx], their count]; a no-op once done
 void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
                           const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          const double c[3], unsigned long long *mask, double4 *nst, double *partials, hipStream_t st,
-                          const int *kpos, const double4 *m4kd, bool y_ready);
+                          const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                          const double4 *m4kd, bool y_ready);
 // nblocks > 0: sums[0..27] = the fold of the partial rows (reduce_kernel's tree); step: K < 6 or a
 // degenerate system sets done and the status (the loop state mirrored to h_state), else the solve:
 // s = 1, R = exp([omega]x), t = (c + tau) - R c into the loop state
 void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, PlaneState *plane, PlaneState *h_plane, IterState *h_state, hipStream_t st);
+                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st);
 // p <- R p + t for every point (p32 nullable); partial [sum over the kept points of ((p' - y) . n)^2],
-// n = nst[i] when nst is given, else n4[idx[i]]
+// n = n4[idx[i]]
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                             int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            const int *idx, const double4 *n4, const double4 *nst, double *partials, hipStream_t st);
+                            const int *idx, const double4 *n4, double *partials, hipStream_t st);
 
 // ---- the model's preparation on the device (icp_model.hip) ------------------------------------
 // out[10] = (sum x, sum y, sum z, lo xyz, hi xyz, non-finite coordinates) of n AoS points:

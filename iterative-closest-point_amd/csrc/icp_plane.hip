@@ -13,14 +13,16 @@
 //   or a pivot not > 1e-12 stops the run like too-few (degenerate);
 //   omega = x[0..2], tau = x[3..5]: R = exp([omega]x), s = 1, t = (c + tau) - R c; every point
 //   moves by q = R p + t, and err = (e + e) / K with e = sum over the kept pairs of ((q - y) . n)^2.
-// The gate's mask is icp_gated.hip's (one 64-bit word per wave of points), and the residual's fold
-// and error step are its launch_gated_err.
+// The loop over the pairs with the gate and its mask (one 64-bit word per wave of points), the
+// transform's body, the fold and the freeze of a stopped run are icp_kept.h's, shared with
+// icp_gated.hip; the residual's fold and error step are that file's launch_gated_err.
 // Compiled with IEEE semantics like icp_gated.hip (`d2 <= D`, `A_kk > 0` and `pivot > 1e-12` must
 // stay false for a NaN).
 #include <hip/hip_runtime.h>
 
 #include "icp_device.h"
 #include "icp_fold.h"
+#include "icp_kept.h"
 #include "icp_kernels.h"
 
 namespace icp {
@@ -35,44 +37,27 @@ __global__ __launch_bounds__(kBlock) void plane_normals4_kernel(const double *__
     n4[i] = make_double4(aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], 0.0);
 }
 
-// Modelled on gated_moments_kernel: the whole-wave loop and the ballot mask are its own; the sums
-// are the 21 + 6 of the normal equations and the kept count as the 28th (a double: exact below
-// 2^53).  No shifts: r is a difference of near points, and (p - c) is taken before any product.
-// NST: each kept pair's normal is also stored at nst[i] (the transform then streams it).
+// The sums over the kept pairs (kept_pairs_pass: the gate and its mask, as the gated moments): the
+// 21 + 6 of the normal equations and the kept count as the 28th (a double: exact below 2^53).  No
+// shifts: r is a difference of near points, and (p - c) is taken before any product.
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN, bool NST>
+template <bool YIN>
 __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
-    double c0, double c1, double c2, unsigned long long *__restrict__ mask, double4 *__restrict__ nst,
-    double *__restrict__ partials, const int *__restrict__ kpos, const double4 *__restrict__ m4kd)
+    double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd)
 {
     if (st->done != 0) return;
     double a[kPlaneSums];
 #pragma unroll
     for (int k = 0; k < kPlaneSums; ++k) a[k] = 0.0;
-    const int lane = threadIdx.x & 63;
-    const long long G = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i - lane < n; i += G) {
-        bool keep = false;
-        if (i < n) {
-            double4 m;
-            if constexpr (YIN) { // (the search wrote y = m[idx]: the same values, streamed)
-                m = make_double4(yx[i], yy[i], yz[i], 0.0);
-            } else {
-                m = kpos ? m4kd[kpos[i]] : m4[idx[i]]; // (kpos: the same point, kd-ordered copy)
-                yx[i] = m.x;
-                yy[i] = m.y;
-                yz[i] = m.z;
-            }
-            const double q0 = px[i], q1 = py[i], q2 = pz[i];
-            const double dx = q0 - m.x, dy = q1 - m.y, dz = q2 - m.z;
-            const double d2 = (dx * dx + dy * dy) + dz * dz;
-            keep = d2 <= D;
-            if (keep) {
+    kept_pairs_pass<YIN>(
+        idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+        [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
+            __attribute__((always_inline)) {
                 const double4 nn = n4[idx[i]]; // (idx is final here whichever search ran: kpos rides beside it)
-                if constexpr (NST) nst[i] = nn;
                 const double u0 = q0 - c0, u1 = q1 - c1, u2 = q2 - c2;
                 double v[6];
                 v[0] = u1 * nn.z - u2 * nn.y;
@@ -89,47 +74,8 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
 #pragma unroll
                 for (int row = 0; row < 6; ++row) a[kPlaneB + row] += v[row] * r;
                 a[kPlaneCount] += 1.0;
-            }
-        }
-        const unsigned long long word = __ballot(keep);
-        if (lane == 0) mask[i >> 6] = word;
-    }
+            });
     block_sum_store<kPlaneSums>(a, partials + (size_t)blockIdx.x * kPlaneSums);
-}
-
-// reduce_kernel<K>'s tree over nblocks rows of kPlaneSums doubles (icp_gated.hip's fold_to, restated
-// for 28 columns): out[k] (global) and res[k] (LDS); every thread of the workgroup must call it.
-__device__ __forceinline__ void plane_fold_to(const double *__restrict__ partials, int nblocks, double *__restrict__ out,
-                                              double *res)
-{
-    constexpr int K = kPlaneSums;
-    __shared__ double sh[kBlock / 64][K];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double a[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) a[k] = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += kBlock) { // (rows t, t + kBlock, ...: fold_rows' order)
-#pragma unroll
-        for (int k = 0; k < K; ++k) a[k] += partials[(size_t)b * K + k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) a[k] += __shfl_xor(a[k], o, 64);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) sh[wave][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double r = sh[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) r += sh[w][threadIdx.x];
-        out[threadIdx.x] = r;
-        res[threadIdx.x] = r;
-    }
-    __syncthreads();
 }
 
 // The 6 x 6 solve of one thread.  sums: the 28 folded sums; A (36) and w (12: g, then x) are the
@@ -179,21 +125,20 @@ __device__ __forceinline__ bool plane_solve(const double *sums, double *A, doubl
     return true;
 }
 
-// The fold of the moments' partial rows into sums[0..27] (nblocks > 0) and / or the solve and step
-// on sums (step; nblocks = 0: the sums as they are, all-reduced).  The step decides from the global
-// sums, identical on every rank: K < 6 or a degenerate system freezes the run (done) with its
-// status before anything of this iteration is applied, and mirrors the loop state of the last
-// completed iteration to the host, as gated_horn_kernel does; else s = 1, R, t of the solve.
+// The fold of the moments' partial rows into sums[0..27] (nblocks > 0; one row in flight: 28 columns
+// leave no registers for four) and / or the solve and step on sums (step; nblocks = 0: the sums as
+// they are, all-reduced).  The step decides from the global sums, identical on every rank: K < 6 or
+// a degenerate system freezes the run with its status (kept_stop); else s = 1, R, t of the solve.
 __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__restrict__ partials, int nblocks,
                                                              double *__restrict__ sums, int step, double c0, double c1,
                                                              double c2, int *__restrict__ cnt, IterState *__restrict__ s,
-                                                             PlaneState *__restrict__ g, PlaneState *__restrict__ h_g,
+                                                             GateState *__restrict__ g, GateState *__restrict__ h_g,
                                                              IterState *__restrict__ h_state)
 {
     __shared__ double res[kPlaneSums];
     __shared__ double A[36], w[12];
     if (nblocks > 0) {
-        plane_fold_to(partials, nblocks, sums, res);
+        fold_to<kPlaneSums, 1>(partials, nblocks, sums, res);
     } else {
         if (threadIdx.x < kPlaneSums) res[threadIdx.x] = sums[threadIdx.x];
         __syncthreads();
@@ -201,34 +146,15 @@ __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__res
     if (!step || threadIdx.x != 0) return;
     if (!s->done) { // (a frozen iteration's sums are stale: its gate was not evaluated)
         const double K = res[kPlaneCount];
-        g->gate.K = (long long)K;
-        h_g->gate.K = (long long)K;
+        g->K = (long long)K;
+        h_g->K = (long long)K;
         int status = 0;
         double piv = 0.0;
         if (!(K >= 6.0)) status = kGateTooFew;
         else if (!plane_solve(res, A, w, &piv)) status = kPlaneDegenerate;
-        if (status) {
-            s->done = 1;
-            g->gate.status = status;
-            g->gate.fail_iter = s->iter;
-            g->min_pivot = piv;
-            h_g->gate.status = status;
-            h_g->gate.fail_iter = s->iter;
-            h_g->min_pivot = piv;
-            const int *src = (const int *)s;
-            int *dst = (int *)h_state;
-            for (size_t k = 0; k < sizeof(IterState) / sizeof(int); ++k) dst[k] = src[k];
-        }
+        if (status) kept_stop(s, g, h_g, h_state, status, piv);
     }
-    // the loop's bookkeeping, as horn_step_body does it (restated: that step's code stays as it is):
-    // the search's queue sizes into the statistics, then zeroed for the next search (always: the
-    // next search appends to these counters even after the loop has stopped)
-    const int qc[4] = {cnt[0], cnt[1], cnt[2], cnt[3]};
-    for (int k = 0; k < 4; ++k) cnt[k] = 0;
-    s->far_acc = 0;
-    s->queued2 = qc[2];
-    if (s->done) return;
-    for (int k = 0; k < 4; ++k) s->nn_counts[k] += qc[k];
+    if (!step_counters(cnt, s)) return; // (done: the search's counters only)
     // R = exp([omega]x) by Rodrigues: I + (sin th / th) W + (2 sin^2(th / 2) / th^2) W^2
     const double o0 = w[6], o1 = w[7], o2 = w[8];
     const double th2 = (o0 * o0 + o1 * o1) + o2 * o2;
@@ -261,43 +187,21 @@ __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__res
     }
 }
 
-// Modelled on gated_transform_kernel: every point moves, and the squared residual along the normal
-// is summed over the kept points (the gate's mask words).  The normal is gathered again through idx,
-// or streamed from the copy the moments stored (NST).  A no-op once *done.
-template <bool NST>
+// Every point moves, and the squared residual along the normal, gathered again through idx, is
+// summed over the kept points (kept_transform).
 __global__ __launch_bounds__(kBlock) void plane_transform_kernel(
     double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, const double *__restrict__ yx,
     const double *__restrict__ yy, const double *__restrict__ yz, int n, const Xform *__restrict__ xfd,
     const int *__restrict__ done, float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
-    const int *__restrict__ idx, const double4 *__restrict__ n4, const double4 *__restrict__ nst,
-    double *__restrict__ partials)
+    const int *__restrict__ idx, const double4 *__restrict__ n4, double *__restrict__ partials)
 {
-    __shared__ Xform sxf;
-    __shared__ int sdone;
-    if (threadIdx.x == 0) {
-        sdone = *done;
-        sxf = *xfd;
-    }
-    __syncthreads();
-    if (sdone) return;
-    const Xform xf = sxf;
-    double a[1] = {0.0};
-    const long long G = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += G) {
-        double q0, q1, q2;
-        transform_point(xf, px[i], py[i], pz[i], q0, q1, q2);
-        if ((mask[i >> 6] >> (i & 63)) & 1ull) {
-            const double4 nn = NST ? nst[i] : n4[idx[i]];
-            const double e0 = q0 - yx[i], e1 = q1 - yy[i], e2 = q2 - yz[i];
-            const double rn = (e0 * nn.x + e1 * nn.y) + e2 * nn.z;
-            a[0] += rn * rn;
-        }
-        px[i] = q0;
-        py[i] = q1;
-        pz[i] = q2;
-        if (p32) p32[i] = make_float4((float)(q0 - xf.c[0]), (float)(q1 - xf.c[1]), (float)(q2 - xf.c[2]), 0.0f);
-    }
-    block_sum_store<1>(a, partials + blockIdx.x);
+    kept_transform(px, py, pz, n, xfd, done, p32, mask, partials,
+                   [&](long long i, double q0, double q1, double q2) __attribute__((always_inline)) {
+                       const double4 nn = n4[idx[i]];
+                       const double e0 = q0 - yx[i], e1 = q1 - yy[i], e2 = q2 - yz[i];
+                       const double rn = (e0 * nn.x + e1 * nn.y) + e2 * nn.z;
+                       return rn * rn;
+                   });
 }
 
 } // namespace
@@ -310,40 +214,30 @@ void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t s
 
 void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
                           const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          const double c[3], unsigned long long *mask, double4 *nst, double *partials, hipStream_t st,
-                          const int *kpos, const double4 *m4kd, bool y_ready)
+                          const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                          const double4 *m4kd, bool y_ready)
 {
-    const int nb = red_blocks(n);
-#define ICP_PLANE_MOMENTS(YIN, NST)                                                                                    \
-    plane_moments_kernel<YIN, NST><<<nb, kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], \
-                                                          c[2], mask, nst, partials, kpos, m4kd)
-    if (y_ready) {
-        if (nst) ICP_PLANE_MOMENTS(true, true);
-        else ICP_PLANE_MOMENTS(true, false);
-    } else {
-        if (nst) ICP_PLANE_MOMENTS(false, true);
-        else ICP_PLANE_MOMENTS(false, false);
-    }
-#undef ICP_PLANE_MOMENTS
+    if (y_ready)
+        plane_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
+                                                                     c[1], c[2], mask, partials, kpos, m4kd);
+    else
+        plane_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
+                                                                      c[1], c[2], mask, partials, kpos, m4kd);
 }
 
 void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, PlaneState *plane, PlaneState *h_plane, IterState *h_state, hipStream_t st)
+                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st)
 {
     plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
-                                             plane, h_plane, h_state);
+                                             gate, h_gate, h_state);
 }
 
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                             int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            const int *idx, const double4 *n4, const double4 *nst, double *partials, hipStream_t st)
+                            const int *idx, const double4 *n4, double *partials, hipStream_t st)
 {
-    if (nst)
-        plane_transform_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx,
-                                                                       n4, nst, partials);
-    else
-        plane_transform_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask,
-                                                                        idx, n4, nst, partials);
+    plane_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4,
+                                                             partials);
 }
 
 } // namespace icp

@@ -4,8 +4,8 @@
 //   icp_run -> run_loop: run_setup, then per iteration enqueue_canon (a scene in slot order: the
 //              canonical schedule) or enqueue_launches (every other scene: the launch loop),
 //              wait_one for the ring's oldest iteration, the drain and finish_run
-//   run_setup hands over to run_plane (icp_set_metric), run_gated (icp_set_max_distance) or
-//              run_persistent (the one-launch loops of small clouds) where they apply
+//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance) or run_persistent (the
+//              one-launch loops of small clouds) where they apply
 //   run_knobs / run_test_knobs: every environment switch of the run path (the table in icp_engine.h)
 #include <algorithm>
 #include <chrono>
@@ -93,8 +93,6 @@ RunKnobs read_run_knobs()
     k.iter_debug = !e ? 0 : atoi(e) == 2 ? 2 : 1;
     k.tail_split_err = getenv("ICP_TAIL_SPLIT_ERR") != nullptr;
     k.debug_policy = getenv("ICP_DEBUG_POLICY") != nullptr;
-    e = getenv("ICP_PLANE_NORMALS");
-    k.plane_stream = e && std::strcmp(e, "stream") == 0;
     return k;
 }
 
@@ -258,7 +256,7 @@ struct LoopRun {
     bool ar_timed[kRing] = {};
     int enqueued = 0, waited = 0, recorded = 0;
     bool stop = false;
-    int timing_stride = 0, timing_phase = 0; // (stride 0: no iteration is timed -- run_gated)
+    int timing_stride = 0, timing_phase = 0; // (stride 0: no iteration is timed -- run_kept)
 };
 
 // The O(N*M) kernel is timed (two events; on multi-rank runs two more around the
@@ -323,7 +321,7 @@ int wait_one(LoopRun &r)
 // What every loop does after search `it` is enqueued: the filter counters and path bits, the
 // correspondences' validity, the CPU rule's host fix-up, the index digest.  fused: the search was
 // a fused grid iteration's (the grid's, y written, no kd positions; its condition excludes the CPU
-// rule, so no fix-up).  slot: the ring slot whose all-reduce timing is cleared (-1: none, run_gated).
+// rule, so no fix-up).  slot: the ring slot whose all-reduce timing is cleared (-1: none, run_kept).
 int after_search(LoopRun &r, int it, bool fused, int slot)
 {
     icp_ctx *ctx = r.ctx;
@@ -651,50 +649,82 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     return finish_run(ctx, threshold, err_trace, res, wall0);
 }
 
-// a mapped K trace of at least max_iter entries (the gated and the point-to-plane loop)
-int grow_ktrace(icp_ctx *ctx, long long **h, long long **d, size_t *cap, int max_iter)
+// the mapped K trace of at least max_iter entries
+int grow_ktrace(icp_ctx *ctx, int max_iter)
 {
-    if (*cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
-    if (*h) HIPCHK(hipHostFree(*h)); // (the previous run ended with a sync)
-    *h = nullptr;
-    *cap = 0;
+    if (ctx->ktrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
+    if (ctx->h_ktrace) HIPCHK(hipHostFree(ctx->h_ktrace)); // (the previous run ended with a sync)
+    ctx->h_ktrace = nullptr;
+    ctx->ktrace_cap = 0;
     const size_t want = (size_t)std::max(max_iter, 64);
-    TRY(mapped_alloc(ctx, h, d, sizeof(long long) * want));
-    *cap = want;
+    TRY(mapped_alloc(ctx, &ctx->h_ktrace, &ctx->d_ktrace, sizeof(long long) * want));
+    ctx->ktrace_cap = want;
     return ICP_OK;
 }
 
-// icp_run with the max-correspondence-distance gate on (icp_set_max_distance; kernels in
-// icp_gated.hip).  run_setup_buffers has prepared the loop state, the mapped mirrors and the flag ring.
+// icp_run over the kept pairs: the max-correspondence-distance gate (icp_set_max_distance; kernels
+// in icp_gated.hip), the point-to-plane metric (icp_set_metric; icp_plane.hip), or both.
+// run_setup_buffers has prepared the loop state, the mapped mirrors and the flag ring.
 // Per iteration: the search as the launch loop's generic path runs it (seeded by the previous
-// correspondences, nothing carried from a transform), the gated moments (gate, mask, 18 sums), the
-// fold and the gated Horn step, the transform of every point with the kept points' residual, the
-// fold and the error step with N = K.  With ranks or a communicator the 18 sums and the residual
-// are each all-reduced before their step (two all-reduces an iteration; the error test is not
-// lagged).  The scene keeps the order it is in (file or slot); on one rank the host does not
-// synchronise inside an iteration.
-int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
-              std::chrono::steady_clock::time_point wall0)
+// correspondences, nothing carried from a transform); the moments (gate, mask, and the metric's
+// sums: 18 for Horn's closed form with N = K, 28 for the 6 x 6 normal equations); their fold and
+// the metric's step; the transform of every point with the kept points' residual (along the normal
+// for the plane metric); its fold and the error step with N = K.  With ranks or a communicator the
+// sums and the residual are each all-reduced before their step (two all-reduces an iteration; the
+// error test is not lagged).  The scene keeps the order it is in (file or slot); on one rank the
+// host does not synchronise inside an iteration.
+// The metrics differ in: the normals (plane), the least K (4 / 6, in the step kernels), D (the
+// plane metric runs ungated with D = +inf), the first iteration's pre-pass (point-to-point only:
+// the plane sums need no shifts), the launchers, and the closing messages.
+// A gated run leaves icp_get_inliers its last gate and K trace; an ungated one leaves the last
+// gated run's.
+int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
+             std::chrono::steady_clock::time_point wall0)
 {
+    const bool plane = ctx->metric == ICP_METRIC_POINT_TO_PLANE;
+    if (plane && !ctx->has_normals)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_run: the point-to-plane metric needs the model's normals (icp_set_model_normals)");
     if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
     const size_t n = ctx->scene.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
-    const double D = ctx->gate_dmax * ctx->gate_dmax; // (fp64, once)
+    const bool gated = ctx->gate_dmax > 0.0;
+    const double D = gated ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
+    const int width = plane ? kPlaneSums : kGateSums;
     const bool ranks = lag_run(ctx);
     const int nb = red_blocks(n);
-    TRY(grow(ctx, &ctx->gate_mask, &ctx->gate_mask_cap, (n + 63) / 64));
-    TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
-    TRY(grow(ctx, &ctx->gate_part, &ctx->gate_part_cap, (size_t)kRedMaxBlocksCap * kGateSums));
-    if (!ctx->gate_state) HIPCHK(hipMalloc((void **)&ctx->gate_state, sizeof(GateState)));
-    if (!ctx->h_gate) TRY(mapped_alloc(ctx, &ctx->h_gate, &ctx->d_gate_mirror, sizeof(GateState)));
-    TRY(grow_ktrace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
-    std::memset(ctx->h_gate, 0, sizeof(GateState));
-    HIPCHK(hipMemsetAsync(ctx->gate_state, 0, sizeof(GateState), ctx->st));
+    TRY(grow(ctx, &ctx->kept_mask, &ctx->kept_mask_cap, (n + 63) / 64));
+    if (gated) TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
+    TRY(grow(ctx, &ctx->kept_part, &ctx->kept_part_cap, (size_t)kRedMaxBlocksCap * kPlaneSums));
+    if (!ctx->kept_state) HIPCHK(hipMalloc((void **)&ctx->kept_state, sizeof(GateState)));
+    if (!ctx->h_kept) TRY(mapped_alloc(ctx, &ctx->h_kept, &ctx->d_kept_mirror, sizeof(GateState)));
+    TRY(grow_ktrace(ctx, max_iter));
+    std::memset(ctx->h_kept, 0, sizeof(GateState));
+    HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
-    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first iteration's pre-pass sums around the model's centre)
+    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c); // (the first gated iteration's pre-pass sums around the model's centre)
     if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
     const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
     ctx->stats.run_path_bits = 0;
+    // the metric's launches: the fold of the moments' partial rows and / or the step on the folded
+    // (all ranks') sums; the moments' pass with its fold
+    const auto step = [&](const double *part, int nblocks, bool do_step) {
+        if (plane)
+            launch_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
+                               ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st);
+        else
+            launch_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
+                              ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st);
+    };
+    const auto moments = [&](bool y_ready, bool do_step) {
+        const int *kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
+        if (plane)
+            launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c,
+                                 ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+        else
+            launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->kept_mask,
+                                 ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+        step(ctx->kept_part, nb, do_step);
+    };
     LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
     r.ctx = ctx;
     r.n = n;
@@ -707,172 +737,48 @@ int run_gated(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
             TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, nullptr, nullptr, false, &ws, &sd->done, ctx->scene_slot,
                                 false, nullptr));
             TRY(after_search(r, r.enqueued, false, -1));
-            // the first iteration's shifts: a pre-pass of the same moments around c gives the kept
-            // pairs' centroids (all ranks'), and the pass below sums around those -- around c a scan
-            // D from the model's centre cancels (D / sigma)^2 of the moments' precision.  Later
-            // iterations get their shifts from the Horn step before them.
-            const bool pre_pass = r.enqueued == 0;
+            // Point-to-point, the first iteration's shifts: a pre-pass of the same moments around c
+            // gives the kept pairs' centroids (all ranks'), and the pass below sums around those --
+            // around c a scan D from the model's centre cancels (D / sigma)^2 of the moments'
+            // precision.  Later iterations get their shifts from the Horn step before them.
+            const bool pre_pass = !plane && r.enqueued == 0;
             if (pre_pass) {
-                launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
-                                     ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
-                                     ctx->y_ready);
-                launch_gated_horn(ctx->gate_part, nb, ctx->sums, false, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st); // (the fold alone)
+                moments(ctx->y_ready, false); // (the fold alone)
                 LAUNCHCHK("gated_moments (first shifts)");
                 if (ranks) TRY(allreduce(ctx, ctx->sums, kGateSums));
                 launch_gated_first_shift(sd, ctx->sums, ctx->st);
                 LAUNCHCHK("gated_first_shift");
             }
-            // 2-4. the gate, the kept pairs' moments and count, the Horn step with N = K
+            // 2-4. the gate, the kept pairs' sums and count, the metric's step
             // (after the pre-pass y = m[idx] is stored: the pass streams it)
-            launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->gate_mask,
-                                 ctx->gate_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd,
-                                 ctx->y_ready || pre_pass);
-            launch_gated_horn(ctx->gate_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                              ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
-            LAUNCHCHK("gated_moments");
+            moments(ctx->y_ready || pre_pass, !ranks);
+            LAUNCHCHK(plane ? "plane_moments" : "gated_moments");
             if (ranks) {
-                TRY(allreduce(ctx, ctx->sums, kGateSums));
-                launch_gated_horn(nullptr, 0, ctx->sums, true, ctx->c, ctx->amb_count, sd, ctx->gate_state,
-                                  ctx->d_gate_mirror, ctx->d_iter_mirror, ctx->st);
-                LAUNCHCHK("gated_horn");
+                TRY(allreduce(ctx, ctx->sums, width));
+                step(nullptr, 0, true);
+                LAUNCHCHK(plane ? "plane_solve" : "gated_horn");
             }
             // 5-6. every point moves; the kept points' residual; err = (e + e) / K
-            launch_gated_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                   ctx->gate_mask, ctx->partials, ctx->st);
+            if (plane)
+                launch_plane_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                       ctx->kept_mask, ctx->idx, ctx->n4, ctx->partials, ctx->st);
+            else
+                launch_gated_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                       ctx->kept_mask, ctx->partials, ctx->st);
             if (!need_p32) ctx->p32_stale = true;
             const int sl = r.enqueued % kRing;
             r.slot_ticket[sl] = ++ctx->flag_ticket;
-            launch_gated_err(ctx->partials, nb, ctx->sums, !ranks, threshold, max_iter, ctx->err_trace_dev, sd,
-                             ctx->gate_state, ctx->d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror,
-                             ctx->d_trace, ctx->st);
-            LAUNCHCHK("gated_transform");
-            if (ranks) {
-                TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
-                launch_gated_err(nullptr, 0, ctx->sums, true, threshold, max_iter, ctx->err_trace_dev, sd, ctx->gate_state,
+            const auto err = [&](const double *part, int nblocks, bool do_step) {
+                launch_gated_err(part, nblocks, ctx->sums, do_step, threshold, max_iter, ctx->err_trace_dev, sd, ctx->kept_state,
                                  ctx->d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace,
                                  ctx->st);
-                LAUNCHCHK("gated_err");
-            }
-            ++r.enqueued;
-            continue;
-        }
-        TRY(wait_one(r));
-    }
-    // the last gate evaluated, as flags in the caller's point order (icp_get_inliers)
-    if (r.enqueued > 0) {
-        launch_gated_unpack(ctx->gate_mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
-        LAUNCHCHK("gated_unpack");
-    }
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the iteration queued behind the last one drains)
-    // nothing of a transform is carried to the next run: it starts from the correspondences alone
-    ctx->seedd_valid = false;
-    ctx->last_far = -1;
-    ctx->last_q2 = -1;
-    ctx->second_pass_items = 0;
-    if (r.enqueued > 0) {
-        ctx->gate_have = true;
-        ctx->gate_iters = ctx->h_iter->iter;
-    }
-    const GateState hg = *ctx->h_gate;
-    TRY(finish_run(ctx, threshold, err_trace, res, wall0));
-    if (hg.status == kGateTooFew)
-        return fail(ctx, ICP_E_TOO_FEW_POINTS,
-                    "icp_run: iteration " + std::to_string(hg.fail_iter) + " kept K = " + std::to_string(hg.K) +
-                        " pairs within the max correspondence distance; need at least 4");
-    return ICP_OK;
-}
-
-// icp_run with the point-to-plane metric (icp_set_metric; kernels in icp_plane.hip): run_gated's
-// loop -- the same search call, ring and bookkeeping -- with the plane moments (gate, mask, 28
-// sums), the fold and the 6 x 6 solve, and the transform with the residual along the normal; the
-// residual's fold and error step are the gated loop's.  No pre-pass: the sums need no shifts.  With
-// ranks or a communicator the 28 sums and the residual are each all-reduced before their step.
-// With the gate on (D finite) the run is the last gated run: it uses the gate's mask and K trace and
-// leaves icp_get_inliers its last gate; with it off (D = +inf) it keeps its own, and the last gated
-// run's stay.  It leaves the state run_gated leaves.
-int run_plane(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
-              std::chrono::steady_clock::time_point wall0)
-{
-    if (!ctx->has_normals)
-        return fail(ctx, ICP_E_NO_MODEL, "icp_run: the point-to-plane metric needs the model's normals (icp_set_model_normals)");
-    if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0);
-    const size_t n = ctx->scene.n;
-    DevCloud &P = ctx->scene, &Y = ctx->Y;
-    const bool gated = ctx->gate_dmax > 0.0;
-    const double D = gated ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
-    const bool ranks = lag_run(ctx);
-    const int nb = red_blocks(n);
-    unsigned long long *mask = nullptr;
-    long long *d_ktrace = nullptr;
-    if (gated) {
-        TRY(grow(ctx, &ctx->gate_mask, &ctx->gate_mask_cap, (n + 63) / 64));
-        TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
-        if (!ctx->h_gate) TRY(mapped_alloc(ctx, &ctx->h_gate, &ctx->d_gate_mirror, sizeof(GateState)));
-        TRY(grow_ktrace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
-        mask = ctx->gate_mask;
-        d_ktrace = ctx->d_ktrace;
-    } else {
-        TRY(grow(ctx, &ctx->plane_mask, &ctx->plane_mask_cap, (n + 63) / 64));
-        TRY(grow_ktrace(ctx, &ctx->h_pktrace, &ctx->d_pktrace, &ctx->pktrace_cap, max_iter));
-        mask = ctx->plane_mask;
-        d_ktrace = ctx->d_pktrace;
-    }
-    TRY(grow(ctx, &ctx->plane_part, &ctx->plane_part_cap, (size_t)kRedMaxBlocksCap * kPlaneSums));
-    double4 *nst = nullptr;
-    if (run_knobs().plane_stream) {
-        TRY(grow(ctx, &ctx->plane_nst, &ctx->plane_nst_cap, n));
-        nst = ctx->plane_nst;
-    }
-    if (!ctx->plane_state) HIPCHK(hipMalloc((void **)&ctx->plane_state, sizeof(PlaneState)));
-    if (!ctx->h_plane) TRY(mapped_alloc(ctx, &ctx->h_plane, &ctx->d_plane_mirror, sizeof(PlaneState)));
-    std::memset(ctx->h_plane, 0, sizeof(PlaneState));
-    HIPCHK(hipMemsetAsync(ctx->plane_state, 0, sizeof(PlaneState), ctx->st));
-    IterState *sd = ctx->iter_state;
-    launch_run_init(sd, ctx->amb_count, ctx->st, ctx->c);
-    if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
-    const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
-    ctx->stats.run_path_bits = 0;
-    LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
-    r.ctx = ctx;
-    r.n = n;
-    r.digest_order = digest_order;
-    while (!r.stop && r.waited < max_iter) {
-        if (r.enqueued < max_iter && r.enqueued - r.waited <= kAhead) {
-            // 1. correspondences (a search queued behind the iteration that froze the run returns at once)
-            const SeedState ws;
-            ctx->second_pass_items = 0;
-            TRY(nn_search_begin(ctx, P, n, ctx->seeds_valid, nullptr, nullptr, false, &ws, &sd->done, ctx->scene_slot,
-                                false, nullptr));
-            TRY(after_search(r, r.enqueued, false, -1));
-            // 2-6. the gate, the kept pairs' 28 sums, the solve
-            launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c, mask, nst,
-                                 ctx->plane_part, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
-            launch_plane_solve(ctx->plane_part, nb, ctx->sums, !ranks, ctx->c, ctx->amb_count, sd, ctx->plane_state,
-                               ctx->d_plane_mirror, ctx->d_iter_mirror, ctx->st);
-            LAUNCHCHK("plane_moments");
-            if (ranks) {
-                TRY(allreduce(ctx, ctx->sums, kPlaneSums));
-                launch_plane_solve(nullptr, 0, ctx->sums, true, ctx->c, ctx->amb_count, sd, ctx->plane_state,
-                                   ctx->d_plane_mirror, ctx->d_iter_mirror, ctx->st);
-                LAUNCHCHK("plane_solve");
-            }
-            // 7. every point moves; the kept points' residual along the normal; err = (e + e) / K
-            launch_plane_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr, mask,
-                                   ctx->idx, ctx->n4, nst, ctx->partials, ctx->st);
-            if (!need_p32) ctx->p32_stale = true;
-            const int sl = r.enqueued % kRing;
-            r.slot_ticket[sl] = ++ctx->flag_ticket;
-            launch_gated_err(ctx->partials, nb, ctx->sums, !ranks, threshold, max_iter, ctx->err_trace_dev, sd,
-                             &ctx->plane_state->gate, d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror,
-                             ctx->d_trace, ctx->st);
-            LAUNCHCHK("plane_transform");
+            };
+            err(ctx->partials, nb, !ranks);
+            LAUNCHCHK(plane ? "plane_transform" : "gated_transform");
             if (ranks) {
                 TRY(allreduce(ctx, ctx->sums + kSumErr, 1));
-                launch_gated_err(nullptr, 0, ctx->sums, true, threshold, max_iter, ctx->err_trace_dev, sd,
-                                 &ctx->plane_state->gate, d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl],
-                                 ctx->d_iter_mirror, ctx->d_trace, ctx->st);
-                LAUNCHCHK("plane_err");
+                err(nullptr, 0, true);
+                LAUNCHCHK(plane ? "plane_err" : "gated_err");
             }
             ++r.enqueued;
             continue;
@@ -881,7 +787,7 @@ int run_plane(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
     }
     // with the gate on: the last gate evaluated, as flags in the caller's point order (icp_get_inliers)
     if (gated && r.enqueued > 0) {
-        launch_gated_unpack(mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
+        launch_gated_unpack(ctx->kept_mask, digest_order, (int)n, ctx->gate_flags, ctx->st);
         LAUNCHCHK("gated_unpack");
     }
     HIPCHK(hipStreamSynchronize(ctx->st)); // (the iteration queued behind the last one drains)
@@ -890,24 +796,25 @@ int run_plane(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
     ctx->last_far = -1;
     ctx->last_q2 = -1;
     ctx->second_pass_items = 0;
-    const PlaneState hp = *ctx->h_plane;
-    if (gated && r.enqueued > 0) {
-        *ctx->h_gate = hp.gate;
+    const GateState hk = *ctx->h_kept;
+    if (gated && r.enqueued > 0) { // (the mapped buffers are the next run's, gated or not)
         ctx->gate_have = true;
-        ctx->gate_iters = ctx->h_iter->iter;
+        ctx->gate_K = hk.K;
+        ctx->gate_ktrace.assign(ctx->h_ktrace, ctx->h_ktrace + ctx->h_iter->iter);
     }
     TRY(finish_run(ctx, threshold, err_trace, res, wall0));
-    if (hp.gate.status == kGateTooFew)
+    if (hk.status == kGateTooFew)
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
-                    "icp_run: iteration " + std::to_string(hp.gate.fail_iter) + " kept K = " + std::to_string(hp.gate.K) +
-                        " pairs; the point-to-plane metric needs at least 6");
-    if (hp.gate.status == kPlaneDegenerate) {
+                    "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
+                        (plane ? " pairs; the point-to-plane metric needs at least 6"
+                               : " pairs within the max correspondence distance; need at least 4"));
+    if (hk.status == kPlaneDegenerate) {
         char piv[32];
-        std::snprintf(piv, sizeof(piv), "%.3g", hp.min_pivot);
+        std::snprintf(piv, sizeof(piv), "%.3g", hk.min_pivot);
         return fail(ctx, ICP_E_DEGENERATE,
-                    "icp_run: iteration " + std::to_string(hp.gate.fail_iter) +
+                    "icp_run: iteration " + std::to_string(hk.fail_iter) +
                         " has a degenerate point-to-plane system (smallest pivot " + piv + ", K = " +
-                        std::to_string(hp.gate.K) + ")");
+                        std::to_string(hk.K) + ")");
     }
     return ICP_OK;
 }
@@ -915,7 +822,7 @@ int run_plane(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, i
 // ---- the set-up ------------------------------------------------------------------------
 
 // The argument checks, the loop state, the mapped mirrors and the flag ring, the seed arguments,
-// the timing events and the scene's fp32 copy: what every loop of icp_run needs (run_gated and
+// the timing events and the scene's fp32 copy: what every loop of icp_run needs (run_kept and
 // run_persistent too)
 int run_setup_buffers(LoopRun &r)
 {
@@ -1177,7 +1084,7 @@ int run_setup_canon(LoopRun &r)
     return ICP_OK;
 }
 
-// Everything before the loop.  *handed: the run was another loop's (run_gated, run_persistent) and
+// Everything before the loop.  *handed: the run was another loop's (run_kept, run_persistent) and
 // is over, with the returned code.
 int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res,
               bool no_tail, bool *handed)
@@ -1187,11 +1094,10 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     r.threshold = threshold;
     TRY(run_setup_buffers(r));
     *handed = true;
-    // icp_set_metric: the point-to-plane loop, gated or not (as the gate: never the one-launch kernels)
-    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE)
-        return run_plane(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
-    // icp_set_max_distance: the gated loop (never the one-launch kernels or the fused iterations)
-    if (ctx->gate_dmax > 0.0) return run_gated(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
+    // icp_set_metric, icp_set_max_distance: the kept-pairs loop (never the one-launch kernels or the
+    // fused iterations)
+    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0)
+        return run_kept(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     {
         size_t lds = 0;
         bool mid = false;

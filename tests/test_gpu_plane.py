@@ -250,6 +250,56 @@ def test_point_to_point_run_after_a_plane_one(icp_lib, oracle):
     np.testing.assert_array_equal(np.array(res_a.R), np.array(res_b.R))
 
 
+def test_last_gate_survives_an_ungated_plane_run(icp_lib, oracle):
+    """The gated and the plane loop share their run-scoped buffers (mask, state, K trace); what
+    inliers() and inlier_trace() report is the last gated run's all the same: unchanged by an
+    ungated plane run on the same scene, replaced by the next gated run, dropped by set_scene.
+
+    The ungated plane run pairs the quarter of this scene that lies 4 away as well, and its three
+    iterations throw the scene off the model: every point ends more than 5.5 from it (plane_ref on
+    the CPU: err 1.5, 5.4, 2.7), so the gated plane run that follows on that scene keeps K = 0 pairs
+    at iteration 0 and stops -- that stop is what the getters then report.  A gated plane run that
+    records its iterations comes after a set_scene: its K are the reference's."""
+    amd = icp_lib
+    m, nrm, p, dmax, r = P.reference(oracle, ("gate", 4097, 0.08))
+    with amd.Context() as ctx:
+        ctx.set_model(m)
+        ctx.set_model_normals(nrm)
+        ctx.set_scene(p)
+        ctx.set_max_distance(dmax)
+        res, _errs = ctx.run(4, -1.0)  # 1. gated, point-to-point
+        mask1, k1 = ctx.inliers()
+        trace1 = ctx.inlier_trace()
+        print("K", list(trace1))
+        assert res.iterations == 4 and trace1.size == 4 and mask1.sum() == k1 == trace1[-1] and 4 <= k1 < p.shape[0]
+        ctx.set_max_distance(0.0)  # 2. ungated, point-to-plane, no set_scene: every pair kept, nothing reported
+        ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+        res, _errs = ctx.run(3, -1.0)
+        assert res.iterations == 3
+        mask2, k2 = ctx.inliers()
+        np.testing.assert_array_equal(mask2, mask1)
+        assert k2 == k1
+        np.testing.assert_array_equal(ctx.inlier_trace(), trace1)
+        ctx.set_max_distance(dmax)  # 3. gated, point-to-plane, the scene where it is: this run's stop
+        with pytest.raises(amd.ICPError) as ei:
+            ctx.run(3, -1.0)
+        assert ei.value.code == amd.ICP_E_TOO_FEW_POINTS and "iteration 0" in str(ei.value) and "K = 0" in str(ei.value)
+        mask3, k3 = ctx.inliers()
+        assert k3 == 0 and not mask3.any() and ctx.inlier_trace().size == 0
+        ctx.set_scene(p)  # ... and from the scene as given: this run's three iterations
+        res, _errs = ctx.run(3, -1.0)
+        mask3, k3 = ctx.inliers()
+        trace3 = ctx.inlier_trace()
+        print("K", list(trace3))
+        assert res.iterations == 3 and list(trace3) == r["K"][:3]
+        assert mask3.sum() == k3 == trace3[-1] and 6 <= k3 < p.shape[0]
+        ctx.set_scene(p)  # 4. a new scene: no gated run since
+        for getter in (ctx.inliers, ctx.inlier_trace):
+            with pytest.raises(amd.ICPError) as ei:
+                getter()
+            assert ei.value.code == amd.ICP_E_NO_MODEL
+
+
 # 8. a scene in slot order, correspondences with kd positions
 def test_plane_run_on_a_scene_in_slot_order(icp_lib):
     """Two point-to-point iterations at 65,536 points leave the scene in slot order and the bundle

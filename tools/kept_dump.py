@@ -1,0 +1,223 @@
+#!/usr/bin/env python3
+"""Everything the kept-pairs loop (icp_run under icp_set_max_distance and / or icp_set_metric)
+computes on the cases of tests/test_gpu_gated.py and tests/test_gpu_plane.py, dumped for a
+bit-for-bit comparison of two libraries (ICP_AMD_LIB picks the library; tools/build_ab.sh builds
+another revision's):
+
+  ICP_AMD_LIB=.../build_ab/REV/libicp_hip.so python3 tools/kept_dump.py --out a.npz
+  python3 tools/kept_dump.py --out b.npz
+  python3 tools/kept_dump.py --compare a.npz b.npz      (exit status 1 if anything differs)
+
+One process.  Per run: the return code and message, errs, the scene, s / R / t, the iterations, with
+a gate the K trace, the mask and k, and the integer counters of stats() (run_path_bits, the
+searches' queue counts).
+"""
+import argparse
+import os
+import sys
+import threading
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "iterative-closest-point_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import icp_amd as amd  # noqa: E402
+import datasets  # noqa: E402
+import gated_ref as G  # noqa: E402
+import plane_ref as P  # noqa: E402
+from test_gpu_gated import HostAllReduce  # noqa: E402
+
+OUT = {}
+
+
+def record(tag, ctx, iters, threshold=-1.0):
+    """One ctx.run and everything it left, under tag."""
+    rc, msg = 0, ""
+    res = errs = None
+    try:
+        res, errs = ctx.run(iters, threshold)
+    except amd.ICPError as e:
+        rc, msg = e.code, str(e)
+    OUT[tag + "/rc"] = np.array(rc)
+    OUT[tag + "/msg"] = np.array(msg)
+    OUT[tag + "/scene"] = ctx.get_scene()
+    if res is not None:
+        OUT[tag + "/errs"] = errs
+        OUT[tag + "/srt"] = np.array([res.s] + list(res.R) + list(res.t))
+        OUT[tag + "/iterations"] = np.array([res.iterations, res.converged])
+    try:
+        mask, k = ctx.inliers()
+        OUT[tag + "/mask"] = mask
+        OUT[tag + "/k"] = np.array(k)
+        OUT[tag + "/inlier_trace"] = ctx.inlier_trace()
+    except amd.ICPError as e:  # (no gated run since set_scene)
+        OUT[tag + "/inliers_rc"] = np.array(e.code)
+    st = ctx.stats()
+    OUT[tag + "/stats"] = np.array([int(v) & (2**64 - 1) for k, v in sorted(st.items()) if not isinstance(v, float)], dtype=np.uint64)
+
+
+def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, **ctx_args):
+    with amd.Context(0, mode, **ctx_args) as ctx:
+        if variant is not None:
+            ctx.set_nn_variant(variant)
+        ctx.set_model(m)
+        if nrm is not None:
+            ctx.set_model_normals(nrm)
+            ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+        ctx.set_scene(p)
+        if dmax:
+            ctx.set_max_distance(dmax)
+        record(tag, ctx, iters, threshold)
+
+
+def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0):
+    red = HostAllReduce(world)
+    errors = []
+
+    def worker(r):
+        try:
+            b, c = amd.shard_range(p.shape[0], r, world)
+            with amd.Context(0, 0, rank=r, world_size=world, host_allreduce=red.for_rank(r)) as ctx:
+                ctx.set_model(m)
+                if nrm is not None:
+                    ctx.set_model_normals(nrm)
+                    ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+                ctx.set_scene(p[b:b + c], np_total=p.shape[0])
+                ctx.set_max_distance(dmax)
+                record(f"{tag}/rank{r}", ctx, iters, threshold)
+        except Exception as e:
+            errors.append(e)
+            red.bar.abort()
+
+    th = [threading.Thread(target=worker, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=600)
+    if errors:
+        raise errors[0]
+
+
+def slot_scene(n=65536):
+    m, p = amd.synthetic_pair(n)
+    r = np.random.default_rng(5)
+    k = n // 4
+    p[r.choice(n, k, replace=False)] = np.array([4.0, 0, 0]) + r.uniform(-0.2, 0.2, size=(k, 3))
+    nrm = r.standard_normal((n, 3))
+    nrm /= np.linalg.norm(nrm, axis=1)[:, None]
+    return m, p, nrm
+
+
+def dump():
+    cow = [amd.load_matrix(datasets.path(k)) for k in ("cow_ref", "cow_tr2")]
+    clump = (cow[0], G.cow_clump(*cow), 0.25 * G.cow_ext(cow[0]))
+    # the gated suite
+    for n in G.SIZES:
+        m, p = G.synth(n, 100 + n, 0.25)
+        fresh(f"gated/size{n}", m, p, G.SIZES_DMAX, G.SIZES_ITERS)
+    for n, dmax in G.BITES:
+        m, p = G.synth(n, 100 + n, 0.25, sigma=0.05)
+        fresh(f"gated/bite{n}_{dmax}", m, p, dmax, G.BITES_ITERS)
+    fresh("gated/clump", *clump, 30, threshold=1e-5)
+    for world in (2, 3):
+        sharded(f"gated/world{world}", *clump, world, 30, threshold=1e-5)
+    fresh("gated/rccl1", *clump, 30, threshold=1e-5, mode=amd.NN_CERTIFIED, rank=0, world_size=1,
+          rccl_id=amd.rccl_unique_id())
+    m, p = G.synth(300, 1, 0.0)
+    fresh("gated/too_few", m, p + np.array([10.0, 0.0, 0.0]), 1.0, 5)
+    # the plane suite
+    for n in P.SIZES:
+        m, nrm, p, _src = P.synth(n, 100 + n, 0.01)
+        fresh(f"plane/size{n}", m, p, 0.0, P.SIZES_ITERS, nrm=nrm)
+    for n, dmax in P.GATES:
+        m, nrm, p = P.gate_case(n)
+        fresh(f"plane/gate{n}_{dmax}", m, p, dmax, P.GATES_ITERS, nrm=nrm)
+    gm, gn, gp = P.gate_case(4097)
+    sm, sn, sp, _src = P.synth(4097, 100 + 4097, 0.01)
+    for name, mode, variant in (("fp64", amd.NN_FP64, None), ("grid", amd.NN_CERTIFIED, amd.VARIANT_GRID)):
+        fresh(f"plane/{name}_gate_on", gm, gp, 0.08, P.GATES_ITERS, nrm=gn, mode=mode, variant=variant)
+        fresh(f"plane/{name}_gate_off", sm, sp, 0.0, P.SIZES_ITERS, nrm=sn, mode=mode, variant=variant)
+    for world in (2, 3):
+        sharded(f"plane/world{world}", gm, gp, 0.08, world, P.GATES_ITERS, nrm=gn)
+    fresh("plane/rccl1", gm, gp, 0.08, P.GATES_ITERS, nrm=gn, rank=0, world_size=1, rccl_id=amd.rccl_unique_id())
+    m, nrm, p = P.five()
+    fresh("plane/too_few", m, p, 0.0, 5, nrm=nrm)
+    m, nrm, p = P.planar()
+    fresh("plane/degenerate", m, p, 0.0, 5, nrm=nrm)
+    # a scene in slot order, each metric
+    m, p, nrm = slot_scene()
+    for name in ("gated", "plane"):
+        with amd.Context() as ctx:
+            ctx.set_model(m)
+            ctx.set_model_normals(nrm)
+            ctx.set_scene(p)
+            record(f"{name}/slot/before", ctx, 2)
+            if name == "plane":
+                ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+            ctx.set_max_distance(0.05)
+            record(f"{name}/slot/run", ctx, 3)
+    # one context: gated point-to-point, ungated plane, gated plane, a new scene
+    with amd.Context() as ctx:
+        ctx.set_model(gm)
+        ctx.set_model_normals(gn)
+        ctx.set_scene(gp)
+        ctx.set_max_distance(0.08)
+        record("sequence/1_gated_point", ctx, 4)
+        ctx.set_max_distance(0.0)
+        ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+        record("sequence/2_ungated_plane", ctx, 3)
+        ctx.set_max_distance(0.08)
+        record("sequence/3_gated_plane", ctx, 3)
+        ctx.set_scene(gp)
+        ctx.set_max_distance(0.0)
+        ctx.set_metric(amd.METRIC_POINT_TO_POINT)
+        record("sequence/4_new_scene_point", ctx, 3)
+    # a point-to-point run after a plane run
+    with amd.Context() as ctx:
+        ctx.set_model(cow[0])
+        nrm = np.random.default_rng(11).standard_normal(cow[0].shape)
+        ctx.set_model_normals(nrm / np.linalg.norm(nrm, axis=1)[:, None])
+        ctx.set_scene(cow[1])
+        ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+        record("after_plane/plane", ctx, 3)
+        ctx.set_metric(amd.METRIC_POINT_TO_POINT)
+        record("after_plane/point", ctx, 5)
+
+
+def compare(a_path, b_path):
+    a, b = np.load(a_path), np.load(b_path)
+    bad = sorted(set(a.files) ^ set(b.files))
+    for k in bad:
+        print("only in one dump:", k)
+    runs = set()
+    for k in sorted(set(a.files) & set(b.files)):
+        runs.add(k.rsplit("/", 1)[0])
+        if not (a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and
+                (np.array_equal(a[k], b[k]) if a[k].dtype.kind in "US" else a[k].tobytes() == b[k].tobytes())):
+            bad.append(k)
+            print("DIFFERS:", k)
+    stops = sorted(k for k in a.files if k.endswith("/rc") and int(a[k]) != 0)
+    print(f"{len(a.files)} arrays of {len(runs)} runs compared bit for bit: {len(bad)} differ")
+    for k in stops:
+        print(f"  {k[:-3]}: rc {int(a[k])} in both: {str(a[k[:-3] + '/msg'])}")
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--compare", nargs=2, metavar=("A.npz", "B.npz"))
+    a = ap.parse_args()
+    if a.compare:
+        sys.exit(compare(*a.compare))
+    if not a.out:
+        ap.error("--out FILE.npz or --compare A.npz B.npz")
+    dump()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    np.savez(a.out, **OUT)
+    print(f"{len(OUT)} arrays of {len({k.rsplit('/', 1)[0] for k in OUT})} runs -> {a.out} ({amd.LIB_PATH})")
+
+
+if __name__ == "__main__":
+    main()

@@ -6,8 +6,7 @@ reaches (dmax = 1e6), so both run the same searches' cascade, the launch loop an
   python3 tools/plane_probe.py [--n 1048576] [--iters 8] [--reps 5] [--only gated|plane]
 
 The clouds are icp_synthetic_pair's, the normals seeded unit vectors (the metric's arithmetic does
-not care that they are not a surface's).  ICP_PLANE_NORMALS=stream selects the transform that
-streams the normals the moments stored.  Under `rocprofv3 --kernel-trace --stats` (with --only) the
+not care that they are not a surface's).  Under `rocprofv3 --kernel-trace --stats` (with --only) the
 kernels' own times are in the trace; the stated algorithmic bytes per point are printed here.
 """
 import argparse
@@ -25,10 +24,8 @@ import icp_amd as amd  # noqa: E402
 BYTES = {
     "gated_moments_kernel": 24 + 4 + 32 + 24,             # p, idx, y gather, y store
     "gated_transform_kernel": 24 + 24 + 24,               # p, y, p store
-    "plane_moments_kernel (gather)": 24 + 4 + 32 + 24 + 32,     # ... + the normal's gather
-    "plane_transform_kernel (gather)": 24 + 24 + 4 + 32 + 24,   # p, y, idx, normal gather, p store
-    "plane_moments_kernel (stream)": 24 + 4 + 32 + 24 + 32 + 32,  # ... + the normal's store by point
-    "plane_transform_kernel (stream)": 24 + 24 + 32 + 24,         # p, y, normal stream, p store
+    "plane_moments_kernel": 24 + 4 + 32 + 24 + 32,        # ... + the normal's gather
+    "plane_transform_kernel": 24 + 24 + 4 + 32 + 24,      # p, y, idx, normal gather, p store
 }
 
 
@@ -42,8 +39,7 @@ def main():
     m, p = amd.synthetic_pair(a.n)
     nrm = np.random.default_rng(7).standard_normal((a.n, 3))
     nrm /= np.linalg.norm(nrm, axis=1)[:, None]
-    form = "stream" if os.environ.get("ICP_PLANE_NORMALS") == "stream" else "gather"
-    print(f"n = nm = {a.n}, {a.iters} iterations a run, normals: {form}")
+    print(f"n = nm = {a.n}, {a.iters} iterations a run")
     for k, v in BYTES.items():
         print(f"  algorithmic bytes a launch, {k}: {v} B x n = {v * a.n / 1e6:.1f} MB")
     modes = [a.only] if a.only else ["gated", "plane"]
