@@ -282,6 +282,39 @@ int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm);
  * stream; valid until the call returns); its values are not checked for finiteness. */
 int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm);
 
+/* ---- normals estimated from the model itself: grid k-NN and PCA ------------ */
+/* The k nearest model points of every point of the resident model, searched over the model's grid.
+ * 1. Neighbour set.  With d = m_j - m_i and d2 = (dx*dx + dy*dy) + dz*dz in fp64 exactly as written,
+ *    N_j is the first k model indices i in ascending (d2, i) order: ties go to the lower index, the
+ *    first-minimum rule extended to k.  The point itself is a candidate like any other (with
+ *    duplicate points it need not come first).  Row j of idx (host, nm x k) is N_j in that order;
+ *    d2 (nullable, host, nm x k) the matching distances.
+ * icp_estimate_model_normals makes the normals of the resident model from those neighbourhoods:
+ * 2. Covariance, two passes in the order of N_j: mu = (sum m_i) / k, C = sum (m_i - mu)(m_i - mu)^T
+ *    (six entries, fp64, the difference taken before any product).  The order is fixed, so two calls,
+ *    and every rank of a job (the model is replicated; there is no communication), give the same bits.
+ * 3. Normal.  With l0 <= l1 <= l2 the eigenvalues of C (cyclic Jacobi, fp64, a fixed number of
+ *    sweeps), the direction is undetermined when !(l2 > 0) or l1 - l0 <= 1e-12 * l2 (all points
+ *    equal, collinear neighbours, a neighbourhood symmetric about an axis): the normal is then
+ *    (0, 0, 0) -- icp_run's point-to-plane metric gives such a point's pairs no weight -- and the
+ *    point is counted in *degenerate (nullable).  The 1e-12 is a condition, not a measurement: below
+ *    it the eigenvector has lost 12 of fp64's 16 digits.  Otherwise the normal is the unit
+ *    eigenvector of l0.
+ * 4. Sign.  With a viewpoint v (nullable, 3 doubles): flipped so that n . (v - m_j) >= 0; without:
+ *    so that its component of largest magnitude is positive (ties: the lowest axis).  The sign is
+ *    immaterial to icp_run: a_j a_j^T and a_j r_j are even in n.
+ * 5. The normals become the context's, exactly as icp_set_model_normals_device leaves them: every
+ *    icp_set_model* call that changes the model drops them, icp_ensure_model keeps them when it did
+ *    not upload.  The metric setting is not touched, and nothing else a run depends on changes: an
+ *    icp_run after an estimate is bit-identical to that run on a fresh context.
+ * Errors: ICP_E_NO_MODEL without a model; ICP_E_ARG for a null required pointer, k < 3, k > 64,
+ * k > nm or a non-finite viewpoint (icp_last_error names the value; nothing has run, so earlier
+ * normals stay).  icp_get_model_normals copies the context's normals, however they were set, to a
+ * host array (3 x nm column-major like a cloud); ICP_E_NO_MODEL without a model or without normals. */
+int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2);
+int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate);
+int icp_get_model_normals(icp_ctx *ctx, double *n_xyz);
+
 /* ---- the ICP loop: GPU::ICP::find_corresponding_opti (src/GPU/gpu.cc:52-83) -- */
 /* Runs up to max_iter iterations on the resident clouds; stops after the iteration
  * whose err < threshold (pass threshold < 0 to run exactly max_iter iterations).

@@ -16,6 +16,10 @@
 //                      each iteration's alignment and error (partial overlap; default: none)
 //   --normals FILE     the model's normals, a CSV in the clouds' format with one row per model point:
 //                      selects the point-to-plane metric (combines with --max-dist; no scale)
+//   --estimate-normals K  the model's normals estimated from its own K nearest neighbours (3 <= K <= 64,
+//                      K <= the model's size; icp_estimate_model_normals): the same metric as --normals,
+//                      which it excludes
+//   --write-normals FILE  writes the normals the run used (either option's) in the clouds' format
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
 #include <cstdio>
@@ -42,6 +46,8 @@ int main(int argc, char **argv)
     const char *prog = std::strrchr(argv[0], '/') ? std::strrchr(argv[0], '/') + 1 : argv[0];
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
+        std::printf("       options: [--max-dist X] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
+                    "[--threshold X] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -49,7 +55,7 @@ int main(int argc, char **argv)
     int nn_mode = ICP_NN_CERTIFIED, device = 0;
     int rule = std::strcmp(prog, "icp") == 0 ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
     double threshold = 1e-5, max_dist = 0.0;
-    const char *out = "output.txt", *normals = nullptr;
+    const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -61,12 +67,34 @@ int main(int argc, char **argv)
         } else if (!std::strcmp(argv[a], "--threshold") && a + 1 < argc) threshold = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--max-dist") && a + 1 < argc) max_dist = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
+        else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
+        else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
         else {
             std::fprintf(stderr, "[error] unknown option %s\n", argv[a]);
             return -1;
         }
+    }
+
+    // the normals' options, checked before any file or device is touched
+    int est_k = 0;
+    if (estimate) {
+        char *end = nullptr;
+        const long v = std::strtol(estimate, &end, 10);
+        if (end == estimate || *end || v < 3 || v > 64) {
+            std::fprintf(stderr, "[error] --estimate-normals: K = %s is not an integer in [3, 64]\n", estimate);
+            return -1;
+        }
+        est_k = (int)v;
+        if (normals) {
+            std::fprintf(stderr, "[error] --estimate-normals and --normals exclude each other\n");
+            return -1;
+        }
+    }
+    if (write_normals && !normals && !estimate) {
+        std::fprintf(stderr, "[error] --write-normals needs --normals or --estimate-normals\n");
+        return -1;
     }
 
     size_t nm = 0, np = 0;
@@ -77,6 +105,11 @@ int main(int argc, char **argv)
     double *nrm = normals ? load_or_exit(normals, &nn) : nullptr;
     if (normals && nn != nm) {
         std::fprintf(stderr, "[error] --normals: %zu rows for a model of %zu points\n", nn, nm);
+        return -1;
+    }
+
+    if (estimate && (size_t)est_k > nm) {
+        std::fprintf(stderr, "[error] --estimate-normals: K = %d exceeds the model's %zu points\n", est_k, nm);
         return -1;
     }
 
@@ -110,6 +143,28 @@ int main(int argc, char **argv)
                     (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK)) {
         std::fprintf(stderr, "[error] --normals: %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
+    }
+    if (estimate) {
+        long long degenerate = 0;
+        if ((rc = icp_estimate_model_normals(ctx, est_k, nullptr, &degenerate)) != ICP_OK ||
+            (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK) {
+            std::fprintf(stderr, "[error] --estimate-normals: %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
+            return 3;
+        }
+        std::fprintf(stderr, "[normals] estimated from %d neighbours; %lld of %zu undetermined (zero)\n", est_k,
+                     degenerate, nm);
+    }
+    if (write_normals) {
+        double *nout = (double *)std::malloc(sizeof(double) * 3 * nm);
+        if (!nout || (rc = icp_get_model_normals(ctx, nout)) != ICP_OK) {
+            std::fprintf(stderr, "[error] --write-normals: %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
+            return 3;
+        }
+        if (icp_write_matrix(write_normals, nout, nm) != ICP_OK) {
+            std::fprintf(stderr, "[error] cannot write %s\n", write_normals);
+            return 2;
+        }
+        std::free(nout);
     }
     double *errs = (double *)std::calloc(max_iter > 0 ? (size_t)max_iter : 1, sizeof(double));
     icp_result res{};

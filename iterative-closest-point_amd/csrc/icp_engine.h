@@ -295,6 +295,12 @@ struct icp_ctx {
     double4 *n4 = nullptr;
     size_t n4_cap = 0;
     bool has_normals = false;
+    // icp_model_knn's nm x k lists and the estimator's counters (icp_normals.hip): scratch of those two
+    // calls alone, so that they leave everything a run reads as they found it
+    int *knn_idx = nullptr;
+    double *knn_d2 = nullptr;
+    unsigned long long *knn_counters = nullptr;
+    size_t knn_idx_cap = 0, knn_d2_cap = 0, knn_counters_cap = 0;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};

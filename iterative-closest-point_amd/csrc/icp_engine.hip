@@ -1262,7 +1262,7 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
-                    (void *)ctx->n4})
+                    (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
@@ -1398,6 +1398,83 @@ int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t n
     TRY(normals_args(ctx, n_xyz_dev, nm));
     HIPCHK(hipDeviceSynchronize()); // (as icp_set_model_device: after the work of any stream)
     return set_normals_from(ctx, n_xyz_dev, nm);
+}
+
+// the checks icp_model_knn and icp_estimate_model_normals share; nothing has run when they fail
+static int knn_args(icp_ctx *ctx, int k, const char *who)
+{
+    if (!ctx->has_model || !ctx->g_start || !ctx->g_pts || !ctx->m4)
+        return fail(ctx, ICP_E_NO_MODEL, std::string(who) + ": no model (icp_set_model)");
+    if (k < kKnnMinK || k > kKnnMaxK)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " is outside [" +
+                                        std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
+    if ((size_t)k > ctx->nm)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " exceeds the model's " +
+                                        std::to_string(ctx->nm) + " points");
+    HIPCHK(hipSetDevice(ctx->device));
+    return ICP_OK;
+}
+
+int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!idx) return fail(ctx, ICP_E_ARG, "icp_model_knn: idx is null");
+    TRY(knn_args(ctx, k, "icp_model_knn"));
+    const size_t cnt = ctx->nm * (size_t)k;
+    TRY(grow(ctx, &ctx->knn_idx, &ctx->knn_idx_cap, cnt));
+    if (d2) TRY(grow(ctx, &ctx->knn_d2, &ctx->knn_d2_cap, cnt));
+    launch_model_knn(grid_view(ctx), ctx->m4, (int)ctx->nm, k, grid_budget(ctx), ctx->knn_idx, d2 ? ctx->knn_d2 : nullptr,
+                     ctx->st);
+    LAUNCHCHK("model_knn");
+    HIPCHK(hipMemcpyAsync(idx, ctx->knn_idx, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, ctx->st));
+    if (d2) HIPCHK(hipMemcpyAsync(d2, ctx->knn_d2, sizeof(double) * cnt, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    return ICP_OK;
+}
+
+int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
+{
+    if (!ctx) return ICP_E_ARG;
+    TRY(knn_args(ctx, k, "icp_estimate_model_normals"));
+    if (viewpoint)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(viewpoint[a]))
+                return fail(ctx, ICP_E_ARG, "icp_estimate_model_normals: viewpoint[" + std::to_string(a) + "] = " +
+                                                std::to_string(viewpoint[a]) + " is not finite");
+    // ICP_NORMALS_DEBUG (set): the search's counts of this call, to stderr (tools/normals_probe.py)
+    static const bool debug = getenv("ICP_NORMALS_DEBUG") != nullptr;
+    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, ctx->nm));
+    TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
+    ctx->has_normals = false; // (until the new ones are complete)
+    HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
+    launch_model_normals(grid_view(ctx), ctx->m4, (int)ctx->nm, k, grid_budget(ctx), viewpoint, ctx->n4, ctx->knn_counters,
+                         debug, ctx->st);
+    LAUNCHCHK("model_normals");
+    unsigned long long c[kKnnCounters];
+    HIPCHK(hipMemcpyAsync(c, ctx->knn_counters, sizeof(c), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    ctx->has_normals = true;
+    if (degenerate) *degenerate = (long long)c[0];
+    if (debug)
+        std::fprintf(stderr, "[normals] nm=%zu k=%d degenerate=%llu second_scans=%llu full_scans=%llu candidates=%llu\n",
+                     ctx->nm, k, c[0], c[1], c[2], c[3]);
+    return ICP_OK;
+}
+
+int icp_get_model_normals(icp_ctx *ctx, double *n_xyz)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!n_xyz) return fail(ctx, ICP_E_ARG, "icp_get_model_normals: n_xyz is null");
+    if (!ctx->has_model || !ctx->has_normals || !ctx->n4)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_get_model_normals: the model has no normals (icp_set_model_normals, "
+                                         "icp_estimate_model_normals)");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    std::vector<double> rows(4 * ctx->nm);
+    HIPCHK(hipMemcpy(rows.data(), ctx->n4, sizeof(double) * 4 * ctx->nm, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < ctx->nm; ++j)
+        for (int a = 0; a < 3; ++a) n_xyz[3 * j + a] = rows[4 * j + a];
+    return ICP_OK;
 }
 
 // The model's AoS copy -> ctx->stage (pageable host memory: the runtime's staged copy).

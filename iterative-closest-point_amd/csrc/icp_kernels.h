@@ -826,6 +826,18 @@ void launch_plane_transform(double *px, double *py, double *pz, const double *yx
                             int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
                             const int *idx, const double4 *n4, double *partials, hipStream_t st);
 
+// ---- the model's k nearest neighbours and estimated normals (icp_normals.hip) -------------------
+constexpr int kKnnMinK = 3, kKnnMaxK = 64;
+constexpr int kKnnCounters = 4; // undetermined normals; debug: second scans, scans of every point, candidates
+// row j of idx / d2 (nullable) = the first k model indices in ascending (d2, index) order of model
+// point j's distances to every model point, over the model's grid (at most `budget` cells a box)
+void launch_model_knn(const GridView &gv, const double4 *m4, int nm, int k, int budget, int *idx, double *d2,
+                      hipStream_t st);
+// n4[j] = (the normal of model point j's k-neighbourhood, 0); viewpoint: nullable, 3 host doubles;
+// counters: kKnnCounters device words, zeroed by the caller ([1..3] counted with debug only)
+void launch_model_normals(const GridView &gv, const double4 *m4, int nm, int k, int budget, const double *viewpoint,
+                          double4 *n4, unsigned long long *counters, bool debug, hipStream_t st);
+
 // ---- the model's preparation on the device (icp_model.hip) ------------------------------------
 // out[10] = (sum x, sum y, sum z, lo xyz, hi xyz, non-finite coordinates) of n AoS points:
 // fixed-order two-stage reductions; scratch: model_stats_scratch_doubles()

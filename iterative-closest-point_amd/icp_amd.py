@@ -73,6 +73,7 @@ EXPORTED = [
     "icp_bundle_audit", "icp_sort_pairs", "icp_get_grid",
     "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
     "icp_set_metric", "icp_set_model_normals", "icp_set_model_normals_device",
+    "icp_model_knn", "icp_estimate_model_normals", "icp_get_model_normals",
 ]
 
 
@@ -189,6 +190,10 @@ def lib() -> C.CDLL:
         L.icp_set_metric.argtypes = [vp, C.c_int]
         L.icp_set_model_normals.argtypes = [vp, dp, sz]
         L.icp_set_model_normals_device.argtypes = [vp, vp, sz]
+    if hasattr(L, "icp_model_knn"):
+        L.icp_model_knn.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp]
+        L.icp_estimate_model_normals.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong)]
+        L.icp_get_model_normals.argtypes = [vp, dp]
     _lib = L
     return L
 
@@ -355,6 +360,7 @@ class Context:
     def set_model(self, m):
         m = _cloud(m)
         self._check(lib().icp_set_model(self._h, _dp(m), m.shape[0]))
+        self._nm = m.shape[0]
 
     def set_model_device(self, ptr: int, nm: int, stream=None):
         """icp_set_model_device: the model's AoS fp64 array already in device memory (a device
@@ -367,6 +373,7 @@ class Context:
             self._check(lib().icp_set_model_device(self._h, C.c_void_p(ptr), nm))
         else:
             self._check(lib().icp_set_model_device_stream(self._h, C.c_void_p(ptr), nm, C.c_void_p(stream)))
+        self._nm = nm
 
     def set_scene_device(self, ptr: int, np_local: int, np_total: int | None = None, stream=None):
         """icp_set_scene_device: the scene's AoS fp64 array already in device memory (stream: as
@@ -390,6 +397,7 @@ class Context:
         m = _cloud(m)
         up = C.c_int(0)
         self._check(lib().icp_ensure_model(self._h, _dp(m), m.shape[0], C.byref(up)))
+        self._nm = m.shape[0]
         return bool(up.value)
 
     def set_scene(self, p, np_total: int | None = None):
@@ -433,6 +441,34 @@ class Context:
     def set_model_normals_device(self, ptr: int, nm: int):
         """icp_set_model_normals_device: the normals' AoS fp64 array already in device memory."""
         self._check(lib().icp_set_model_normals_device(self._h, C.c_void_p(ptr), nm))
+
+    def model_knn(self, k: int, distances: bool = False):
+        """icp_model_knn: the k nearest model points of every model point, ascending (d2, index)
+        -> idx (nm, k) int32, or (idx, d2) with distances."""
+        k = int(k)
+        cnt = getattr(self, "_nm", 0) * k if 0 < k <= 64 else 0  # (a refused k writes nothing)
+        idx = np.empty(max(cnt, 1), dtype=np.int32)
+        d2 = np.empty(max(cnt, 1)) if distances else None
+        self._check(lib().icp_model_knn(self._h, k, idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        _dp(d2) if distances else None))
+        idx = idx[:cnt].reshape(-1, k)
+        return (idx, d2[:cnt].reshape(-1, k)) if distances else idx
+
+    def estimate_model_normals(self, k: int, viewpoint=None) -> int:
+        """icp_estimate_model_normals: the resident model's normals from its own k-neighbourhoods
+        (PCA; towards `viewpoint`, or the largest component positive); they become the context's
+        normals.  Returns how many points got a zero normal (direction undetermined)."""
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        deg = C.c_longlong(0)
+        self._check(lib().icp_estimate_model_normals(self._h, int(k), None if v is None else _dp(v), C.byref(deg)))
+        return int(deg.value)
+
+    def model_normals(self) -> np.ndarray:
+        """icp_get_model_normals: the context's normals (nm, 3), however they were set."""
+        nm = getattr(self, "_nm", 0)
+        out = np.empty((max(nm, 1), 3))
+        self._check(lib().icp_get_model_normals(self._h, _dp(out)))
+        return out[:nm]
 
     def inliers(self):
         """The last gate of the last gated run() -> (mask: bool (np_local,), caller's order; K over all ranks)."""
@@ -599,6 +635,7 @@ class ICP:
     allow_unequal: bool = False
     max_distance: float | None = None  # icp_set_max_distance (None: no gate)
     normals: np.ndarray | None = None  # the model's normals: the point-to-plane metric (None: point-to-point)
+    estimate_normals: int | None = None  # k: the normals estimated from the model (estimate_model_normals), same metric
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -606,6 +643,8 @@ class ICP:
     errors: np.ndarray = field(init=False)
 
     def __post_init__(self):
+        if self.normals is not None and self.estimate_normals is not None:
+            raise ValueError("ICP: give either normals or estimate_normals, not both")
         self.m = _cloud(self.m); self.p = _cloud(self.p)
         self.new_p = self.p.copy()
         self.r = np.eye(3); self.t = np.zeros(3)
@@ -617,6 +656,9 @@ class ICP:
         self._ctx.set_model(self.m)
         if self.normals is not None:
             self._ctx.set_model_normals(self.normals)
+            self._ctx.set_metric(METRIC_POINT_TO_PLANE)
+        if self.estimate_normals is not None:
+            self._ctx.estimate_model_normals(self.estimate_normals)
             self._ctx.set_metric(METRIC_POINT_TO_PLANE)
         self._ctx.set_scene(self.p)
 
