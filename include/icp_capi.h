@@ -282,6 +282,40 @@ int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm);
  * stream; valid until the call returns); its values are not checked for finiteness. */
 int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm);
 
+/* ---- robust weights: iteratively re-weighted least squares ------------------ */
+/* With a kind other than ICP_ROBUST_NONE, every pair the gate keeps enters the iteration's sums
+ * multiplied by a weight w_j of its residual at the current pose (PCL / Open3D robust kernels).
+ * With d = p_j - y_j the residual is r2_j = (dx*dx + dy*dy) + dz*dz, the gate's own d2, under
+ * ICP_METRIC_POINT_TO_POINT, and r2_j = r_j * r_j with r_j = (dx*nx + dy*ny) + dz*nz under
+ * ICP_METRIC_POINT_TO_PLANE.  With k in the clouds' units and k2 = k * k (fp64, once, on the host):
+ *   ICP_ROBUST_HUBER   w = r2 <= k2 ? 1 : k / sqrt(r2)
+ *   ICP_ROBUST_TUKEY   w = r2 < k2 ? (1 - r2/k2)^2 : 0
+ *   ICP_ROBUST_CAUCHY  w = 1 / (1 + r2/k2)
+ * in fp64 as written; a NaN residual weighs 0.  Each of the pair's terms t of the unweighted
+ * iteration (the 17 shifted moments, or the 21 + 6 entries of A and b) is summed as w * t, and two
+ * sums join the kept count K: W = sum w and K+ = #{w > 0}, over all ranks.  Point-to-point: Horn's
+ * closed form on the weighted sums with N = W (weighted centroids, S, and scale).  Point-to-plane:
+ * (sum w a a^T) x = -sum w a r, solved as the unweighted system.  An iteration with K or K+ below
+ * the metric's least count (4 / 6) stops the run before it changes anything with
+ * ICP_E_TOO_FEW_POINTS, and icp_last_error names the iteration, K and K+.  Everything else is the
+ * unweighted loop's: every point moves, err = (e + e) / K stays the kept pairs' UNWEIGHTED
+ * residual (Open3D's inlier_rmse; a threshold keeps its meaning), and icp_get_inliers /
+ * icp_get_inlier_trace keep reporting the gate.  A robust run always takes the launch loop
+ * (ICP_RUN_LAUNCHES), whatever icp_set_run_mode says; it combines with the gate (off: every pair is
+ * kept and weighted), both metrics, ranks and communicators.
+ * k must be finite and > 0 with k * k finite and > 0, and the kind one of the four: anything else
+ * is ICP_E_ARG and leaves the earlier setting.  With ICP_ROBUST_NONE (the default: icp_run exactly
+ * as without this call) k is ignored.  The setting survives icp_set_scene / icp_set_model. */
+#define ICP_ROBUST_NONE 0
+#define ICP_ROBUST_HUBER 1
+#define ICP_ROBUST_TUKEY 2
+#define ICP_ROBUST_CAUCHY 3
+int icp_set_robust(icp_ctx *ctx, int kind, double k);
+/* W and K+ of each recorded iteration of the last robust icp_run: writes min(cap, iterations)
+ * entries to each array that is not NULL and returns the number of recorded iterations (>= 0), or
+ * ICP_E_NO_MODEL if no robust run has happened since icp_set_scene. */
+int icp_get_robust_trace(icp_ctx *ctx, double *wsum_out, long long *active_out, size_t cap);
+
 /* ---- normals estimated from the model itself: grid k-NN and PCA ------------ */
 /* The k nearest model points of every point of the resident model, searched over the model's grid.
  * 1. Neighbour set.  With d = m_j - m_i and d2 = (dx*dx + dy*dy) + dz*dz in fp64 exactly as written,

@@ -19,6 +19,8 @@
 //   --estimate-normals K  the model's normals estimated from its own K nearest neighbours (3 <= K <= 64,
 //                      K <= the model's size; icp_estimate_model_normals): the same metric as --normals,
 //                      which it excludes
+//   --robust huber|tukey|cauchy  robust weights on the kept pairs (icp_set_robust): needs --robust-k
+//   --robust-k K       the weights' scale, in the clouds' units (> 0); needs --robust
 //   --write-normals FILE  writes the normals the run used (either option's) in the clouds' format
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
@@ -47,7 +49,7 @@ int main(int argc, char **argv)
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
         std::printf("       options: [--max-dist X] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
-                    "[--threshold X] [--out PATH]\n");
+                    "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -56,6 +58,7 @@ int main(int argc, char **argv)
     int rule = std::strcmp(prog, "icp") == 0 ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
     double threshold = 1e-5, max_dist = 0.0;
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
+    const char *robust = nullptr, *robust_k = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -69,6 +72,8 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
         else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
+        else if (!std::strcmp(argv[a], "--robust") && a + 1 < argc) robust = argv[++a];
+        else if (!std::strcmp(argv[a], "--robust-k") && a + 1 < argc) robust_k = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
         else {
@@ -95,6 +100,30 @@ int main(int argc, char **argv)
     if (write_normals && !normals && !estimate) {
         std::fprintf(stderr, "[error] --write-normals needs --normals or --estimate-normals\n");
         return -1;
+    }
+
+    // the robust weights' options: a kind and its scale come together
+    int robust_kind = ICP_ROBUST_NONE;
+    double robust_scale = 0.0;
+    if (robust || robust_k) {
+        if (!robust || !robust_k) {
+            std::fprintf(stderr, "[error] --robust and --robust-k need each other\n");
+            return -1;
+        }
+        robust_kind = !std::strcmp(robust, "huber")    ? ICP_ROBUST_HUBER
+                      : !std::strcmp(robust, "tukey")  ? ICP_ROBUST_TUKEY
+                      : !std::strcmp(robust, "cauchy") ? ICP_ROBUST_CAUCHY
+                                                       : ICP_ROBUST_NONE;
+        char *end = nullptr;
+        robust_scale = std::strtod(robust_k, &end);
+        if (robust_kind == ICP_ROBUST_NONE) {
+            std::fprintf(stderr, "[error] --robust: %s is not huber, tukey or cauchy\n", robust);
+            return -1;
+        }
+        if (end == robust_k || *end) {
+            std::fprintf(stderr, "[error] --robust-k: %s is not a number\n", robust_k);
+            return -1;
+        }
     }
 
     size_t nm = 0, np = 0;
@@ -133,6 +162,10 @@ int main(int argc, char **argv)
     icp_set_nn_rule(ctx, rule);
     if ((rc = icp_set_max_distance(ctx, max_dist)) != ICP_OK) {
         std::fprintf(stderr, "[error] --max-dist: %s\n", icp_strerror(rc));
+        return 3;
+    }
+    if ((rc = icp_set_robust(ctx, robust_kind, robust_scale)) != ICP_OK) {
+        std::fprintf(stderr, "[error] --robust-k: %s\n", icp_strerror(rc));
         return 3;
     }
     if ((rc = icp_set_model(ctx, m, nm)) != ICP_OK || (rc = icp_set_scene(ctx, p, np, np)) != ICP_OK) {

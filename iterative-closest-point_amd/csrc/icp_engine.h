@@ -271,8 +271,8 @@ struct icp_ctx {
 
     // The kept-pairs loop (run_kept: the max-correspondence-distance gate, icp_set_max_distance and
     // icp_gated.hip, and the point-to-plane metric, icp_set_metric and icp_plane.hip).  Scoped to one
-    // run, whichever metric: the mask words (the scene's order), the moments' partial rows (kPlaneSums a
-    // workgroup, the wider of the two), the device state with its mapped host mirror, the mapped K trace.
+    // run, whichever metric: the mask words (the scene's order), the moments' partial rows (kRobustPlaneSums
+    // a workgroup, the widest), the device state with its mapped host mirror, the mapped K trace.
     unsigned long long *kept_mask = nullptr;
     double *kept_part = nullptr;
     size_t kept_mask_cap = 0, kept_part_cap = 0;
@@ -288,6 +288,17 @@ struct icp_ctx {
     bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
     long long gate_K = 0;
     std::vector<long long> gate_ktrace;
+    // Robust weights (icp_set_robust): the kind (ICP_ROBUST_*; 0: off), k and k2 = k * k (fp64, once),
+    // the mapped W / K+ traces beside the K trace (grown with it), and what icp_get_robust_trace
+    // reports, saved at the end of the last robust run (dropped with the scene).
+    int robust_kind = 0;
+    double robust_k = 0.0, robust_k2 = 0.0;
+    double *h_wtrace = nullptr, *d_wtrace = nullptr;
+    long long *h_ptrace = nullptr, *d_ptrace = nullptr;
+    size_t rtrace_cap = 0;
+    bool robust_have = false;
+    std::vector<double> robust_wtrace;
+    std::vector<long long> robust_ptrace;
 
     // the point-to-plane metric: the model's normals as (nx, ny, nz, 0) by model index (dropped with
     // the model)

@@ -1271,6 +1271,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
     if (ctx->h_far) (void)hipHostFree(ctx->h_far);
     if (ctx->h_kept) (void)hipHostFree(ctx->h_kept);
     if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
+    if (ctx->h_wtrace) (void)hipHostFree(ctx->h_wtrace);
+    if (ctx->h_ptrace) (void)hipHostFree(ctx->h_ptrace);
     if (ctx->h_few) (void)hipHostFree(ctx->h_few);
     if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
     if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
@@ -1351,6 +1353,32 @@ int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap)
     const size_t k = std::min(cap, ctx->gate_ktrace.size());
     if (k) std::memcpy(counts_out, ctx->gate_ktrace.data(), sizeof(long long) * k);
     return (int)ctx->gate_ktrace.size();
+}
+
+int icp_set_robust(icp_ctx *ctx, int kind, double k)
+{
+    if (!ctx || kind < ICP_ROBUST_NONE || kind > ICP_ROBUST_CAUCHY) return ICP_E_ARG;
+    if (kind == ICP_ROBUST_NONE) { // (k is ignored)
+        ctx->robust_kind = kind;
+        return ICP_OK;
+    }
+    const double k2 = k * k; // (fp64, once: what every kernel of the run compares against)
+    if (!std::isfinite(k) || !(k > 0.0) || !std::isfinite(k2) || !(k2 > 0.0)) return ICP_E_ARG;
+    ctx->robust_kind = kind;
+    ctx->robust_k = k;
+    ctx->robust_k2 = k2;
+    return ICP_OK;
+}
+
+int icp_get_robust_trace(icp_ctx *ctx, double *wsum_out, long long *active_out, size_t cap)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!ctx->has_scene || !ctx->robust_have)
+        return fail(ctx, ICP_E_NO_MODEL, "no robust icp_run since icp_set_scene (icp_set_robust)");
+    const size_t k = std::min(cap, ctx->robust_wtrace.size());
+    if (k && wsum_out) std::memcpy(wsum_out, ctx->robust_wtrace.data(), sizeof(double) * k);
+    if (k && active_out) std::memcpy(active_out, ctx->robust_ptrace.data(), sizeof(long long) * k);
+    return (int)ctx->robust_wtrace.size();
 }
 
 int icp_set_metric(icp_ctx *ctx, int metric)
@@ -1830,6 +1858,7 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
     ctx->seeds_valid = false;
     ctx->seedd_valid = false;
     ctx->gate_have = false;
+    ctx->robust_have = false;
     ctx->q_order_src = nullptr; // new contents: a new query order
     ctx->scene_slot = slot;     // (else in the caller's order)
     ctx->scene_revert = false;

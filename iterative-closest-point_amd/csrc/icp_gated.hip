@@ -12,10 +12,14 @@
 // The loop over the pairs with the gate and its mask, the transform's body, the fold and the freeze
 // of a stopped run are icp_kept.h's, shared with the point-to-plane kernels (icp_plane.hip); the
 // residual's fold and error step here (launch_gated_err) and the mask's unpacking serve both.
+// With robust weights (icp_set_robust) the moments and the fold + step have weighted twins here
+// (robust_gated_moments_kernel, robust_gated_horn_kernel, robust_first_shift_kernel): each kept
+// pair's terms enter as w * t, w a function of the pair's d2, beside W = sum w and K+ = #{w > 0}.
 // Compiled with IEEE semantics like icp_step.hip (the error step's `err < threshold` and the
 // gate's `d2 <= D` must stay false for a NaN).
 #include <hip/hip_runtime.h>
 
+#include "icp_canon.h"
 #include "icp_device.h"
 #include "icp_fold.h"
 #include "icp_kept.h"
@@ -56,21 +60,59 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
     block_sum_store<kGateSums>(b, partials + (size_t)blockIdx.x * kGateSums);
 }
 
-// The fold of the moments' partial rows into sums[0..17] (nblocks > 0) and / or the gated Horn
+// gated_moments_kernel with robust weights (icp_set_robust): each kept pair's 17 terms (moment_leaves:
+// shifted_moment_terms' arithmetic) enter as a += w * t with w = robust_weight<KIND>(d2), d2 the
+// gate's own; the kept count stays the 18th sum, W = sum w and K+ = #{w > 0} are the 19th and 20th
+// (doubles: K+ exact below 2^53).  A weight of exactly 1.0 adds the unweighted kernel's bits.
+template <bool YIN, int KIND>
+__global__ __launch_bounds__(kBlock) void robust_gated_moments_kernel(
+    const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ px,
+    const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
+    double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
+    unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
+    const double4 *__restrict__ m4kd, double k, double k2)
+{
+    if (st->done != 0) return;
+    const double cp[3] = {st->shift_p[0], st->shift_p[1], st->shift_p[2]};
+    const double cy[3] = {st->shift_y[0], st->shift_y[1], st->shift_y[2]};
+    double a[kRobustGateSums];
+#pragma unroll
+    for (int j = 0; j < kRobustGateSums; ++j) a[j] = 0.0;
+    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+                         [&](long long, double q0, double q1, double q2, const double4 &m, double dx, double dy, double dz)
+                             __attribute__((always_inline)) {
+                                 const double w = robust_weight<KIND>((dx * dx + dy * dy) + dz * dz, k, k2);
+                                 double t[17];
+                                 moment_leaves(q0, q1, q2, m.x, m.y, m.z, cp, cy, t);
+#pragma unroll
+                                 for (int j = 0; j < 17; ++j) a[j] += w * t[j];
+                                 a[kGateCount] += 1.0;
+                                 a[kRobustGateW] += w;
+                                 a[kRobustGateKpos] += w > 0.0 ? 1.0 : 0.0;
+                             });
+    block_sum_store<kRobustGateSums>(a, partials + (size_t)blockIdx.x * kRobustGateSums);
+}
+
+// The fold of the moments' partial rows into sums[0..WIDTH) (nblocks > 0) and / or the gated Horn
 // step on sums (step; nblocks = 0: the sums as they are, all-reduced).  The step decides from the
 // global count K = sums[kGateCount], identical on every rank: K < 4 freezes the run with the
 // too-few status (kept_stop); else Horn's closed form over the kept pairs, N = K.
-__global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__restrict__ partials, int nblocks,
-                                                            double *__restrict__ sums, int step, double c0, double c1,
-                                                            double c2, int *__restrict__ cnt, IterState *__restrict__ s,
-                                                            GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                            IterState *__restrict__ h_state)
+// WIDTH = kRobustGateSums, the weighted rows: K+ < 4 freezes the run as well, N = W, and a solved
+// iteration's W and K+ join their mapped traces (the error step records that iteration's K and error).
+template <int WIDTH>
+__device__ __forceinline__ void gated_horn_body(const double *__restrict__ partials, int nblocks,
+                                                double *__restrict__ sums, int step, double c0, double c1, double c2,
+                                                int *__restrict__ cnt, IterState *__restrict__ s,
+                                                GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                                IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
+                                                long long *__restrict__ h_ptrace)
 {
-    __shared__ double res[kGateSums];
+    constexpr bool kRobust = WIDTH == kRobustGateSums;
+    __shared__ double res[WIDTH];
     if (nblocks > 0) {
-        fold_to<kGateSums>(partials, nblocks, sums, res);
+        fold_to<WIDTH>(partials, nblocks, sums, res);
     } else {
-        if (threadIdx.x < kGateSums) res[threadIdx.x] = sums[threadIdx.x];
+        if (threadIdx.x < WIDTH) res[threadIdx.x] = sums[threadIdx.x];
         __syncthreads();
     }
     if (!step || threadIdx.x != 0) return;
@@ -78,9 +120,40 @@ __global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__rest
     if (!s->done) { // (a frozen iteration's sums are stale: its gate was not evaluated)
         g->K = (long long)K;
         h_g->K = (long long)K;
-        if (!(K >= 4.0)) kept_stop(s, g, h_g, h_state, kGateTooFew, 0.0);
+        bool few = !(K >= 4.0);
+        if constexpr (kRobust) {
+            const double W = res[kRobustGateW], Kpos = res[kRobustGateKpos];
+            g->W = W;
+            g->Kpos = (long long)Kpos;
+            h_g->W = W;
+            h_g->Kpos = (long long)Kpos;
+            few = few || !(Kpos >= 4.0);
+            if (!few) {
+                h_wtrace[s->iter] = W;
+                h_ptrace[s->iter] = (long long)Kpos;
+            }
+        }
+        if (few) kept_stop(s, g, h_g, h_state, kGateTooFew, 0.0);
     }
-    horn_step_body(res, K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
+    horn_step_body(res, kRobust ? res[kRobustGateW] : K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
+}
+
+__global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__restrict__ partials, int nblocks,
+                                                            double *__restrict__ sums, int step, double c0, double c1,
+                                                            double c2, int *__restrict__ cnt, IterState *__restrict__ s,
+                                                            GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                                            IterState *__restrict__ h_state)
+{
+    gated_horn_body<kGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void robust_gated_horn_kernel(
+    const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
+    int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace)
+{
+    gated_horn_body<kRobustGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
+                                     h_ptrace);
 }
 
 // The first gated iteration's shifts, from a pre-pass of the moments around the model's centre c
@@ -95,6 +168,17 @@ __global__ void gated_first_shift_kernel(IterState *__restrict__ s, const double
     if (threadIdx.x >= 3 || s->done || !(K >= 1.0)) return;
     s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / K;
     s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / K;
+}
+
+// gated_first_shift_kernel for the weighted pre-pass (rows of 20): the weighted centroids,
+// c + sum w (p - c) / W and c + sum w (y - c) / W.  The weights do not depend on the shifts, so the
+// pass that follows computes the same ones.  W not > 0 leaves c (K+ = 0: the step stops the run).
+__global__ void robust_first_shift_kernel(IterState *__restrict__ s, const double *__restrict__ sums)
+{
+    const double W = sums[kRobustGateW];
+    if (threadIdx.x >= 3 || s->done || !(W > 0.0)) return;
+    s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / W;
+    s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / W;
 }
 
 // Modelled on the plain branch of transform_err_kernel: every point moves, the residual is
@@ -163,6 +247,44 @@ void launch_gated_horn(const double *partials, int nblocks, double *sums, bool s
 void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
 {
     gated_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums);
+}
+
+template <int KIND>
+static void robust_gated_moments_of(double k, double k2, const int *idx, const double4 *m4, const double *px,
+                                    const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
+                                    const IterState *st_dev, double D, unsigned long long *mask, double *partials,
+                                    hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready)
+{
+    if (y_ready)
+        robust_gated_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
+                                                                                  D, mask, partials, kpos, m4kd, k, k2);
+    else
+        robust_gated_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
+                                                                                   D, mask, partials, kpos, m4kd, k, k2);
+}
+
+void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
+                                 const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
+                                 const IterState *st_dev, double D, unsigned long long *mask, double *partials,
+                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready)
+{
+    const auto go = kind == kRobustHuber   ? robust_gated_moments_of<kRobustHuber>
+                    : kind == kRobustTukey ? robust_gated_moments_of<kRobustTukey>
+                                           : robust_gated_moments_of<kRobustCauchy>;
+    go(k, k2, idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask, partials, st, kpos, m4kd, y_ready);
+}
+
+void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
+                              int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
+                              double *h_wtrace, long long *h_ptrace, hipStream_t st)
+{
+    robust_gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
+                                                   st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace);
+}
+
+void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
+{
+    robust_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums);
 }
 
 void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,

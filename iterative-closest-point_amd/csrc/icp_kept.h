@@ -3,6 +3,7 @@
 // files, which hold each metric's own arithmetic and are compiled with IEEE semantics (`d2 <= D`
 // must stay false for a NaN):
 //   kept_pairs_pass   the moments kernels' loop: y, the gate, the mask word, a callable per kept pair
+//   robust_weight     a kept pair's weight from its squared residual (icp_set_robust)
 //   kept_transform    the transform kernels' body: every point moves, a callable gives a kept
 //                     point's squared residual
 //   fold_to           the fold of per-workgroup partial rows (reduce_kernel's tree)
@@ -51,6 +52,23 @@ __device__ __forceinline__ void kept_pairs_pass(const int *__restrict__ idx, con
         }
         const unsigned long long word = __ballot(keep);
         if (lane == 0) mask[i >> 6] = word;
+    }
+}
+
+// The robust weight of a kept pair from its squared residual r2 (icp_set_robust; k2 = k * k from the
+// host), fp64 as written.  KIND is a template parameter: the pairs' loop carries no switch.  Every
+// comparison is false for a NaN, so a NaN residual weighs 0; Huber is exactly 1.0 within k.
+template <int KIND>
+__device__ __forceinline__ double robust_weight(double r2, double k, double k2)
+{
+    if constexpr (KIND == kRobustHuber) {
+        return r2 <= k2 ? 1.0 : (r2 > k2 ? k / sqrt(r2) : 0.0);
+    } else if constexpr (KIND == kRobustTukey) {
+        const double u = 1.0 - r2 / k2;
+        return r2 < k2 ? u * u : 0.0;
+    } else {
+        static_assert(KIND == kRobustCauchy, "robust_weight: unknown kind");
+        return r2 == r2 ? 1.0 / (1.0 + r2 / k2) : 0.0;
     }
 }
 

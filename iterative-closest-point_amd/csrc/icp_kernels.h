@@ -773,6 +773,8 @@ struct GateState {
     int fail_iter;    // ... the iteration (0-based) that found it
     long long K;      // kept pairs, all ranks', of the last gate evaluated
     double min_pivot; // kPlaneDegenerate: the smallest Cholesky pivot met (0: a diagonal entry was not > 0)
+    double W;         // a robust run (icp_set_robust): the kept pairs' weights summed, all ranks', of that gate
+    long long Kpos;   // ... and the kept pairs with a weight > 0
 };
 // y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; mask word w = the ballot of points
 // 64 w ..; partial [17 shifted moment terms of the kept pairs, their count]; a no-op once done
@@ -825,6 +827,38 @@ void launch_plane_solve(const double *partials, int nblocks, double *sums, bool 
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                             int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
                             const int *idx, const double4 *n4, double *partials, hipStream_t st);
+
+// ---- robust weights on the kept pairs (icp_set_robust; kernels beside their unweighted twins) ----
+// A robust iteration multiplies each kept pair's terms in the moments by w(r2), r2 the pair's squared
+// residual at the current pose (point-to-point: the gate's d2; point-to-plane: (d . n)^2), and sums
+// W = sum w and K+ = #{w > 0} beside the kept count K: rows of 20 (17 terms, K, W, K+) and of 30
+// (27 sums, K, W, K+).  K keeps its slot, so the error step and the residual's fold are the
+// unweighted loop's.  The step solves with N = W (point-to-point) and stops like too-few on K+ too.
+constexpr int kRobustNone = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3; // (ICP_ROBUST_*)
+constexpr int kRobustGateSums = 20, kRobustGateW = 18, kRobustGateKpos = 19;
+constexpr int kRobustPlaneSums = 30, kRobustPlaneW = 28, kRobustPlaneKpos = 29;
+// launch_gated_moments with the weights: kind (kRobust*, not None), k and k2 = k * k; rows of 20
+void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
+                                 const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
+                                 const IterState *st_dev, double D, unsigned long long *mask, double *partials,
+                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready);
+// launch_gated_horn on rows of 20: K < 4 or K+ < 4 stops the run; else Horn's closed form on the
+// weighted sums with N = W, and h_wtrace[iter] = W, h_ptrace[iter] = K+ (mapped) for that iteration
+void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
+                              int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
+                              double *h_wtrace, long long *h_ptrace, hipStream_t st);
+// launch_gated_first_shift for the weighted pre-pass: the shifts += sum w (p - c) / W, sum w (y - c) / W
+void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
+// launch_plane_moments with the weights (r2 = r * r, r the residual along the normal); rows of 30
+void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
+                                 const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
+                                 double *yz, const IterState *st_dev, double D, const double c[3],
+                                 unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                                 const double4 *m4kd, bool y_ready);
+// launch_plane_solve on rows of 30: K < 6 or K+ < 6 stops the run; the same solve on the weighted sums
+void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
+                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
+                               double *h_wtrace, long long *h_ptrace, hipStream_t st);
 
 // ---- the model's k nearest neighbours and estimated normals (icp_normals.hip) -------------------
 constexpr int kKnnMinK = 3, kKnnMaxK = 64;

@@ -16,6 +16,9 @@
 // The loop over the pairs with the gate and its mask (one 64-bit word per wave of points), the
 // transform's body, the fold and the freeze of a stopped run are icp_kept.h's, shared with
 // icp_gated.hip; the residual's fold and error step are that file's launch_gated_err.
+// With robust weights (icp_set_robust) the moments and the fold + solve have weighted twins here
+// (robust_plane_moments_kernel, robust_plane_solve_kernel): A = sum w a a^T, b = -sum w a r with w a
+// function of r * r, beside W = sum w and K+ = #{w > 0}.
 // Compiled with IEEE semantics like icp_gated.hip (`d2 <= D`, `A_kk > 0` and `pivot > 1e-12` must
 // stay false for a NaN).
 #include <hip/hip_runtime.h>
@@ -78,6 +81,50 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     block_sum_store<kPlaneSums>(a, partials + (size_t)blockIdx.x * kPlaneSums);
 }
 
+// plane_moments_kernel with robust weights (icp_set_robust): each of the pair's 27 terms, computed
+// as there, enters as a += w * t with w = robust_weight<KIND>(r * r), r the residual along the
+// normal; the kept count stays the 28th sum, W = sum w and K+ = #{w > 0} are the 29th and 30th.
+template <bool YIN, int KIND>
+__global__ __launch_bounds__(kBlock) void robust_plane_moments_kernel(
+    const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
+    const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
+    double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
+    double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, double k, double k2)
+{
+    if (st->done != 0) return;
+    double a[kRobustPlaneSums];
+#pragma unroll
+    for (int j = 0; j < kRobustPlaneSums; ++j) a[j] = 0.0;
+    kept_pairs_pass<YIN>(
+        idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+        [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
+            __attribute__((always_inline)) {
+                const double4 nn = n4[idx[i]];
+                const double u0 = q0 - c0, u1 = q1 - c1, u2 = q2 - c2;
+                double v[6];
+                v[0] = u1 * nn.z - u2 * nn.y;
+                v[1] = u2 * nn.x - u0 * nn.z;
+                v[2] = u0 * nn.y - u1 * nn.x;
+                v[3] = nn.x;
+                v[4] = nn.y;
+                v[5] = nn.z;
+                const double r = (dx * nn.x + dy * nn.y) + dz * nn.z;
+                const double w = robust_weight<KIND>(r * r, k, k2);
+#pragma unroll
+                for (int row = 0; row < 6; ++row)
+#pragma unroll
+                    for (int col = row; col < 6; ++col)
+                        a[6 * row - row * (row - 1) / 2 + (col - row)] += w * (v[row] * v[col]);
+#pragma unroll
+                for (int row = 0; row < 6; ++row) a[kPlaneB + row] += w * (v[row] * r);
+                a[kPlaneCount] += 1.0;
+                a[kRobustPlaneW] += w;
+                a[kRobustPlaneKpos] += w > 0.0 ? 1.0 : 0.0;
+            });
+    block_sum_store<kRobustPlaneSums>(a, partials + (size_t)blockIdx.x * kRobustPlaneSums);
+}
+
 // The 6 x 6 solve of one thread.  sums: the 28 folded sums; A (36) and w (12: g, then x) are the
 // thread's arrays, in LDS so that no index turns into a private-memory access.  Returns whether the
 // system is regular; *piv = the smallest Cholesky pivot met (0 when a diagonal entry is not > 0).
@@ -125,22 +172,27 @@ __device__ __forceinline__ bool plane_solve(const double *sums, double *A, doubl
     return true;
 }
 
-// The fold of the moments' partial rows into sums[0..27] (nblocks > 0; one row in flight: 28 columns
+// The fold of the moments' partial rows into sums[0..WIDTH) (nblocks > 0; one row in flight: 28 columns
 // leave no registers for four) and / or the solve and step on sums (step; nblocks = 0: the sums as
 // they are, all-reduced).  The step decides from the global sums, identical on every rank: K < 6 or
 // a degenerate system freezes the run with its status (kept_stop); else s = 1, R, t of the solve.
-__global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__restrict__ partials, int nblocks,
-                                                             double *__restrict__ sums, int step, double c0, double c1,
-                                                             double c2, int *__restrict__ cnt, IterState *__restrict__ s,
-                                                             GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                             IterState *__restrict__ h_state)
+// WIDTH = kRobustPlaneSums, the weighted rows: K+ < 6 freezes the run as well, the system solved is
+// the weighted one, and a solved iteration's W and K+ join their mapped traces.
+template <int WIDTH>
+__device__ __forceinline__ void plane_solve_body(const double *__restrict__ partials, int nblocks,
+                                                 double *__restrict__ sums, int step, double c0, double c1, double c2,
+                                                 int *__restrict__ cnt, IterState *__restrict__ s,
+                                                 GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                                 IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
+                                                 long long *__restrict__ h_ptrace)
 {
-    __shared__ double res[kPlaneSums];
+    constexpr bool kRobust = WIDTH == kRobustPlaneSums;
+    __shared__ double res[WIDTH];
     __shared__ double A[36], w[12];
     if (nblocks > 0) {
-        fold_to<kPlaneSums, 1>(partials, nblocks, sums, res);
+        fold_to<WIDTH, 1>(partials, nblocks, sums, res);
     } else {
-        if (threadIdx.x < kPlaneSums) res[threadIdx.x] = sums[threadIdx.x];
+        if (threadIdx.x < WIDTH) res[threadIdx.x] = sums[threadIdx.x];
         __syncthreads();
     }
     if (!step || threadIdx.x != 0) return;
@@ -150,9 +202,24 @@ __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__res
         h_g->K = (long long)K;
         int status = 0;
         double piv = 0.0;
-        if (!(K >= 6.0)) status = kGateTooFew;
+        bool few = !(K >= 6.0);
+        if constexpr (kRobust) {
+            const double W = res[kRobustPlaneW], Kpos = res[kRobustPlaneKpos];
+            g->W = W;
+            g->Kpos = (long long)Kpos;
+            h_g->W = W;
+            h_g->Kpos = (long long)Kpos;
+            few = few || !(Kpos >= 6.0);
+        }
+        if (few) status = kGateTooFew;
         else if (!plane_solve(res, A, w, &piv)) status = kPlaneDegenerate;
         if (status) kept_stop(s, g, h_g, h_state, status, piv);
+        if constexpr (kRobust) {
+            if (!status) {
+                h_wtrace[s->iter] = res[kRobustPlaneW];
+                h_ptrace[s->iter] = (long long)res[kRobustPlaneKpos];
+            }
+        }
     }
     if (!step_counters(cnt, s)) return; // (done: the search's counters only)
     // R = exp([omega]x) by Rodrigues: I + (sin th / th) W + (2 sin^2(th / 2) / th^2) W^2
@@ -185,6 +252,24 @@ __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__res
         s->xf.t[k] = t;
         s->xf.c[k] = c[k];
     }
+}
+
+__global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__restrict__ partials, int nblocks,
+                                                             double *__restrict__ sums, int step, double c0, double c1,
+                                                             double c2, int *__restrict__ cnt, IterState *__restrict__ s,
+                                                             GateState *__restrict__ g, GateState *__restrict__ h_g,
+                                                             IterState *__restrict__ h_state)
+{
+    plane_solve_body<kPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void robust_plane_solve_kernel(
+    const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
+    int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace)
+{
+    plane_solve_body<kRobustPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
+                                       h_ptrace);
 }
 
 // Every point moves, and the squared residual along the normal, gathered again through idx, is
@@ -230,6 +315,41 @@ void launch_plane_solve(const double *partials, int nblocks, double *sums, bool 
 {
     plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
                                              gate, h_gate, h_state);
+}
+
+template <int KIND>
+static void robust_plane_moments_of(double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
+                                    const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
+                                    double *yz, const IterState *st_dev, double D, const double c[3],
+                                    unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                                    const double4 *m4kd, bool y_ready)
+{
+    if (y_ready)
+        robust_plane_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(
+            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2);
+    else
+        robust_plane_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(
+            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2);
+}
+
+void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
+                                 const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
+                                 double *yz, const IterState *st_dev, double D, const double c[3],
+                                 unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
+                                 const double4 *m4kd, bool y_ready)
+{
+    const auto go = kind == kRobustHuber   ? robust_plane_moments_of<kRobustHuber>
+                    : kind == kRobustTukey ? robust_plane_moments_of<kRobustTukey>
+                                           : robust_plane_moments_of<kRobustCauchy>;
+    go(k, k2, idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c, mask, partials, st, kpos, m4kd, y_ready);
+}
+
+void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
+                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
+                               double *h_wtrace, long long *h_ptrace, hipStream_t st)
+{
+    robust_plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
+                                                    st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace);
 }
 
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,

@@ -4,7 +4,7 @@
 //   icp_run -> run_loop: run_setup, then per iteration enqueue_canon (a scene in slot order: the
 //              canonical schedule) or enqueue_launches (every other scene: the launch loop),
 //              wait_one for the ring's oldest iteration, the drain and finish_run
-//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance) or run_persistent (the
+//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance, icp_set_robust) or run_persistent (the
 //              one-launch loops of small clouds) where they apply
 //   run_knobs / run_test_knobs: every environment switch of the run path (the table in icp_engine.h)
 #include <algorithm>
@@ -662,8 +662,25 @@ int grow_ktrace(icp_ctx *ctx, int max_iter)
     return ICP_OK;
 }
 
+// the mapped W and K+ traces of a robust run, of at least max_iter entries each
+int grow_rtrace(icp_ctx *ctx, int max_iter)
+{
+    if (ctx->rtrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
+    if (ctx->h_wtrace) HIPCHK(hipHostFree(ctx->h_wtrace)); // (the previous run ended with a sync)
+    ctx->h_wtrace = nullptr;
+    if (ctx->h_ptrace) HIPCHK(hipHostFree(ctx->h_ptrace));
+    ctx->h_ptrace = nullptr;
+    ctx->rtrace_cap = 0;
+    const size_t want = (size_t)std::max(max_iter, 64);
+    TRY(mapped_alloc(ctx, &ctx->h_wtrace, &ctx->d_wtrace, sizeof(double) * want));
+    TRY(mapped_alloc(ctx, &ctx->h_ptrace, &ctx->d_ptrace, sizeof(long long) * want));
+    ctx->rtrace_cap = want;
+    return ICP_OK;
+}
+
 // icp_run over the kept pairs: the max-correspondence-distance gate (icp_set_max_distance; kernels
-// in icp_gated.hip), the point-to-plane metric (icp_set_metric; icp_plane.hip), or both.
+// in icp_gated.hip), the point-to-plane metric (icp_set_metric; icp_plane.hip), robust weights
+// (icp_set_robust; both files), or any of them together.
 // run_setup_buffers has prepared the loop state, the mapped mirrors and the flag ring.
 // Per iteration: the search as the launch loop's generic path runs it (seeded by the previous
 // correspondences, nothing carried from a transform); the moments (gate, mask, and the metric's
@@ -678,6 +695,10 @@ int grow_ktrace(icp_ctx *ctx, int max_iter)
 // the plane sums need no shifts), the launchers, and the closing messages.
 // A gated run leaves icp_get_inliers its last gate and K trace; an ungated one leaves the last
 // gated run's.
+// With robust weights (icp_set_robust) the moments and the fold + step are the weighted kernels
+// (rows of 20 and 30: the sums, K, W = sum w, K+ = #{w > 0}; the pre-pass's shifts divide by W; the
+// step stops on K+ as on K and writes W and K+ to their mapped traces); the transform, the residual
+// and the error step, hence err = (e + e) / K, are the unweighted loop's.
 int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
              std::chrono::steady_clock::time_point wall0)
 {
@@ -689,15 +710,18 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     DevCloud &P = ctx->scene, &Y = ctx->Y;
     const bool gated = ctx->gate_dmax > 0.0;
     const double D = gated ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
-    const int width = plane ? kPlaneSums : kGateSums;
+    const int robust = ctx->robust_kind; // (ICP_ROBUST_*; 0: the unweighted kernels, as without the setting)
+    const double rk = ctx->robust_k, rk2 = ctx->robust_k2;
+    const int width = plane ? (robust ? kRobustPlaneSums : kPlaneSums) : (robust ? kRobustGateSums : kGateSums);
     const bool ranks = lag_run(ctx);
     const int nb = red_blocks(n);
     TRY(grow(ctx, &ctx->kept_mask, &ctx->kept_mask_cap, (n + 63) / 64));
     if (gated) TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
-    TRY(grow(ctx, &ctx->kept_part, &ctx->kept_part_cap, (size_t)kRedMaxBlocksCap * kPlaneSums));
+    TRY(grow(ctx, &ctx->kept_part, &ctx->kept_part_cap, (size_t)kRedMaxBlocksCap * kRobustPlaneSums));
     if (!ctx->kept_state) HIPCHK(hipMalloc((void **)&ctx->kept_state, sizeof(GateState)));
     if (!ctx->h_kept) TRY(mapped_alloc(ctx, &ctx->h_kept, &ctx->d_kept_mirror, sizeof(GateState)));
     TRY(grow_ktrace(ctx, max_iter));
+    if (robust) TRY(grow_rtrace(ctx, max_iter));
     std::memset(ctx->h_kept, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -708,7 +732,13 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     // the metric's launches: the fold of the moments' partial rows and / or the step on the folded
     // (all ranks') sums; the moments' pass with its fold
     const auto step = [&](const double *part, int nblocks, bool do_step) {
-        if (plane)
+        if (plane && robust)
+            launch_robust_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
+                                      ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st);
+        else if (robust)
+            launch_robust_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
+                                     ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st);
+        else if (plane)
             launch_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
                                ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st);
         else
@@ -717,7 +747,13 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     };
     const auto moments = [&](bool y_ready, bool do_step) {
         const int *kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
-        if (plane)
+        if (plane && robust)
+            launch_robust_plane_moments(robust, rk, rk2, ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd,
+                                        D, ctx->c, ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+        else if (robust)
+            launch_robust_gated_moments(robust, rk, rk2, ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D,
+                                        ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+        else if (plane)
             launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c,
                                  ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
         else
@@ -745,8 +781,9 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             if (pre_pass) {
                 moments(ctx->y_ready, false); // (the fold alone)
                 LAUNCHCHK("gated_moments (first shifts)");
-                if (ranks) TRY(allreduce(ctx, ctx->sums, kGateSums));
-                launch_gated_first_shift(sd, ctx->sums, ctx->st);
+                if (ranks) TRY(allreduce(ctx, ctx->sums, width));
+                if (robust) launch_robust_first_shift(sd, ctx->sums, ctx->st);
+                else launch_gated_first_shift(sd, ctx->sums, ctx->st);
                 LAUNCHCHK("gated_first_shift");
             }
             // 2-4. the gate, the kept pairs' sums and count, the metric's step
@@ -802,7 +839,17 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         ctx->gate_K = hk.K;
         ctx->gate_ktrace.assign(ctx->h_ktrace, ctx->h_ktrace + ctx->h_iter->iter);
     }
+    if (robust && r.enqueued > 0) { // (icp_get_robust_trace: the recorded iterations' W and K+)
+        ctx->robust_have = true;
+        ctx->robust_wtrace.assign(ctx->h_wtrace, ctx->h_wtrace + ctx->h_iter->iter);
+        ctx->robust_ptrace.assign(ctx->h_ptrace, ctx->h_ptrace + ctx->h_iter->iter);
+    }
     TRY(finish_run(ctx, threshold, err_trace, res, wall0));
+    if (hk.status == kGateTooFew && robust)
+        return fail(ctx, ICP_E_TOO_FEW_POINTS,
+                    "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
+                        " pairs, K+ = " + std::to_string(hk.Kpos) + " of them with a robust weight > 0; " +
+                        (plane ? "the point-to-plane metric needs at least 6 of both" : "need at least 4 of both"));
     if (hk.status == kGateTooFew)
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
@@ -1094,9 +1141,9 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     r.threshold = threshold;
     TRY(run_setup_buffers(r));
     *handed = true;
-    // icp_set_metric, icp_set_max_distance: the kept-pairs loop (never the one-launch kernels or the
+    // icp_set_metric, icp_set_max_distance, icp_set_robust: the kept-pairs loop (never the one-launch kernels or the
     // fused iterations)
-    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0)
+    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0 || ctx->robust_kind != 0)
         return run_kept(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     {
         size_t lds = 0;

@@ -55,6 +55,10 @@ RUN_LAUNCHES = 1
 RUN_PERSISTENT = 2
 METRIC_POINT_TO_POINT = 0  # icp_set_metric: Horn's closed form, scale included (the default)
 METRIC_POINT_TO_PLANE = 1  # the distance along the model's normals (set_model_normals), no scale
+ROBUST_NONE = 0    # icp_set_robust: every kept pair with weight 1 (the default)
+ROBUST_HUBER = 1   # w = 1 within k, k / |r| beyond
+ROBUST_TUKEY = 2   # w = (1 - r^2/k^2)^2 within k, 0 beyond
+ROBUST_CAUCHY = 3  # w = 1 / (1 + r^2/k^2)
 
 # every function include/icp_capi.h declares (checked by tests/test_capi.py)
 EXPORTED = [
@@ -74,6 +78,7 @@ EXPORTED = [
     "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
     "icp_set_metric", "icp_set_model_normals", "icp_set_model_normals_device",
     "icp_model_knn", "icp_estimate_model_normals", "icp_get_model_normals",
+    "icp_set_robust", "icp_get_robust_trace",
 ]
 
 
@@ -194,6 +199,9 @@ def lib() -> C.CDLL:
         L.icp_model_knn.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp]
         L.icp_estimate_model_normals.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong)]
         L.icp_get_model_normals.argtypes = [vp, dp]
+    if hasattr(L, "icp_set_robust"):
+        L.icp_set_robust.argtypes = [vp, C.c_int, C.c_double]
+        L.icp_get_robust_trace.argtypes = [vp, dp, C.POINTER(C.c_longlong), sz]
     _lib = L
     return L
 
@@ -488,6 +496,24 @@ class Context:
             self._check(rc)
         return out[:n]
 
+    def set_robust(self, kind: int, k: float = 0.0):
+        """icp_set_robust: run() weighs every kept pair by ROBUST_HUBER / ROBUST_TUKEY / ROBUST_CAUCHY of
+        its residual with the scale k (the clouds' units); ROBUST_NONE (k ignored): off."""
+        self._check(lib().icp_set_robust(self._h, int(kind), float(k)))
+
+    def robust_trace(self):
+        """Of each recorded iteration of the last robust run() -> (W: the kept pairs' weights summed
+        (float64), K+: the kept pairs with a weight > 0 (int64)), over all ranks."""
+        n = lib().icp_get_robust_trace(self._h, None, None, 0)
+        if n < 0:
+            self._check(n)
+        w = np.zeros(max(n, 1))
+        kpos = np.zeros(max(n, 1), dtype=np.int64)
+        rc = lib().icp_get_robust_trace(self._h, _dp(w), kpos.ctypes.data_as(C.POINTER(C.c_longlong)), n)
+        if rc < 0:
+            self._check(rc)
+        return w[:n], kpos[:n]
+
     def run(self, max_iter: int, threshold: float = 1e-5):
         errs = np.zeros(max(max_iter, 1))
         res = Result()
@@ -636,6 +662,7 @@ class ICP:
     max_distance: float | None = None  # icp_set_max_distance (None: no gate)
     normals: np.ndarray | None = None  # the model's normals: the point-to-plane metric (None: point-to-point)
     estimate_normals: int | None = None  # k: the normals estimated from the model (estimate_model_normals), same metric
+    robust: tuple | None = None  # (kind, k): icp_set_robust (None: every kept pair with weight 1)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -653,6 +680,8 @@ class ICP:
         self._ctx.set_allow_unequal(self.allow_unequal)
         if self.max_distance is not None:
             self._ctx.set_max_distance(self.max_distance)
+        if self.robust is not None:
+            self._ctx.set_robust(*self.robust)
         self._ctx.set_model(self.m)
         if self.normals is not None:
             self._ctx.set_model_normals(self.normals)
