@@ -349,6 +349,52 @@ int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2);
 int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate);
 int icp_get_model_normals(icp_ctx *ctx, double *n_xyz);
 
+/* ---- coarse-to-fine: the total transform, a pose for the scene, a voxel downsample -- */
+/* icp_get_transform: the similarity q = s R p + t (R row-major) that maps the scene as icp_set_scene*
+ * received it onto the resident scene now: every APPLIED iteration of every icp_run since then and
+ * every icp_transform_scene, composed as (s2, R2, t2) o (s1, R1, t1) = (s2 s1, R2 R1, s2 R2 t1 + t2)
+ * in fp64, each 3-term sum as ((a + b) + c); the first step is copied, so after one iteration it has
+ * icp_result's bits.  The identity after icp_set_scene*; s stays 1 under ICP_METRIC_POINT_TO_PLANE.
+ * The step of an iteration that stopped the run before it changed anything (ICP_E_TOO_FEW_POINTS,
+ * ICP_E_DEGENERATE) is not part of it.  The steps come from all-reduced sums, so every rank of a job
+ * reports the same bits.  ICP_E_NO_MODEL without a scene, ICP_E_ARG for a null pointer.
+ * icp_transform_scene: moves this rank's resident scene by q = sR p + t, with sR = s * R formed once
+ * on the host and q = ((sR0 p0 + sR1 p1) + sR2 p2) + t per row, the iterations' own arithmetic; R is
+ * used as given.  The transform is composed into the total, and the context is left exactly as
+ * icp_set_scene of the moved points would leave it (the correspondences, the gate's and the robust
+ * weights' reports are dropped; the scene is prepared again by the set-up's own passes): an icp_run
+ * after it is bit-identical to that run on a fresh context given icp_get_scene's points.
+ * ICP_E_ARG for a null pointer, a non-finite value or s <= 0; ICP_E_NO_MODEL without a scene. */
+int icp_get_transform(icp_ctx *ctx, double *s, double R[9], double t[3]);
+int icp_transform_scene(icp_ctx *ctx, double s, const double R[9], const double t[3]);
+/* One point per occupied cell of a cubic lattice of side `voxel`: the mean of the cell's points.
+ * 1. Cell.  With lo_a = origin ? origin[a] : min_i x_a, a point's cell per axis is
+ *    c_a = floor((x_a - lo_a) / voxel) in fp64 exactly as written (IEEE division, no reciprocal), and
+ *    g_a = 1 + max_i c_a.  Two clouds downsampled with the same origin share the lattice.
+ * 2. Key.  (c_z * g_y + c_y) * g_x + c_x, 64 bits.
+ * 3. Output.  Point v of xyz_out is the mean (sum x_i) / L_v of the L_v points of the v-th occupied cell
+ *    in ascending key order, count_out[v] (nullable) = L_v, *n_out the number of occupied cells.
+ *    xyz_out and count_out have room for n entries.
+ * 4. Order of the sum: a pure function of the input (no floating-point atomics; two calls give the
+ *    same bits, the host and the device form too).  A cell's points in input order are cut into
+ *    chunks of 1,024; in a chunk 64 partial sums start from +0 and take the points l, l + 64, ... in
+ *    order, and are combined by the butterfly a_l += a_(l xor 32), 16, 8, 4, 2, 1; the chunk sums are
+ *    added, from +0, in chunk order.  Any order satisfies
+ *    |mean - exact mean| <= (L + 1) 2^-53 max_i |x_i| per axis.
+ * xyz: 3 x n column-major like a cloud; origin (nullable): 3 host doubles.  The device form takes
+ * xyz, xyz_out and count_out in device memory, read like icp_set_model_device's array (after the work
+ * of any stream; valid until the call returns).  Both calls are synchronous (*n_out is on the host)
+ * and touch neither the resident clouds nor anything a run depends on: an icp_run after one is
+ * bit-identical to that run without it.
+ * ICP_E_ARG: a null required pointer, n == 0, n > INT_MAX, voxel not finite or not > 0, a non-finite
+ * origin or (host form) a non-finite coordinate.  ICP_E_RANGE: some c_a < 0 (a point below an explicit
+ * origin) or some g_a > 2^21 (icp_last_error names the axis and the value); the device form: a
+ * non-finite coordinate, as icp_set_model_device.  Nothing is written to the outputs on an error. */
+int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel, const double *origin,
+                         double *xyz_out, int32_t *count_out, size_t *n_out);
+int icp_voxel_downsample_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double voxel, const double *origin,
+                                double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out);
+
 /* ---- the ICP loop: GPU::ICP::find_corresponding_opti (src/GPU/gpu.cc:52-83) -- */
 /* Runs up to max_iter iterations on the resident clouds; stops after the iteration
  * whose err < threshold (pass threshold < 0 to run exactly max_iter iterations).

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_kernel(const double *
     if constexpr (MODE != 4)
         err_step_body(s_sum, cs.N, cs.threshold, cs.max_iter, cs.err_trace, cs.s, cs.hflag, cs.ticket, cs.h_state,
                       cs.h_trace);
-    if constexpr (MODE == 1 || MODE == 4) horn_step_body(s_sum, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s);
+    if constexpr (MODE == 1 || MODE == 4) horn_step_body(s_sum, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s, true);
 }
 
 
@@ -442,7 +442,7 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const dou
     if constexpr (MODE == 1)
         err_step_body(s_sum, cs.N, cs.threshold, cs.max_iter, cs.err_trace, cs.s, cs.hflag, cs.ticket, cs.h_state,
                       cs.h_trace);
-    horn_step_body(s_sum, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s);
+    horn_step_body(s_sum, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s, true);
 }
 
 } // namespace

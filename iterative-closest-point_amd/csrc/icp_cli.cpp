@@ -22,12 +22,22 @@
 //   --robust huber|tukey|cauchy  robust weights on the kept pairs (icp_set_robust): needs --robust-k
 //   --robust-k K       the weights' scale, in the clouds' units (> 0); needs --robust
 //   --write-normals FILE  writes the normals the run used (either option's) in the clouds' format
+//   --pyramid H1[,H2,...]  coarse-to-fine: for each voxel size in the order given, both clouds are
+//                      downsampled (icp_voxel_downsample), set with the unequal-size check lifted, the scene
+//                      moved by the pose so far (icp_transform_scene), registered with the run's own settings
+//                      and the total taken (icp_get_transform); then the full clouds from that pose.  One
+//                      "[pyramid] level ..." line per level and a "[pyramid] total ..." line go to stderr.
+//                      With --estimate-normals the normals are estimated per level; excludes --normals
+//   --pyramid-iters K  iterations per level (default nb_iter)
+//   --write-transform FILE  the total transform q = s R p + t (icp_get_transform) as a 4 x 4 matrix
+//                      [sR t; 0 0 0 1], four comma-separated rows of 6 significant digits
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/icp_capi.h"
 
@@ -49,7 +59,8 @@ int main(int argc, char **argv)
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
         std::printf("       options: [--max-dist X] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
-                    "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--out PATH]\n");
+                    "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
+                    "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -59,6 +70,7 @@ int main(int argc, char **argv)
     double threshold = 1e-5, max_dist = 0.0;
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
     const char *robust = nullptr, *robust_k = nullptr;
+    const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -74,6 +86,9 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
         else if (!std::strcmp(argv[a], "--robust") && a + 1 < argc) robust = argv[++a];
         else if (!std::strcmp(argv[a], "--robust-k") && a + 1 < argc) robust_k = argv[++a];
+        else if (!std::strcmp(argv[a], "--pyramid") && a + 1 < argc) pyramid = argv[++a];
+        else if (!std::strcmp(argv[a], "--pyramid-iters") && a + 1 < argc) pyramid_iters = argv[++a];
+        else if (!std::strcmp(argv[a], "--write-transform") && a + 1 < argc) write_transform = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
         else {
@@ -126,6 +141,38 @@ int main(int argc, char **argv)
         }
     }
 
+    // the pyramid's options: the list of voxel sizes (each a number > 0, no empty entry), the levels'
+    // iterations; --normals' rows belong to the full model
+    std::vector<double> voxels;
+    int level_iter = max_iter;
+    if (pyramid) {
+        for (const char *q = pyramid;;) {
+            char *end = nullptr;
+            const double h = std::strtod(q, &end);
+            if (end == q || (*end && *end != ',') || !(h > 0.0) || h > 1.7e308) {
+                std::fprintf(stderr, "[error] --pyramid: %s is not a list of voxel sizes > 0\n", pyramid);
+                return -1;
+            }
+            voxels.push_back(h);
+            if (!*end) break;
+            q = end + 1;
+        }
+        if (normals) {
+            std::fprintf(stderr, "[error] --pyramid and --normals exclude each other (the file's rows belong to the "
+                                 "full model): use --estimate-normals\n");
+            return -1;
+        }
+    }
+    if (pyramid_iters) {
+        char *end = nullptr;
+        const long v = std::strtol(pyramid_iters, &end, 10);
+        if (!pyramid || end == pyramid_iters || *end || v < 0 || v > 1000000) {
+            std::fprintf(stderr, "[error] --pyramid-iters: needs --pyramid and an integer >= 0\n");
+            return -1;
+        }
+        level_iter = (int)v;
+    }
+
     size_t nm = 0, np = 0;
     double *m = load_or_exit(argv[1], &nm);
     double *p = load_or_exit(argv[2], &np);
@@ -168,6 +215,103 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[error] --robust-k: %s\n", icp_strerror(rc));
         return 3;
     }
+    const auto die = [&](const char *what) {
+        std::fprintf(stderr, "[error] %s: %s: %s\n", what, icp_strerror(rc), icp_last_error(ctx));
+        return 3;
+    };
+    const auto write_total = [&]() { // --write-transform: [sR t; 0 0 0 1] in the CSV style
+        double s = 1.0, R[9], t[3];
+        if ((rc = icp_get_transform(ctx, &s, R, t)) != ICP_OK) return die("--write-transform");
+        FILE *f = std::fopen(write_transform, "w");
+        if (!f) {
+            std::fprintf(stderr, "[error] cannot write %s\n", write_transform);
+            return 2;
+        }
+        for (int r = 0; r < 3; ++r)
+            std::fprintf(f, "%g,%g,%g,%g\n", s * R[3 * r], s * R[3 * r + 1], s * R[3 * r + 2], t[r]);
+        std::fprintf(f, "0,0,0,1\n");
+        std::fclose(f);
+        return 0;
+    };
+    if (pyramid) {
+        // The calls of icp_amd.register_pyramid, in its order: every level's clouds first, then per
+        // level (and for the full clouds) set_allow_unequal, set_model, [estimate], set_scene,
+        // transform_scene by the pose so far, run, get_transform.
+        struct Level {
+            double h;
+            std::vector<double> m, p;
+        };
+        std::vector<Level> levels(voxels.size());
+        for (size_t l = 0; l < voxels.size(); ++l) {
+            Level &L = levels[l];
+            L.h = voxels[l];
+            L.m.resize(3 * nm);
+            L.p.resize(3 * np);
+            size_t cm = 0, cp = 0;
+            if ((rc = icp_voxel_downsample(ctx, m, nm, L.h, nullptr, L.m.data(), nullptr, &cm)) != ICP_OK ||
+                (rc = icp_voxel_downsample(ctx, p, np, L.h, nullptr, L.p.data(), nullptr, &cp)) != ICP_OK)
+                return die("--pyramid");
+            L.m.resize(3 * cm);
+            L.p.resize(3 * cp);
+        }
+        if (estimate)
+            for (const Level &L : levels)
+                if (L.m.size() / 3 < (size_t)est_k) {
+                    std::fprintf(stderr, "[error] --estimate-normals: K = %d exceeds the %zu model points of the level h=%g\n",
+                                 est_k, L.m.size() / 3, L.h);
+                    return -1;
+                }
+        if (estimate && (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK) return die("--estimate-normals");
+        double s = 1.0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+        double *errs = (double *)std::calloc((size_t)(max_iter > level_iter ? max_iter : level_iter) + 1, sizeof(double));
+        icp_result res{};
+        for (size_t l = 0; l <= levels.size(); ++l) {
+            const bool full = l == levels.size();
+            const double *lm = full ? m : levels[l].m.data(), *lp = full ? p : levels[l].p.data();
+            const size_t lnm = full ? nm : levels[l].m.size() / 3, lnp = full ? np : levels[l].p.size() / 3;
+            icp_set_allow_unequal(ctx, full ? (allow_unequal ? 1 : 0) : 1);
+            if ((rc = icp_set_model(ctx, lm, lnm)) != ICP_OK) return die("--pyramid");
+            if (estimate && (rc = icp_estimate_model_normals(ctx, est_k, nullptr, nullptr)) != ICP_OK)
+                return die("--estimate-normals");
+            if ((rc = icp_set_scene(ctx, lp, lnp, lnp)) != ICP_OK || (rc = icp_transform_scene(ctx, s, R, t)) != ICP_OK)
+                return die("--pyramid");
+            if (full) // the fine run's lines, as a plain run prints them
+                icp_set_progress(
+                    ctx,
+                    [](int i, double e, void *) { std::fprintf(stderr, "[ICP] iteration number %d | error value = %g\n", i, e); },
+                    nullptr);
+            if ((rc = icp_run(ctx, full ? max_iter : level_iter, threshold, errs, &res)) != ICP_OK) return die("icp_run");
+            if ((rc = icp_get_transform(ctx, &s, R, t)) != ICP_OK) return die("--pyramid");
+            if (!full)
+                std::fprintf(stderr, "[pyramid] level h=%g model %zu scene %zu points, %d iterations, err %g\n", levels[l].h,
+                             lnm, lnp, res.iterations, res.err);
+        }
+        std::fprintf(stderr, "[pyramid] total s=%.17g R=%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g t=%.17g,%.17g,%.17g\n", s,
+                     R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], t[0], t[1], t[2]);
+        if (write_normals) {
+            std::vector<double> nout(3 * nm);
+            if ((rc = icp_get_model_normals(ctx, nout.data())) != ICP_OK) return die("--write-normals");
+            if (icp_write_matrix(write_normals, nout.data(), nm) != ICP_OK) {
+                std::fprintf(stderr, "[error] cannot write %s\n", write_normals);
+                return 2;
+            }
+        }
+        if (write_transform) {
+            const int w = write_total();
+            if (w) return w;
+        }
+        if ((rc = icp_get_scene(ctx, p)) != ICP_OK) return die("icp_get_scene");
+        if (icp_write_matrix(out, p, np) != ICP_OK) {
+            std::fprintf(stderr, "[error] cannot write %s\n", out);
+            return 2;
+        }
+        std::fprintf(stderr, "[output] output file \"%s\" was generated.\n", out);
+        icp_ctx_destroy(ctx);
+        std::free(errs);
+        icp_free(m);
+        icp_free(p);
+        return 0;
+    }
     if ((rc = icp_set_model(ctx, m, nm)) != ICP_OK || (rc = icp_set_scene(ctx, p, np, np)) != ICP_OK) {
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
@@ -209,6 +353,10 @@ int main(int argc, char **argv)
     if (rc != ICP_OK) {
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
+    }
+    if (write_transform) {
+        const int w = write_total();
+        if (w) return w;
     }
     if ((rc = icp_get_scene(ctx, p)) != ICP_OK) {
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));

@@ -73,6 +73,11 @@ struct icp_ctx {
     DevCloud scene, Y;
     size_t np_total = 0;
     bool has_scene = false;
+    // icp_get_transform: (s, R row-major, t) mapping the scene as icp_set_scene* received it onto the
+    // resident one -- every finished run's total (IterState::tot, finish_run) and every
+    // icp_transform_scene, composed on the host (compose_srt); tot_n == 0: the identity
+    double tot[13] = {0};
+    int tot_n = 0;
 
     // scratch clouds for the per-operation surface
     DevCloud qa, qb;
@@ -312,6 +317,14 @@ struct icp_ctx {
     double *knn_d2 = nullptr;
     unsigned long long *knn_counters = nullptr;
     size_t knn_idx_cap = 0, knn_d2_cap = 0, knn_counters_cap = 0;
+
+    // icp_voxel_downsample* (icp_voxel.hip): scratch of those calls alone -- the keys, orders, run
+    // heads and box rows (vox_buf), the host form's staged input and output clouds (vox_io: 6 n
+    // doubles) and counts (vox_cnt)
+    char *vox_buf = nullptr;
+    double *vox_io = nullptr;
+    int *vox_cnt = nullptr;
+    size_t vox_buf_cap = 0, vox_io_cap = 0, vox_cnt_cap = 0;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};

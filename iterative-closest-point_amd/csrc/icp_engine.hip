@@ -1262,7 +1262,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
-                    (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters})
+                    (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
+                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
@@ -1855,6 +1856,7 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
 {
     ctx->np_total = np_total;
     ctx->has_scene = true;
+    ctx->tot_n = 0; // (icp_get_transform: the identity)
     ctx->seeds_valid = false;
     ctx->seedd_valid = false;
     ctx->gate_have = false;
@@ -1893,6 +1895,182 @@ int icp_get_scene(icp_ctx *ctx, double *p_xyz_out)
         return download_cloud(ctx, ctx->s_tmp, P.n, p_xyz_out);
     }
     return download_cloud(ctx, ctx->scene, ctx->scene.n, p_xyz_out);
+}
+
+// ---- the total transform, a pose for the resident scene, the voxel downsample -----------
+
+int icp_get_transform(icp_ctx *ctx, double *s, double R[9], double t[3])
+{
+    if (!ctx || !s || !R || !t) return ICP_E_ARG;
+    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, "icp_get_transform: scene not set");
+    *s = 1.0;
+    for (int k = 0; k < 9; ++k) R[k] = k % 4 == 0 ? 1.0 : 0.0;
+    for (int k = 0; k < 3; ++k) t[k] = 0.0;
+    if (ctx->tot_n > 0) {
+        *s = ctx->tot[0];
+        for (int k = 0; k < 9; ++k) R[k] = ctx->tot[1 + k];
+        for (int k = 0; k < 3; ++k) t[k] = ctx->tot[10 + k];
+    }
+    return ICP_OK;
+}
+
+int icp_transform_scene(icp_ctx *ctx, double s, const double R[9], const double t[3])
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!R || !t) return fail(ctx, ICP_E_ARG, "icp_transform_scene: R or t is null");
+    bool finite = std::isfinite(s);
+    for (int k = 0; k < 9; ++k) finite = finite && std::isfinite(R[k]);
+    for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(t[k]);
+    if (!finite) return fail(ctx, ICP_E_ARG, "icp_transform_scene: s, R or t is not finite");
+    if (!(s > 0.0)) return fail(ctx, ICP_E_ARG, "icp_transform_scene: s = " + std::to_string(s) + " is not > 0");
+    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, "icp_transform_scene: scene not set");
+    HIPCHK(hipSetDevice(ctx->device));
+    double step[13];
+    Xform xf{};
+    step[0] = s;
+    for (int k = 0; k < 9; ++k) {
+        step[1 + k] = R[k];
+        xf.sR[k] = s * R[k]; // (once, as the Horn step forms it)
+    }
+    for (int k = 0; k < 3; ++k) {
+        step[10 + k] = t[k];
+        xf.t[k] = t[k];
+        xf.c[k] = ctx->c[k];
+    }
+    // The moved points, in the caller's order, into the stage; from there the scene is prepared as
+    // icp_set_scene prepares an upload of them: the same kernels on the same values, so the slot
+    // order, the fp32 copy and every flag are those of a fresh icp_set_scene.
+    const size_t n = ctx->scene.n;
+    bool slot = false;
+    if (n) {
+        DevCloud &P = ctx->scene;
+        TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+        launch_transform_to_aos(P.x, P.y, P.z, (int)n, ctx->scene_slot ? ctx->s_order : nullptr, xf, ctx->stage, ctx->st);
+        LAUNCHCHK("transform_to_aos");
+        if (3 * n <= kMappedIo) {
+            launch_aos_to_soa_f32(ctx->stage, n, P.x, P.y, P.z, ctx->c, P.f, ctx->st);
+            LAUNCHCHK("transform_scene");
+        } else {
+            TRY(scene_from_aos(ctx, ctx->stage, n, &slot));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->st));
+    }
+    double tot[13];
+    const int tot_n = ctx->tot_n;
+    std::memcpy(tot, ctx->tot, sizeof(tot));
+    TRY(set_scene_common(ctx, n, ctx->np_total, slot));
+    std::memcpy(ctx->tot, tot, sizeof(tot));
+    ctx->tot_n = tot_n;
+    compose_srt(step, ctx->tot, &ctx->tot_n);
+    return ICP_OK;
+}
+
+// the box rows folded: lo / hi per axis; ICP_E_RANGE for a non-finite coordinate (as icp_set_model_device)
+static int voxel_box(icp_ctx *ctx, const double *xyz_dev, size_t n, double lo[3], double hi[3])
+{
+    const int rows = voxel_box_blocks((int)n);
+    double *part = (double *)ctx->vox_buf; // (the head of the scratch: read back before the passes write it)
+    launch_voxel_box(xyz_dev, (int)n, part, ctx->st);
+    LAUNCHCHK("voxel_box");
+    std::vector<double> h(8 * (size_t)rows);
+    HIPCHK(hipMemcpyAsync(h.data(), part, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    bool bad = false;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = h[a];
+        hi[a] = h[3 + a];
+    }
+    for (int r = 0; r < rows; ++r) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = std::min(lo[a], h[8 * (size_t)r + a]);
+            hi[a] = std::max(hi[a], h[8 * (size_t)r + 3 + a]);
+        }
+        bad = bad || h[8 * (size_t)r + 6] != 0.0;
+    }
+    if (bad) return fail(ctx, ICP_E_RANGE, "icp_voxel_downsample: the cloud has non-finite coordinates");
+    return ICP_OK;
+}
+
+// both forms, the cloud and the outputs in device memory; *n_out on the host when it returns
+static int voxel_downsample_dev(icp_ctx *ctx, const double *xyz_dev, size_t n, double voxel, const double *origin,
+                                double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out)
+{
+    const size_t bytes = std::max(voxel_scratch_bytes((int)n), sizeof(double) * 8 * (size_t)voxel_box_blocks((int)n)) + 256;
+    TRY(grow(ctx, &ctx->vox_buf, &ctx->vox_buf_cap, bytes));
+    double lo[3], hi[3];
+    TRY(voxel_box(ctx, xyz_dev, n, lo, hi));
+    VoxelGrid vg{};
+    vg.voxel = voxel;
+    static const char axis[3] = {'x', 'y', 'z'};
+    for (int a = 0; a < 3; ++a) {
+        vg.lo[a] = origin ? origin[a] : lo[a];
+        // floor((x - lo) / voxel) does not decrease with x: the least and the largest cell of the axis
+        const double c_min = std::floor((lo[a] - vg.lo[a]) / voxel), c_max = std::floor((hi[a] - vg.lo[a]) / voxel);
+        if (c_min < 0.0)
+            return fail(ctx, ICP_E_RANGE, std::string("icp_voxel_downsample: a point's ") + axis[a] + " = " +
+                                              std::to_string(lo[a]) + " lies below the origin's " +
+                                              std::to_string(vg.lo[a]));
+        if (!(c_max + 1.0 <= 2097152.0))
+            return fail(ctx, ICP_E_RANGE, std::string("icp_voxel_downsample: the ") + axis[a] + " axis needs " +
+                                              std::to_string(c_max + 1.0) + " cells, more than 2^21 (voxel = " +
+                                              std::to_string(voxel) + ")");
+        vg.g[a] = (long long)c_max + 1;
+    }
+    int *n_dev = (int *)(ctx->vox_buf + bytes - 256);
+    if (launch_voxel_downsample(xyz_dev, (int)n, vg, ctx->vox_buf, bytes - 256, xyz_out_dev, count_out_dev, n_dev, ctx->st) !=
+        hipSuccess)
+        return fail(ctx, ICP_E_HIP, "icp_voxel_downsample: a launch failed");
+    int cells = 0;
+    HIPCHK(hipMemcpyAsync(&cells, n_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    *n_out = (size_t)cells;
+    return ICP_OK;
+}
+
+static int voxel_args(icp_ctx *ctx, const void *xyz, size_t n, double voxel, const double *origin, const void *xyz_out,
+                      const size_t *n_out)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!xyz || !xyz_out || !n_out) return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: xyz, xyz_out or n_out is null");
+    if (n == 0 || n > (size_t)INT_MAX)
+        return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: n = " + std::to_string(n) + " is outside [1, INT_MAX]");
+    if (!std::isfinite(voxel) || !(voxel > 0.0))
+        return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: voxel = " + std::to_string(voxel) + " is not finite and > 0");
+    if (origin)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(origin[a]))
+                return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: origin[" + std::to_string(a) + "] is not finite");
+    HIPCHK(hipSetDevice(ctx->device));
+    return ICP_OK;
+}
+
+int icp_voxel_downsample_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double voxel, const double *origin,
+                                double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out)
+{
+    TRY(voxel_args(ctx, xyz_dev, n, voxel, origin, xyz_out_dev, n_out));
+    HIPCHK(hipDeviceSynchronize()); // (the array is read after the work of any stream, as icp_set_model_device's)
+    return voxel_downsample_dev(ctx, xyz_dev, n, voxel, origin, xyz_out_dev, count_out_dev, n_out);
+}
+
+int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel, const double *origin, double *xyz_out,
+                         int32_t *count_out, size_t *n_out)
+{
+    TRY(voxel_args(ctx, xyz, n, voxel, origin, xyz_out, n_out));
+    for (size_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(xyz[k]))
+            return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: point " + std::to_string(k / 3) + " is not finite");
+    TRY(grow(ctx, &ctx->vox_io, &ctx->vox_io_cap, 6 * n));
+    if (count_out) TRY(grow(ctx, &ctx->vox_cnt, &ctx->vox_cnt_cap, n));
+    double *in = ctx->vox_io, *out = ctx->vox_io + 3 * n;
+    HIPCHK(hipMemcpyAsync(in, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
+    size_t cells = 0;
+    TRY(voxel_downsample_dev(ctx, in, n, voxel, origin, out, count_out ? ctx->vox_cnt : nullptr, &cells));
+    HIPCHK(hipMemcpyAsync(xyz_out, out, sizeof(double) * 3 * cells, hipMemcpyDeviceToHost, ctx->st));
+    if (count_out)
+        HIPCHK(hipMemcpyAsync(count_out, ctx->vox_cnt, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    *n_out = cells;
+    return ICP_OK;
 }
 
 // ---- per-operation surface ------------------------------------------------------------

@@ -26,10 +26,20 @@ __device__ __forceinline__ bool step_counters(int *__restrict__ cnt, IterState *
     return true;
 }
 
+// early_total (a compile-time constant at every call): the first and the last word of the run's total
+// are loaded before the solve, which brings its two cache lines near while the solve runs (the
+// canonical fold, where the step is on every iteration's critical path and the state is in global
+// memory); the rest is loaded where it is composed.  Loading all of it early cost the fold 27 VGPRs
+// and the benchmark 2 % (profiles/voxel/bench_ab.txt).
 __device__ __forceinline__ void horn_step_body(const double *__restrict__ sums, double N, double c0, double c1, double c2,
-                               int shifted, int *__restrict__ cnt, IterState *__restrict__ s)
+                               int shifted, int *__restrict__ cnt, IterState *__restrict__ s, bool early_total = false)
 {
     if (!step_counters(cnt, s)) return;
+    double tot_first = 0.0, tot_last = 0.0;
+    if (early_total) {
+        tot_first = s->tot[0];
+        tot_last = s->tot[12];
+    }
     double mu_p[3], mu_y[3], S[9], d_caps, sp;
     if (!shifted) { // two-pass sums (moments_phase): Σp, Σy, then centred S, d_caps, sp
         for (int k = 0; k < 3; ++k) {
@@ -54,14 +64,25 @@ __device__ __forceinline__ void horn_step_body(const double *__restrict__ sums, 
     }
     double sc, R[9], t[3];
     horn_solve(S, mu_p, mu_y, d_caps, sp, &sc, R, t);
-    s->srt[0] = sc;
-    for (int k = 0; k < 9; ++k) {
-        s->srt[1 + k] = R[k];
-        s->xf.sR[k] = sc * R[k];
-    }
-    for (int k = 0; k < 3; ++k) {
-        s->srt[10 + k] = t[k];
-        s->xf.t[k] = t[k];
+    double step[13];
+    step[0] = sc;
+    for (int k = 0; k < 9; ++k) step[1 + k] = R[k];
+    for (int k = 0; k < 3; ++k) step[10 + k] = t[k];
+    for (int k = 0; k < 13; ++k) s->srt[k] = step[k];
+    for (int k = 0; k < 9; ++k) s->xf.sR[k] = sc * R[k];
+    for (int k = 0; k < 3; ++k) s->xf.t[k] = t[k];
+    // the run's total (icp_get_transform): this step's transform follows, so it is applied
+    if (early_total) {
+        double tot[13];
+        tot[0] = tot_first;
+        for (int k = 1; k < 12; ++k) tot[k] = s->tot[k];
+        tot[12] = tot_last;
+        int tot_n = s->tot_n;
+        compose_srt(step, tot, &tot_n);
+        for (int k = 0; k < 13; ++k) s->tot[k] = tot[k];
+        s->tot_n = tot_n;
+    } else {
+        compose_srt(step, s->tot, &s->tot_n);
     }
     s->xf.c[0] = c0;
     s->xf.c[1] = c1;

@@ -271,4 +271,28 @@ ICP_HD inline void horn_solve(const double S[9], const double mu_p[3], const dou
     *s_out = sc;
 }
 
+// The total transform (icp_get_transform): tot <- step o tot on (s, R row-major, t) triples of 13
+// doubles, (s2, R2, t2) o (s1, R1, t1) = (s2 s1, R2 R1, s2 R2 t1 + t2), every 3-term sum as matvec3's.
+// *n counts the steps composed; the first one is copied (the identity composes exactly).
+ICP_HD inline void compose_srt(const double step[13], double tot[13], int *n)
+{
+    if (*n == 0) {
+        for (int k = 0; k < 13; ++k) tot[k] = step[k];
+    } else {
+        double R[9], sR[9], st[3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const double a = step[1 + 3 * r] * tot[1 + c], b = step[2 + 3 * r] * tot[4 + c],
+                             d = step[3 + 3 * r] * tot[7 + c];
+                R[3 * r + c] = (a + b) + d;
+            }
+        for (int k = 0; k < 9; ++k) sR[k] = step[0] * step[1 + k];
+        matvec3(sR, tot + 10, st);
+        tot[0] = step[0] * tot[0];
+        for (int k = 0; k < 9; ++k) tot[1 + k] = R[k];
+        for (int k = 0; k < 3; ++k) tot[10 + k] = st[k] + step[10 + k];
+    }
+    *n += 1;
+}
+
 } // namespace icp

@@ -496,7 +496,33 @@ struct IterState {
     int queued2;       // amb_count[2] of the last search (the seeded grid search's second pass),
                        // copied by the Horn step before it zeroes the counters (the host sizes
                        // the next second pass by it)
+    // The run's total so far (icp_get_transform): tot_n steps composed, tot = (s, R row-major, t) of
+    // step tot_n o ... o step 1 -- written by the thread that writes srt (compose_total, icp_horn.h),
+    // so every schedule keeps it.  tot_n == 0 (the zeroed state of a run's start): the identity.
+    double tot[13];
+    int tot_n;
+    int tot_pad;
 };
+
+// ---- the voxel downsample and icp_transform_scene's kernel (icp_voxel.hip) -----------------
+// The lattice: a point's cell per axis is floor((x_a - lo[a]) / voxel), 0 <= cell < g[a] <= 2^21
+struct VoxelGrid {
+    double lo[3];
+    double voxel;
+    long long g[3];
+};
+// the cloud's box: voxel_box_blocks(n) rows of 8 doubles (min xyz, max xyz, a non-finite flag, -),
+// folded by the host
+int voxel_box_blocks(int n);
+void launch_voxel_box(const double *aos, int n, double *part, hipStream_t st);
+// keys, sort, run heads, segmented means: xyz_out (3 x n doubles) and count_out (n ints, nullable)
+// get one entry per occupied cell in ascending key order, *n_out_dev their number; all on `st`
+size_t voxel_scratch_bytes(int n);
+hipError_t launch_voxel_downsample(const double *aos, int n, const VoxelGrid &vg, void *scratch, size_t bytes,
+                                   double *xyz_out, int *count_out, int *n_out_dev, hipStream_t st);
+// aos[order ? order[i] : i] = sR (x, y, z)[i] + t (transform_point)
+void launch_transform_to_aos(const double *x, const double *y, const double *z, int n, const int *order, const Xform &xf,
+                             double *aos, hipStream_t st);
 
 // ---- the canonical order of a slot-order scene's iteration sums (icp_canon.h / .hip) ------
 // The error step of the previous iteration and this iteration's Horn step (canon_fold_kernel)

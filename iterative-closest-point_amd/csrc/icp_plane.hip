@@ -252,6 +252,9 @@ __device__ __forceinline__ void plane_solve_body(const double *__restrict__ part
         s->xf.t[k] = t;
         s->xf.c[k] = c[k];
     }
+    double inc[13]; // (the step is applied: a frozen iteration returned above)
+    for (int k = 0; k < 13; ++k) inc[k] = s->srt[k];
+    compose_srt(inc, s->tot, &s->tot_n);
 }
 
 __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__restrict__ partials, int nblocks,

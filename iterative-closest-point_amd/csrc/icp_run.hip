@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "icp_engine.h"
+#include "icp_horn.h"
 
 namespace {
 
@@ -178,6 +179,8 @@ int finish_run(icp_ctx *ctx, double threshold, double *err_trace, icp_result *re
         for (int k = 0; k < 9; ++k) r.R[k] = hs.srt[1 + k];
         for (int k = 0; k < 3; ++k) r.t[k] = hs.srt[10 + k];
     }
+    // (the run's applied steps into the context's total; a run that recorded nothing mirrored nothing)
+    if (hs.iter > 0 && hs.tot_n > 0) compose_srt(hs.tot, ctx->tot, &ctx->tot_n);
     ctx->stats.iterations += hs.iter;
     if (ctx->nn_mode == ICP_NN_CERTIFIED) {
         ctx->stats.ambiguous += hs.nn_counts[0];

@@ -79,6 +79,7 @@ EXPORTED = [
     "icp_set_metric", "icp_set_model_normals", "icp_set_model_normals_device",
     "icp_model_knn", "icp_estimate_model_normals", "icp_get_model_normals",
     "icp_set_robust", "icp_get_robust_trace",
+    "icp_voxel_downsample", "icp_voxel_downsample_device", "icp_get_transform", "icp_transform_scene",
 ]
 
 
@@ -202,6 +203,11 @@ def lib() -> C.CDLL:
     if hasattr(L, "icp_set_robust"):
         L.icp_set_robust.argtypes = [vp, C.c_int, C.c_double]
         L.icp_get_robust_trace.argtypes = [vp, dp, C.POINTER(C.c_longlong), sz]
+    if hasattr(L, "icp_voxel_downsample"):
+        L.icp_voxel_downsample.argtypes = [vp, dp, sz, C.c_double, dp, dp, C.POINTER(C.c_int32), C.POINTER(sz)]
+        L.icp_voxel_downsample_device.argtypes = [vp, vp, sz, C.c_double, dp, vp, vp, C.POINTER(sz)]
+        L.icp_get_transform.argtypes = [vp, dp, dp, dp]
+        L.icp_transform_scene.argtypes = [vp, C.c_double, dp, dp]
     _lib = L
     return L
 
@@ -431,6 +437,50 @@ class Context:
 
     def set_allow_unequal(self, allow: bool):
         self._check(lib().icp_set_allow_unequal(self._h, 1 if allow else 0))
+        self._allow_unequal = bool(allow)
+
+    def voxel_downsample(self, xyz, voxel: float, origin=None, counts: bool = False):
+        """icp_voxel_downsample: one point per occupied cell of a lattice of side `voxel` through
+        `origin` (None: the cloud's minimum corner), the mean of the cell's points, in ascending cell-key
+        order -> (n_out, 3), or (points, counts int32) with counts."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        out = np.empty((max(n, 1), 3))
+        cnt = np.empty(max(n, 1), dtype=np.int32) if counts else None
+        n_out = C.c_size_t(0)
+        self._check(lib().icp_voxel_downsample(self._h, _dp(xyz), n, float(voxel), None if o is None else _dp(o),
+                                               _dp(out), cnt.ctypes.data_as(C.POINTER(C.c_int32)) if counts else None,
+                                               C.byref(n_out)))
+        k = int(n_out.value)
+        return (out[:k].copy(), cnt[:k].copy()) if counts else out[:k].copy()
+
+    def voxel_downsample_device(self, ptr: int, n: int, voxel: float, out_ptr: int, origin=None,
+                                count_ptr: int | None = None) -> int:
+        """icp_voxel_downsample_device: the cloud (AoS fp64), the output cloud (room for n points) and
+        the counts (int32, room for n; None: not wanted) are device pointers -> the number of cells."""
+        o = None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+        n_out = C.c_size_t(0)
+        self._check(lib().icp_voxel_downsample_device(self._h, C.c_void_p(ptr), n, float(voxel),
+                                                      None if o is None else _dp(o), C.c_void_p(out_ptr),
+                                                      C.c_void_p(count_ptr) if count_ptr else None, C.byref(n_out)))
+        return int(n_out.value)
+
+    def transform(self):
+        """icp_get_transform: (s, R (3, 3), t (3,)) with q = s R p + t mapping the scene as set_scene
+        received it onto the resident scene now (every applied iteration, every transform_scene)."""
+        s = C.c_double(0.0)
+        R = np.empty(9)
+        t = np.empty(3)
+        self._check(lib().icp_get_transform(self._h, C.cast(C.byref(s), C.POINTER(C.c_double)), _dp(R), _dp(t)))
+        return float(s.value), R.reshape(3, 3), t
+
+    def transform_scene(self, s: float, R, t):
+        """icp_transform_scene: moves the resident scene by q = s R p + t, composes it into the total
+        and prepares the scene as set_scene of the moved points would."""
+        R = _vec(R, 9)
+        t = _vec(t, 3)
+        self._check(lib().icp_transform_scene(self._h, float(s), _dp(R), _dp(t)))
 
     def set_max_distance(self, d: float):
         """icp_set_max_distance: run() keeps only the pairs no farther apart than d (0 or inf: off)."""
@@ -648,6 +698,54 @@ class Context:
 # ---------------------------------------------------------------------------------
 # reference-shaped API (src/GPU/gpu.hh)
 # ---------------------------------------------------------------------------------
+
+def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int | None = None,
+                     threshold: float = 1e-5, estimate_normals: int | None = None):
+    """Coarse-to-fine registration of the scene p onto the model m from the engine's own calls (the
+    icp-gpu CLI's --pyramid makes the same calls in the same order).  For each voxel size, in the
+    order given (coarse to fine): downsample both clouds, set them with the unequal-size check
+    lifted, move the scene by the pose so far (transform_scene), run level_iter (default max_iter)
+    iterations with the context's own settings (gate, robust weights, metric), take the total
+    (transform).  Then the full clouds: set them, apply the pose, run max_iter iterations.
+    estimate_normals = K: the model's normals are estimated at every level (and for the full
+    clouds) from K neighbours; a level whose model has fewer than K points raises before any run.
+    -> (the fine run's Result, the total (s, R, t), the records: one dict per level -- voxel,
+    model_points, scene_points, iterations, err, converged, errs -- and a last one, voxel None, for
+    the fine run)."""
+    m = _cloud(m)
+    p = _cloud(p)
+    voxels = [float(h) for h in voxels]
+    if any(not (h > 0.0) or not np.isfinite(h) for h in voxels):
+        raise ValueError("voxel sizes must be finite and > 0")
+    k_iter = max_iter if level_iter is None else int(level_iter)
+    allow = getattr(ctx, "_allow_unequal", False)
+    clouds = [(h, ctx.voxel_downsample(m, h), ctx.voxel_downsample(p, h)) for h in voxels]
+    if estimate_normals is not None:
+        for h, mc, _ in clouds:
+            if mc.shape[0] < estimate_normals:
+                raise ValueError(f"--estimate-normals {estimate_normals}: the level h={h:g} has a model of "
+                                 f"{mc.shape[0]} points")
+    clouds.append((None, m, p))
+    pose = (1.0, np.eye(3), np.zeros(3))
+    records = []
+    res = None
+    try:
+        for h, mc, pc in clouds:
+            ctx.set_allow_unequal(True if h is not None else allow)
+            ctx.set_model(mc)
+            if estimate_normals is not None:
+                ctx.estimate_model_normals(estimate_normals)
+            ctx.set_scene(pc)
+            ctx.transform_scene(*pose)
+            res, errs = ctx.run(max_iter if h is None else k_iter, threshold)
+            pose = ctx.transform()
+            records.append({"voxel": h, "model_points": mc.shape[0], "scene_points": pc.shape[0],
+                            "iterations": res.iterations, "err": float(res.err), "converged": bool(res.converged),
+                            "errs": errs})
+    finally:
+        ctx.set_allow_unequal(allow)
+    return res, pose, records
+
 
 @dataclass
 class ICP:
