@@ -3,6 +3,7 @@ icp_transform_scene, icp_get_transform): icp_amd.register_pyramid and the CLI's 
 
 The voxel of the cow pair's coarse level is extent / 16 (voxel_ref.COW_VOXEL_DIV: tests/test_voxel_ref.py
 checks on the CPU that the numpy twin then needs at most half the plain run's iterations).
+test_matches_the_numpy_twin holds one- and two-level pyramids to voxel_ref.pyramid_twin itself.
 """
 import os
 import subprocess
@@ -86,6 +87,44 @@ def test_total_moves_the_original_scene_onto_the_final_one(cow, pyramid):
     bound = 8.0 * V.G_REL * float(np.abs(p).max())
     print(f"total against the final scene: {gap:.3e} (bound {bound:.3e})")
     assert gap <= bound
+
+
+_TWIN = {}
+
+
+def twin(m, p, divs):
+    """voxel_ref.pyramid_twin on the order rule's coarse clouds, every run its full count: once per pyramid."""
+    if tuple(divs) not in _TWIN:
+        _TWIN[tuple(divs)] = V.pyramid_twin(m, p, [V.extent(m) / d for d in divs], V.PYRAMID_FINE_ITERS,
+                                            V.PYRAMID_LEVEL_ITERS, -1.0, V.coarse_rule)
+    return _TWIN[tuple(divs)]
+
+
+@pytest.mark.parametrize("divs", V.COW_PYRAMIDS)
+def test_matches_the_numpy_twin(icp_lib, cow, divs):
+    """One level and two against the numpy twin, at the tolerances tests/test_gpu_parity.py holds the cow
+    pair's plain run to (tests/test_voxel_ref.py: the twin moves by less than a hundredth of them when its
+    coarse means are rounded another way)."""
+    m, p = cow
+    moved, errs, (s, R, t), levels = twin(m, p, divs)
+    with icp_lib.Context() as ctx:
+        res, total, records = icp_lib.register_pyramid(ctx, m, p, [V.extent(m) / d for d in divs], V.PYRAMID_FINE_ITERS,
+                                                       V.PYRAMID_LEVEL_ITERS, threshold=-1.0)
+        scene = ctx.get_scene()
+    assert len(records) == len(divs) + 1
+    for rec, lev in zip(records, levels):
+        assert (rec["model_points"], rec["scene_points"], rec["iterations"]) == lev[:3]
+        print(f"{divs} level h = {rec['voxel']:.4g}: errs {np.max(np.abs(rec['errs'] - lev[3]) / lev[3]):.3e} relative")
+    assert records[-1]["iterations"] == res.iterations == len(errs) == V.PYRAMID_FINE_ITERS
+    scale = float(np.abs(m).max())
+    print(f"{divs}: errs {np.max(np.abs(records[-1]['errs'] - errs) / errs):.3e} relative, scene "
+          f"{np.abs(scene - moved).max():.3e}, s {abs(total[0] - s):.3e}, R {np.abs(total[1] - R).max():.3e}, "
+          f"t {np.abs(total[2] - t).max():.3e}")
+    np.testing.assert_allclose(records[-1]["errs"], errs, rtol=1e-9)
+    np.testing.assert_allclose(scene, moved, atol=1e-9 * scale)
+    assert abs(total[0] - s) <= 1e-9
+    np.testing.assert_allclose(total[1], R, atol=1e-9)
+    np.testing.assert_allclose(total[2], t, atol=1e-9 * scale)
 
 
 def test_cli_pyramid_writes_the_python_paths_scene(icp_lib, cow, pyramid, tmp_path):

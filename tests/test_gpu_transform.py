@@ -245,6 +245,115 @@ def test_transform_scene(icp_lib, cow, n):
             step_bits(res2.s, np.array(res2.R[:]), np.array(res2.t[:]))
 
 
+def check_pose_then_run(amd, m, p, allow_unequal=False, model2=None):
+    """test_transform_scene's pattern: two iterations, [a new model], the pose, then the moved points
+    against numpy, the total's composition, and five more iterations bit for bit against a fresh context
+    given the moved points."""
+    s, R, t = pose()
+    with amd.Context() as ctx:
+        ctx.set_allow_unequal(allow_unequal)
+        ctx.set_model(m)
+        ctx.set_scene(p)
+        ctx.run(2, -1.0)
+        before, first = ctx.get_scene(), ctx.transform()
+        if model2 is not None:  # (a scene in slot order then waits to be put back into file order)
+            ctx.set_model(model2)
+        ctx.transform_scene(s, R, t)
+        moved = ctx.get_scene()
+        sR = s * R
+        tol = 4.0 * V.U * (np.abs(before) @ np.abs(sR).T + np.abs(t))
+        assert (np.abs(moved - (before @ sR.T + t)) <= tol).all()
+        ts, tR, tt = ctx.transform()
+        assert abs(ts - s * first[0]) <= 4 * V.U * ts
+        assert np.abs(tR - R @ first[1]).max() <= 8 * V.U
+        assert np.abs(tt - (sR @ first[2] + t)).max() <= 16 * V.U * (np.abs(first[2]).max() + np.abs(t).max())
+        assert total_gap(ctx, p) <= bound(p)
+        res, errs = ctx.run(5, -1.0)
+        scene, idx = ctx.get_scene(), ctx.get_indices()
+    with amd.Context() as ctx:
+        ctx.set_allow_unequal(allow_unequal)
+        ctx.set_model(m if model2 is None else model2)
+        ctx.set_scene(moved)
+        res2, errs2 = ctx.run(5, -1.0)
+        assert res.iterations == res2.iterations == 5
+        assert bits(errs) == bits(errs2)
+        assert np.array_equal(idx, ctx.get_indices())
+        assert bits(scene) == bits(ctx.get_scene())
+        assert step_bits(res.s, np.array(res.R[:]), np.array(res.t[:])) == \
+            step_bits(res2.s, np.array(res2.R[:]), np.array(res2.t[:]))
+
+
+@pytest.mark.parametrize("n", [65536, 65537])
+def test_transform_scene_in_slot_order(icp_lib, n):
+    """Two iterations at 2^16 points and more leave the scene in slot order (tests/test_gpu_plane.py's case
+    8 relies on it), so the pose un-permutes it.  65,536: the largest scene prepared through the mapped
+    buffer; 65,537: the staged path, whose preparation sorts the moved points into a new slot order."""
+    m, p = icp_lib.synthetic_pair(n)
+    check_pose_then_run(icp_lib, m, p)
+
+
+def test_transform_scene_staged_in_file_order(icp_lib):
+    """A 70,000-point scene against a 4,097-point model: staged, and too small a model for slot order."""
+    amd = icp_lib
+    m, _ = amd.synthetic_pair(4097)
+    r = np.random.default_rng(70000)
+    p = np.tile(m, (18, 1))[:70000] + 0.01 * r.standard_normal((70000, 3))
+    check_pose_then_run(amd, m, p, allow_unequal=True)
+
+
+def test_transform_scene_with_a_revert_pending(icp_lib):
+    """set_model on a scene in slot order only marks it (the next run puts it back into file order); a
+    pose before that run moves the scene as it was, in the caller's order."""
+    m, p = icp_lib.synthetic_pair(65536)
+    check_pose_then_run(icp_lib, m, p, model2=m + np.array([0.01, 0.0, 0.0]))
+
+
+def test_transform_scene_on_two_ranks(icp_lib, cow):
+    amd = icp_lib
+    m, p = cow
+    s, R, t = pose()
+
+    def sequence(ctx):
+        r1, e1 = ctx.run(2, -1.0)
+        ctx.transform_scene(s, R, t)
+        r2, e2 = ctx.run(3, -1.0)
+        assert r1.iterations == 2 and r2.iterations == 3
+        return np.concatenate([e1, e2]), ctx.transform(), ctx.get_scene()
+
+    with amd.Context() as ctx:
+        ctx.set_model(m)
+        ctx.set_scene(p)
+        single = sequence(ctx)
+    red = HostAllReduce(2)
+    results, errors = [None, None], []
+
+    def worker(r):
+        try:
+            b, c = amd.shard_range(p.shape[0], r, 2)
+            with amd.Context(0, amd.NN_CERTIFIED, rank=r, world_size=2, host_allreduce=red.for_rank(r)) as ctx:
+                ctx.set_model(m)
+                ctx.set_scene(p[b:b + c], np_total=p.shape[0])
+                results[r] = sequence(ctx) + (p[b:b + c],)
+        except Exception as e:  # pragma: no cover - surfaced below
+            errors.append(e)
+            red.bar.abort()
+
+    th = [threading.Thread(target=worker, args=(r,)) for r in range(2)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join(timeout=300)
+    assert not errors, errors
+    assert step_bits(*results[0][1]) == step_bits(*results[1][1])
+    assert bits(results[0][0]) == bits(results[1][0])
+    for _, (ts, tR, tt), scene, shard in results:
+        gap = float(np.abs((shard @ (ts * tR).T + tt) - scene).max())
+        print(f"shard: {gap:.3e} (bound {bound(p):.3e})")
+        assert gap <= bound(p)
+    np.testing.assert_allclose(results[0][0], single[0], rtol=1e-11)
+    np.testing.assert_allclose(np.concatenate([r[2] for r in results]), single[2], atol=1e-12)
+
+
 def test_transform_errors(icp_lib, cow):
     amd = icp_lib
     m, p = cow

@@ -4,6 +4,9 @@ Cell membership is exact: n_out, every count, and every output point compared wi
 reference partition's cell of the same rank.  A mean must satisfy the any-order bound
 |mean - mean_longdouble| <= (L + 1) 2^-53 max_i |x_i| per axis (voxel_ref.mean_bound), which holds for
 any summation order plus the division: no measured tolerance.
+
+The bits are the header's too (item 4, the order of the sum): every mean equals voxel_ref.rule_means, a
+plain numpy restatement of the rule, as uint64 -- whichever of the kernel's three forms took the cell.
 """
 import ctypes as C
 
@@ -20,11 +23,13 @@ _REF = {}
 
 
 def ref(name):
-    """(xyz, voxel, origin, means longdouble, counts, bound): computed once, shared, never changed."""
+    """(xyz, voxel, origin, means longdouble, counts, bound, the order rule's means): computed once, shared,
+    never changed."""
     if name not in _REF:
         xyz, voxel, origin = V.case(name)
         mean, counts, rank = V.downsample_ref(xyz, voxel, origin)
-        _REF[name] = (xyz, voxel, origin, mean, counts, V.mean_bound(xyz, rank, counts))
+        _REF[name] = (xyz, voxel, origin, mean, counts, V.mean_bound(xyz, rank, counts),
+                      V.rule_means(xyz, rank, counts.size))
     return _REF[name]
 
 
@@ -40,12 +45,14 @@ def device_form(ctx, xyz, voxel, origin):
     cnt = torch.full((xyz.shape[0],), -7, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     k = ctx.voxel_downsample_device(d.data_ptr(), xyz.shape[0], voxel, out.data_ptr(), origin, cnt.data_ptr())
-    return out.cpu().numpy()[:k], cnt.cpu().numpy()[:k]
+    out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
+    assert (out[k:] == -7.0).all() and (cnt[k:] == -7).all()  # (nothing past the outputs)
+    return out[:k], cnt[:k]
 
 
-@pytest.mark.parametrize("name", V.CASES)
+@pytest.mark.parametrize("name", V.CASES + V.BIG_CASES)
 def test_matches_reference(ctx, name):
-    xyz, voxel, origin, mean, counts, bound = ref(name)
+    xyz, voxel, origin, mean, counts, bound = ref(name)[:6]
     got, got_counts = ctx.voxel_downsample(xyz, voxel, origin, counts=True)
     assert got.shape[0] == counts.size
     assert np.array_equal(got_counts, counts)
@@ -57,7 +64,45 @@ def test_matches_reference(ctx, name):
     assert np.array_equal(ctx.voxel_downsample(xyz, voxel, origin).view(np.uint64), got.view(np.uint64))
 
 
-@pytest.mark.parametrize("name", ["n1", "n4097", "one_cell4097", "one_cell70000", "mixed", "wide", "shared_a", "cow"])
+@pytest.mark.parametrize("name", V.CASES + V.BIG_CASES)
+def test_means_follow_the_order_rule(ctx, name):
+    """The promised bits: chunks of 1,024, 64 lane sums from +0, the xor butterfly, the chunk sums in
+    order from +0, one division -- not merely some order inside the any-order bound."""
+    xyz, voxel, origin, _, counts, _, rule = ref(name)
+    got, got_counts = ctx.voxel_downsample(xyz, voxel, origin, counts=True)
+    assert got.shape[0] == counts.size
+    assert np.array_equal(got_counts, counts)
+    differ = (got.view(np.uint64) != rule.view(np.uint64)).any(axis=1)
+    print(f"{name}: n_out {got.shape[0]}, largest cell {got_counts.max()}, {int(differ.sum())} cells differ from the rule"
+          + (f" (lengths {sorted(set(counts[differ].tolist()))[:20]})" if differ.any() else ""))
+    assert not differ.any()
+
+
+@pytest.mark.parametrize("name", ["lengths", "wide48"])
+def test_device_form_writes_nothing_past_the_outputs(ctx, name):
+    """Rows n_out .. n - 1 of xyz_out and count_out keep their fill (device_form checks it), and the
+    rows before them are the rule's."""
+    xyz, voxel, origin, _, counts, _, rule = ref(name)
+    d, cd = device_form(ctx, xyz, voxel, origin)
+    assert d.shape[0] == counts.size < xyz.shape[0]
+    assert np.array_equal(cd, counts) and np.array_equal(d.view(np.uint64), rule.view(np.uint64))
+
+
+def test_sums_start_from_plus_zero(ctx):
+    """A cell of three points (the eight-lane form) and one of 70 (the whole wave), x = -0.0 throughout:
+    the mean's x has the bits of +0.0."""
+    xyz, voxel, origin = V.negative_zero_case()
+    _, counts, rank = V.downsample_ref(xyz, voxel, origin)
+    got, got_counts = ctx.voxel_downsample(xyz, voxel, origin, counts=True)
+    assert got_counts.tolist() == counts.tolist() == [3, 70]
+    assert got[:, 0].view(np.uint64).tolist() == [0, 0]
+    assert np.array_equal(got.view(np.uint64), V.rule_means(xyz, rank, 2).view(np.uint64))
+    d, _ = device_form(ctx, xyz, voxel, origin)
+    assert np.array_equal(d.view(np.uint64), got.view(np.uint64))
+
+
+@pytest.mark.parametrize("name", ["n1", "n4097", "one_cell4097", "one_cell70000", "mixed", "wide", "shared_a", "cow",
+                                  "lengths", "long_many", "wide63"])
 def test_forms_and_calls_give_the_same_bits(ctx, name):
     xyz, voxel, origin = ref(name)[:3]
     a, ca = ctx.voxel_downsample(xyz, voxel, origin, counts=True)
