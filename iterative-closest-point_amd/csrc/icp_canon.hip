@@ -280,7 +280,9 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_kernel(const double *
 // of one): workgroup k computes column k exactly as canon_fold_kernel does (thread t's rows in
 // order, the wave trees, the 8 waves' pairwise tree: the same bits).  MODE 1: the last workgroup
 // to finish (a relaxed ticket after write-through column sums, icp_fold.h's hand-off) runs the error step and
-// the Horn step on the 18 sums.  MODE 0: the sums only (several ranks: the all-reduce follows).
+// the Horn step on the 18 sums; the error step's host side, while the run goes on, leaves from
+// the residual column's workgroup as soon as that column is summed (below).  MODE 0: the sums
+// only (several ranks: the all-reduce follows).
 //
 // Workgroups 18 .. 25 (launched only with a table to build, IterOrder::order): workgroup 18 + k
 // builds XCD k's part of the next fused launch's dispatch order (icp_kernels.h, IterOrder) from
@@ -383,6 +385,35 @@ __device__ __forceinline__ void iter_order_build(const IterOrder &o, int k)
     }
 }
 
+// canon_row_value of rows r0, r0 + 512, ... (U of them; a row past R 0.0) with every load issued
+// before the first is waited for: the loads are unconditional, their indices clamped into the
+// column, and the conditions select afterwards.  (A load under a condition becomes a branch
+// around it and a wait for it where it stands: one memory round trip a row.)  The same bits.
+template <int U>
+__device__ __forceinline__ void canon_row_values(const double *__restrict__ col, int S, int R, int r0, double (&v)[U])
+{
+    if (S <= 0) {
+        double q[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) q[u] = col[min(r0 + u * kFoldThreads, R - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = r0 + u * kFoldThreads < R ? q[u] : 0.0;
+        return;
+    }
+    double q[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[u][j] = col[min(4 * (r0 + u * kFoldThreads) + j, S - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int s = 4 * (r0 + u * kFoldThreads);
+        const double a = q[u][0], b = s + 1 < S ? q[u][1] : 0.0, c = s + 2 < S ? q[u][2] : 0.0,
+                     d = s + 3 < S ? q[u][3] : 0.0;
+        v[u] = r0 + u * kFoldThreads < R ? (a + b) + (c + d) : 0.0;
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const double *__restrict__ rows, int R,
                                                                        double *__restrict__ sums, CanonStep cs, int S,
@@ -393,19 +424,30 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const dou
         return;
     }
     __shared__ double sh[kFoldThreads / 64];
-    __shared__ double s_sum[kCanonCols];
     __shared__ int s_last;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = blockIdx.x;
     const double *col = rows + (size_t)k * (S > 0 ? S : R);
     double a = 0.0;
-    constexpr int U = 4; // (as canon_fold_kernel: rows t, t + 512, ... in order, R <= 4,096)
+    // MODE 1: the error step's host side leaves from lane 0 of wave 1 of the residual's workgroup as
+    // soon as that column is summed (err_publish_running), not from the last workgroup's thread 0
+    // after every ticket, the 18 loads and the step: the posted host writes and their release
+    // drain while the other columns arrive and the Horn step runs.  The state's words are in its
+    // registers before the first barrier, so before this workgroup's ticket and any step.
+    const bool early = MODE == 1 && k == kSumErr && threadIdx.x == 64;
+    int e_done = 1, e_iter = 0, e_far = 0, e_queued2 = 0;
+    if (early) {
+        e_done = cs.s->done;
+        e_iter = cs.s->iter;
+        e_far = cs.s->far_acc;
+        e_queued2 = cs.s->queued2;
+    }
+    // (as canon_fold_kernel: rows t, t + 512, ... in order, R <= 4,096 -- here every row's loads
+    // in one batch, up to 32 a thread: canon_row_values)
+    constexpr int U = 8;
+    static_assert(kCanonStrandsMax / 4 <= U * kFoldThreads, "one pass of the fold's rows");
     for (int r0 = threadIdx.x; r0 < R; r0 += U * kFoldThreads) {
         double v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int r = r0 + u * kFoldThreads;
-            v[u] = r < R ? canon_row_value(col, S, r) : 0.0;
-        }
+        canon_row_values<U>(col, S, R, r0, v);
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (r0 + u * kFoldThreads < R) a = a + v[u];
@@ -413,8 +455,9 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const dou
     const double w = wave_tree_halves(a);
     const double two = lane_value(w, 31) + lane_value(w, 63);
     if (lane == 0) sh[wave] = two;
+    if (early) asm volatile("s_waitcnt vmcnt(0)" ::"v"(e_done), "v"(e_iter), "v"(e_far), "v"(e_queued2) : "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
+    auto waves_sum = [&] { // (the 8 waves' sums, pairwise)
         double t[kFoldThreads / 64];
 #pragma unroll
         for (int i = 0; i < kFoldThreads / 64; ++i) t[i] = sh[i];
@@ -422,7 +465,10 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const dou
         for (int span = 1; span < kFoldThreads / 64; span <<= 1)
 #pragma unroll
             for (int i = 0; i < kFoldThreads / 64; i += 2 * span) t[i] = t[i] + t[i + span];
-        pub_store(sums + k, t[0]); // (write-through: the hand-off of icp_fold.h, no release fence)
+        return t[0];
+    };
+    if (threadIdx.x == 0) {
+        pub_store(sums + k, waves_sum()); // (write-through: the hand-off of icp_fold.h, no release fence)
         if (MODE == 0 && k == 0) // (several ranks: the far count rides on the all-reduce)
             sums[kSumFar] = (double)__hip_atomic_load(&cs.s->far_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (MODE != 0) {
@@ -433,16 +479,23 @@ __global__ __launch_bounds__(kFoldThreads) void canon_fold_cols_kernel(const dou
     }
     if constexpr (MODE == 0) return;
     __syncthreads();
+    if (early)
+        err_publish_running(waves_sum(), cs.N, cs.threshold, cs.max_iter, e_done, e_iter, e_far, e_queued2, cs.hflag,
+                            cs.ticket, cs.h_state, cs.h_trace);
     if (!s_last || threadIdx.x != 0) return;
     // every column's sum by write-through-coherent loads: no agent-scope release / acquire fences
     // (their L2 write-back and invalidate; with the mirror's fewer host writes, icp_fold.h, the fold
-    // is 10.7 -> 10.1 us at C4, profiles/r06/r06fold3/)
-    for (int i = 0; i < kCanonCols; ++i) s_sum[i] = pub_load(sums + i);
+    // is 10.7 -> 10.1 us at C4, profiles/r06/r06fold3/).  All 18 are issued before the first is
+    // used: an atomic load stored straight to LDS is waited for before the next is issued, 18
+    // dependent round trips (profiles/r11/).  They stay in registers: the steps are this thread's.
+    double t[kCanonCols];
+#pragma unroll
+    for (int i = 0; i < kCanonCols; ++i) t[i] = pub_load(sums + i);
     __hip_atomic_store(cs.fold_ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the next iteration's ticket)
     if constexpr (MODE == 1)
-        err_step_body(s_sum, cs.N, cs.threshold, cs.max_iter, cs.err_trace, cs.s, cs.hflag, cs.ticket, cs.h_state,
-                      cs.h_trace);
-    horn_step_body(s_sum, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s, true);
+        err_step_body(t, cs.N, cs.threshold, cs.max_iter, cs.err_trace, cs.s, cs.hflag, cs.ticket, cs.h_state,
+                      cs.h_trace, false, -1, true);
+    horn_step_body(t, cs.N, cs.c[0], cs.c[1], cs.c[2], 1, cs.cnt, cs.s, true);
 }
 
 } // namespace

@@ -99,35 +99,65 @@ __device__ __forceinline__ void horn_step_body(const double *__restrict__ sums, 
 
 __device__ __forceinline__ void err_step_body(const double *__restrict__ sums, double N, double threshold, int max_iter,
                               double *__restrict__ err_trace, IterState *__restrict__ s, int *hflag, int ticket,
-                              IterState *h_state, double *h_trace, bool far_coherent = false, int far_global = -1)
+                              IterState *h_state, double *h_trace, bool far_coherent = false, int far_global = -1,
+                              bool running_published = false)
 {
-    if (!s->done) {
+    // The state's four words the step reads, loaded together: one memory round trip when s is
+    // global, not three dependent ones (done; then iter; then, the run going on, the two counts)
+    // (far_coherent: s is global and this launch's workgroups added to s->far_acc -- a fused
+    // transform -- so its count is read at agent scope; s may be an LDS copy otherwise)
+    int done = s->done, iter = s->iter;
+    const int queued2 = s->queued2;
+    const int far_acc = far_coherent ? __hip_atomic_load(&s->far_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s->far_acc;
+    asm volatile("" ::"v"(queued2), "v"(far_acc)); // (here: the compiler sinks a load used under one condition below it)
+    if (!done) {
         const double e = sums[kSumErr];
         const double err = (e + e) / N; // gpu.cc:71-76: find_alignment's residual is the same sum
-        err_trace[s->iter] = err;
-        h_trace[s->iter] = err; // mapped host copies: the run's result needs no copy back
-        s->iter += 1;
-        if (err < threshold || s->iter >= max_iter) s->done = 1; // gpu.cc:79-80
+        err_trace[iter] = err;
+        iter += 1;
+        s->iter = iter;
+        if (err < threshold || iter >= max_iter) s->done = done = 1; // gpu.cc:79-80
+        if (running_published && !done) return; // (the host side is err_publish_running's, on another wave)
+        h_trace[iter - 1] = err; // mapped host copies: the run's result needs no copy back
         // the mirror: every field once the run is done (the result: iter, srt, nn_counts); before
         // that only what the host reads while the run goes on (the policy's far_acc and queued2) --
         // each field is a posted write over the host link that the ticket's release waits for
-        if (s->done) {
+        if (done) {
             const int *src = (const int *)s;
             int *dst = (int *)h_state;
             for (size_t k = 0; k < sizeof(IterState) / sizeof(int); ++k) dst[k] = src[k];
+            if (far_coherent) h_state->far_acc = far_acc;
         } else {
-            h_state->iter = s->iter;
-            h_state->far_acc = s->far_acc;
-            h_state->queued2 = s->queued2;
+            h_state->iter = iter;
+            h_state->far_acc = far_acc;
+            h_state->queued2 = queued2;
         }
-        // (far_coherent: s is global and this launch's workgroups added to s->far_acc -- a fused
-        // transform -- so its count is read at agent scope; s may be an LDS copy otherwise)
-        if (far_coherent) h_state->far_acc = __hip_atomic_load(&s->far_acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (far_global >= 0) h_state->far_acc = far_global; // (all ranks' count: sums[kSumFar] after the all-reduce)
     }
     // (done, iter) to the host (mapped memory), then the ticket the host spins on
-    __hip_atomic_store(hflag, s->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(hflag + 1, s->iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(hflag, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(hflag + 1, iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(hflag + 2, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The host side of an error step that leaves the run going, from the values the step will read
+// (the state's words loaded before any thread steps it, the residual's sum): what err_step_body
+// writes to the host then, bit for bit, and nothing on the device.  A step that ends the run, or
+// finds it ended, is published by the thread that steps it (running_published), whole mirror
+// and all; both take the decision by the same arithmetic from the same values.
+__device__ __forceinline__ void err_publish_running(double e, double N, double threshold, int max_iter, int done, int iter,
+                                                    int far_acc, int queued2, int *hflag, int ticket,
+                                                    IterState *h_state, double *h_trace)
+{
+    if (done) return;
+    const double err = (e + e) / N;
+    if (err < threshold || iter + 1 >= max_iter) return;
+    h_trace[iter] = err;
+    h_state->iter = iter + 1;
+    h_state->far_acc = far_acc;
+    h_state->queued2 = queued2;
+    __hip_atomic_store(hflag, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(hflag + 1, iter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(hflag + 2, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
