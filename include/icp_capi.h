@@ -316,6 +316,31 @@ int icp_set_robust(icp_ctx *ctx, int kind, double k);
  * ICP_E_NO_MODEL if no robust run has happened since icp_set_scene. */
 int icp_get_robust_trace(icp_ctx *ctx, double *wsum_out, long long *active_out, size_t cap);
 
+/* ---- partial overlap without a length: the trimmed fraction ----------------- */
+/* 0 < fraction < 1: every iteration of icp_run keeps the T pairs with the smallest d2 (trimmed
+ * ICP, Chetverikov et al.; PCL's CorrespondenceRejectorTrimmed), the expected overlap fraction
+ * instead of a length in the clouds' units.  T = max(1, (long long)(fraction * (double)np_total)):
+ * the product in fp64 as written, truncated, once on the host.  With d2_j = (dx*dx + dy*dy) + dz*dz
+ * between scene point j and its correspondence (the gate's own value, under either metric), C is
+ * the T-th smallest d2 over all ranks (1-based), selected on the device, and pair j is kept when
+ * d2_j <= min(D, C), D = dmax * dmax of icp_set_max_distance or +inf when the gate is off.  Ties at
+ * C are all kept: K >= T when the trim binds, K does not depend on the points' order or the number
+ * of ranks, and no index breaks a tie.  Everything after the cut is the gated loop's: N = K (W with
+ * robust weights, which apply to the kept pairs), every point moves, err = (e + e) / K, and K below
+ * the metric's least count (4 / 6) stops the run before it changes anything with
+ * ICP_E_TOO_FEW_POINTS; so does T below it, and icp_last_error names the iteration, K and T.  A
+ * trimmed run counts as a gated one for icp_get_inliers / icp_get_inlier_trace (the mask and K of
+ * min(D, C)), and always takes the launch loop (ICP_RUN_LAUNCHES), whatever icp_set_run_mode says.
+ * fraction == 1 switches the trim off (the default: icp_run exactly as without this call);
+ * fraction <= 0, > 1 or NaN is ICP_E_ARG and leaves the earlier setting.  The setting survives
+ * icp_set_scene / icp_set_model. */
+int icp_set_trim(icp_ctx *ctx, double fraction);
+/* C of each recorded iteration of the last trimmed icp_run, the selected d2 itself (before the
+ * min with the gate; every rank reports the same bits): writes min(cap, iterations) entries
+ * (cut_d2_out may be NULL when cap is 0) and returns the number of recorded iterations (>= 0), or
+ * ICP_E_NO_MODEL if no trimmed run has happened since icp_set_scene. */
+int icp_get_trim_trace(icp_ctx *ctx, double *cut_d2_out, size_t cap);
+
 /* ---- normals estimated from the model itself: grid k-NN and PCA ------------ */
 /* The k nearest model points of every point of the resident model, searched over the model's grid.
  * 1. Neighbour set.  With d = m_j - m_i and d2 = (dx*dx + dy*dy) + dz*dz in fp64 exactly as written,
@@ -511,6 +536,12 @@ int icp_get_model_order(icp_ctx *ctx, int32_t *kd_out);
  * the keys in that order.  Host arrays; runs on `device` (synchronous).  ICP_E_ARG for bits
  * outside [0, 32] or n > INT_MAX. */
 int icp_sort_pairs(int device, const uint32_t *keys, size_t n, int bits, uint32_t *keys_out, int32_t *order_out);
+/* The engine's radix select (icp_select.hip: the cut of a trimmed icp_run; the same kernels),
+ * exposed for its tests: *out = the k-th smallest (1-based) of the n host doubles v in the total
+ * order -inf < ... < -0 < +0 < ... < +inf < NaN; every NaN is equal and last, and is returned as a
+ * quiet NaN.  Runs on `device` (synchronous).  ICP_E_ARG for a null pointer, n == 0, n > INT_MAX,
+ * k == 0 or k > n. */
+int icp_select_kth(int device, const double *v, size_t n, size_t k, double *out);
 /* The resident model's uniform grid (icp_grid.hip: launch_grid_build), exposed for its tests:
  * g = the cells per axis, lo = the grid's origin, *inv_h = 1 / cell size (a point's cell per axis is
  * clamp(floor((x - lo) * inv_h), 0, g - 1), its id (cz * g[1] + cy) * g[0] + cx); start (nullable,

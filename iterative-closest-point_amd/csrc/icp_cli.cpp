@@ -14,6 +14,9 @@
 //   --threshold X      convergence threshold (default 1e-5, src/cpu.hh:113)
 //   --max-dist X       max correspondence distance: pairs farther apart than X are left out of
 //                      each iteration's alignment and error (partial overlap; default: none)
+//   --trim F           trimmed ICP (icp_set_trim): each iteration keeps the fraction F (0 < F <= 1) of the
+//                      pairs with the smallest distances, the expected overlap; combines with --max-dist,
+//                      --normals, --robust and --pyramid (each level trimmed by the same fraction)
 //   --normals FILE     the model's normals, a CSV in the clouds' format with one row per model point:
 //                      selects the point-to-plane metric (combines with --max-dist; no scale)
 //   --estimate-normals K  the model's normals estimated from its own K nearest neighbours (3 <= K <= 64,
@@ -58,7 +61,7 @@ int main(int argc, char **argv)
     const char *prog = std::strrchr(argv[0], '/') ? std::strrchr(argv[0], '/') + 1 : argv[0];
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
-        std::printf("       options: [--max-dist X] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
+        std::printf("       options: [--max-dist X] [--trim F] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
         return -1;
@@ -69,7 +72,7 @@ int main(int argc, char **argv)
     int rule = std::strcmp(prog, "icp") == 0 ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
     double threshold = 1e-5, max_dist = 0.0;
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
-    const char *robust = nullptr, *robust_k = nullptr;
+    const char *robust = nullptr, *robust_k = nullptr, *trim = nullptr;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
@@ -81,6 +84,7 @@ int main(int argc, char **argv)
             rule = !std::strcmp(argv[a], "cpu") ? ICP_NN_RULE_CPU_SQRT : ICP_NN_RULE_SQUARED;
         } else if (!std::strcmp(argv[a], "--threshold") && a + 1 < argc) threshold = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--max-dist") && a + 1 < argc) max_dist = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--trim") && a + 1 < argc) trim = argv[++a];
         else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
         else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
@@ -117,6 +121,15 @@ int main(int argc, char **argv)
         return -1;
     }
 
+    double trim_fraction = 1.0;
+    if (trim) {
+        char *end = nullptr;
+        trim_fraction = std::strtod(trim, &end);
+        if (end == trim || *end) {
+            std::fprintf(stderr, "[error] --trim: %s is not a number\n", trim);
+            return -1;
+        }
+    }
     // the robust weights' options: a kind and its scale come together
     int robust_kind = ICP_ROBUST_NONE;
     double robust_scale = 0.0;
@@ -209,6 +222,10 @@ int main(int argc, char **argv)
     icp_set_nn_rule(ctx, rule);
     if ((rc = icp_set_max_distance(ctx, max_dist)) != ICP_OK) {
         std::fprintf(stderr, "[error] --max-dist: %s\n", icp_strerror(rc));
+        return 3;
+    }
+    if ((rc = icp_set_trim(ctx, trim_fraction)) != ICP_OK) {
+        std::fprintf(stderr, "[error] --trim: %s (a fraction in (0, 1])\n", icp_strerror(rc));
         return 3;
     }
     if ((rc = icp_set_robust(ctx, robust_kind, robust_scale)) != ICP_OK) {

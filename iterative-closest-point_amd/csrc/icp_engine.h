@@ -293,6 +293,20 @@ struct icp_ctx {
     bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
     long long gate_K = 0;
     std::vector<long long> gate_ktrace;
+    // The trim (icp_set_trim): the fraction (1: off); per run the scene's d2 keys, the selection's
+    // bins (integers; as doubles on their way through the all-reduce), its state and the
+    // iteration's cut C (icp_select.hip), the mapped C trace beside the K trace; and what
+    // icp_get_trim_trace reports, saved at the end of the last trimmed run (dropped with the scene).
+    double trim_fraction = 1.0;
+    unsigned long long *trim_keys = nullptr;
+    size_t trim_keys_cap = 0;
+    unsigned *trim_bins = nullptr;
+    double *trim_bins_d = nullptr, *trim_cut = nullptr;
+    SelectState *trim_state = nullptr;
+    double *h_ctrace = nullptr, *d_ctrace = nullptr;
+    size_t ctrace_cap = 0;
+    bool trim_have = false;
+    std::vector<double> trim_ctrace;
     // Robust weights (icp_set_robust): the kind (ICP_ROBUST_*; 0: off), k and k2 = k * k (fp64, once),
     // the mapped W / K+ traces beside the K trace (grown with it), and what icp_get_robust_trace
     // reports, saved at the end of the last robust run (dropped with the scene).

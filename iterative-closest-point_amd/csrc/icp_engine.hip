@@ -956,7 +956,9 @@ int allreduce(icp_ctx *ctx, double *buf, size_t count)
     }
     if (ctx->world <= 1) return ICP_OK;
     if (!ctx->host_reduce) return fail(ctx, ICP_E_ARG, "world_size > 1 without a communicator");
-    double tmp[32];
+    double few[32];
+    std::vector<double> many(count > 32 ? count : 0); // (the selection's bins: kSelectBins doubles)
+    double *tmp = count > 32 ? many.data() : few;
     HIPCHK(hipMemcpyAsync(tmp, buf, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
     if (ctx->host_reduce(tmp, count, ctx->host_reduce_user) != 0)
@@ -1263,7 +1265,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
                     (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
-                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt})
+                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->trim_keys,
+                    (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
@@ -1274,6 +1277,7 @@ void icp_ctx_destroy(icp_ctx *ctx)
     if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
     if (ctx->h_wtrace) (void)hipHostFree(ctx->h_wtrace);
     if (ctx->h_ptrace) (void)hipHostFree(ctx->h_ptrace);
+    if (ctx->h_ctrace) (void)hipHostFree(ctx->h_ctrace);
     if (ctx->h_few) (void)hipHostFree(ctx->h_few);
     if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
     if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
@@ -1354,6 +1358,23 @@ int icp_get_inlier_trace(icp_ctx *ctx, long long *counts_out, size_t cap)
     const size_t k = std::min(cap, ctx->gate_ktrace.size());
     if (k) std::memcpy(counts_out, ctx->gate_ktrace.data(), sizeof(long long) * k);
     return (int)ctx->gate_ktrace.size();
+}
+
+int icp_set_trim(icp_ctx *ctx, double fraction)
+{
+    if (!ctx || !(fraction > 0.0) || !(fraction <= 1.0)) return ICP_E_ARG; // (a NaN fails both)
+    ctx->trim_fraction = fraction;
+    return ICP_OK;
+}
+
+int icp_get_trim_trace(icp_ctx *ctx, double *cut_d2_out, size_t cap)
+{
+    if (!ctx || (!cut_d2_out && cap)) return ICP_E_ARG;
+    if (!ctx->has_scene || !ctx->trim_have)
+        return fail(ctx, ICP_E_NO_MODEL, "no trimmed icp_run since icp_set_scene (icp_set_trim)");
+    const size_t k = std::min(cap, ctx->trim_ctrace.size());
+    if (k) std::memcpy(cut_d2_out, ctx->trim_ctrace.data(), sizeof(double) * k);
+    return (int)ctx->trim_ctrace.size();
 }
 
 int icp_set_robust(icp_ctx *ctx, int kind, double k)
@@ -1861,6 +1882,7 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
     ctx->seedd_valid = false;
     ctx->gate_have = false;
     ctx->robust_have = false;
+    ctx->trim_have = false;
     ctx->q_order_src = nullptr; // new contents: a new query order
     ctx->scene_slot = slot;     // (else in the caller's order)
     ctx->scene_revert = false;
@@ -2500,6 +2522,29 @@ int icp_sort_pairs(int device, const uint32_t *keys, size_t n, int bits, uint32_
               icp::sort_pairs_u32(buf + 3 * kb, temp, k0, k1, nullptr, v1, (int)n, bits, nullptr) == hipSuccess &&
               hipMemcpy(order_out, v1, n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
               (!keys_out || hipMemcpy(keys_out, k1, n * 4, hipMemcpyDeviceToHost) == hipSuccess);
+    ok = hipFree(buf) == hipSuccess && ok;
+    return ok ? ICP_OK : ICP_E_HIP;
+}
+
+int icp_select_kth(int device, const double *v, size_t n, size_t k, double *out)
+{
+    if (!v || !out || n == 0 || n > (size_t)INT_MAX || k == 0 || k > n) return ICP_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return ICP_E_HIP;
+    // one allocation: the values, their keys, the bins, the state, the result
+    const size_t vb = (n * 8 + 255) & ~(size_t)255, bb = sizeof(unsigned) * icp::kSelectBins;
+    char *buf = nullptr;
+    if (hipMalloc(&buf, 2 * vb + bb + 256 + 256) != hipSuccess) return ICP_E_HIP;
+    double *dv = (double *)buf;
+    unsigned long long *keys = (unsigned long long *)(buf + vb);
+    unsigned *bins = (unsigned *)(buf + 2 * vb);
+    icp::SelectState *state = (icp::SelectState *)(buf + 2 * vb + bb);
+    double *cut = (double *)(buf + 2 * vb + bb + 256);
+    bool ok = hipMemcpy(dv, v, n * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemset(bins, 0, bb) == hipSuccess;
+    if (ok) {
+        icp::launch_select_map(dv, (int)n, keys, nullptr);
+        icp::launch_select_kth(keys, (int)n, (unsigned long long)k, state, nullptr, bins, cut, nullptr, nullptr, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(out, cut, sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
     ok = hipFree(buf) == hipSuccess && ok;
     return ok ? ICP_OK : ICP_E_HIP;
 }

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
     const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
     double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
-    const double4 *__restrict__ m4kd)
+    const double4 *__restrict__ m4kd, const double *__restrict__ cut)
 {
     if (st->done != 0) return;
     const double cp0 = st->shift_p[0], cp1 = st->shift_p[1], cp2 = st->shift_p[2];
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
 #pragma unroll
     for (int k = 0; k < 17; ++k) a[k] = 0.0;
     double kept = 0.0;
-    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
                          [&](long long, double q0, double q1, double q2, const double4 &m, double, double, double)
                              __attribute__((always_inline)) {
                                  shifted_moment_terms(q0, q1, q2, m, cp0, cp1, cp2, cy0, cy1, cy2, a);
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void robust_gated_moments_kernel(
     const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
     double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
-    const double4 *__restrict__ m4kd, double k, double k2)
+    const double4 *__restrict__ m4kd, double k, double k2, const double *__restrict__ cut)
 {
     if (st->done != 0) return;
     const double cp[3] = {st->shift_p[0], st->shift_p[1], st->shift_p[2]};
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void robust_gated_moments_kernel(
     double a[kRobustGateSums];
 #pragma unroll
     for (int j = 0; j < kRobustGateSums; ++j) a[j] = 0.0;
-    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
                          [&](long long, double q0, double q1, double q2, const double4 &m, double dx, double dy, double dz)
                              __attribute__((always_inline)) {
                                  const double w = robust_weight<KIND>((dx * dx + dy * dy) + dz * dz, k, k2);
@@ -99,13 +99,14 @@ __global__ __launch_bounds__(kBlock) void robust_gated_moments_kernel(
 // too-few status (kept_stop); else Horn's closed form over the kept pairs, N = K.
 // WIDTH = kRobustGateSums, the weighted rows: K+ < 4 freezes the run as well, N = W, and a solved
 // iteration's W and K+ join their mapped traces (the error step records that iteration's K and error).
+// trim_few: the trim's T is below the least count (icp_set_trim), which stops the run like K.
 template <int WIDTH>
 __device__ __forceinline__ void gated_horn_body(const double *__restrict__ partials, int nblocks,
                                                 double *__restrict__ sums, int step, double c0, double c1, double c2,
                                                 int *__restrict__ cnt, IterState *__restrict__ s,
                                                 GateState *__restrict__ g, GateState *__restrict__ h_g,
                                                 IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
-                                                long long *__restrict__ h_ptrace)
+                                                long long *__restrict__ h_ptrace, int trim_few)
 {
     constexpr bool kRobust = WIDTH == kRobustGateSums;
     __shared__ double res[WIDTH];
@@ -120,7 +121,7 @@ __device__ __forceinline__ void gated_horn_body(const double *__restrict__ parti
     if (!s->done) { // (a frozen iteration's sums are stale: its gate was not evaluated)
         g->K = (long long)K;
         h_g->K = (long long)K;
-        bool few = !(K >= 4.0);
+        bool few = !(K >= 4.0) || trim_few != 0;
         if constexpr (kRobust) {
             const double W = res[kRobustGateW], Kpos = res[kRobustGateKpos];
             g->W = W;
@@ -142,18 +143,19 @@ __global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__rest
                                                             double *__restrict__ sums, int step, double c0, double c1,
                                                             double c2, int *__restrict__ cnt, IterState *__restrict__ s,
                                                             GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                            IterState *__restrict__ h_state)
+                                                            IterState *__restrict__ h_state, int trim_few)
 {
-    gated_horn_body<kGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr);
+    gated_horn_body<kGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr,
+                               trim_few);
 }
 
 __global__ __launch_bounds__(kBlock) void robust_gated_horn_kernel(
     const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
     int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
-    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace)
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
     gated_horn_body<kRobustGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
-                                     h_ptrace);
+                                     h_ptrace, trim_few);
 }
 
 // The first gated iteration's shifts, from a pre-pass of the moments around the model's centre c
@@ -227,21 +229,22 @@ __global__ __launch_bounds__(kBlock) void gated_unpack_kernel(const unsigned lon
 void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
                           int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
                           unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready)
+                          const double4 *m4kd, bool y_ready, const double *cut)
 {
     if (y_ready)
         gated_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
-                                                                     partials, kpos, m4kd);
+                                                                     partials, kpos, m4kd, cut);
     else
         gated_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
-                                                                      partials, kpos, m4kd);
+                                                                      partials, kpos, m4kd, cut);
 }
 
 void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st)
+                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
+                       bool trim_few)
 {
     gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
-                                            gate, h_gate, h_state);
+                                            gate, h_gate, h_state, trim_few ? 1 : 0);
 }
 
 void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
@@ -253,33 +256,33 @@ template <int KIND>
 static void robust_gated_moments_of(double k, double k2, const int *idx, const double4 *m4, const double *px,
                                     const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
                                     const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                    hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready)
+                                    hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready, const double *cut)
 {
     if (y_ready)
         robust_gated_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
-                                                                                  D, mask, partials, kpos, m4kd, k, k2);
+                                                                                  D, mask, partials, kpos, m4kd, k, k2, cut);
     else
         robust_gated_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
-                                                                                   D, mask, partials, kpos, m4kd, k, k2);
+                                                                                   D, mask, partials, kpos, m4kd, k, k2, cut);
 }
 
 void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
                                  const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
                                  const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready)
+                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready, const double *cut)
 {
     const auto go = kind == kRobustHuber   ? robust_gated_moments_of<kRobustHuber>
                     : kind == kRobustTukey ? robust_gated_moments_of<kRobustTukey>
                                            : robust_gated_moments_of<kRobustCauchy>;
-    go(k, k2, idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask, partials, st, kpos, m4kd, y_ready);
+    go(k, k2, idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask, partials, st, kpos, m4kd, y_ready, cut);
 }
 
 void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                              double *h_wtrace, long long *h_ptrace, hipStream_t st)
+                              double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few)
 {
     robust_gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
-                                                   st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace);
+                                                   st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace, trim_few ? 1 : 0);
 }
 
 void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st)

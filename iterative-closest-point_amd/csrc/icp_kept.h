@@ -3,6 +3,7 @@
 // files, which hold each metric's own arithmetic and are compiled with IEEE semantics (`d2 <= D`
 // must stay false for a NaN):
 //   kept_pairs_pass   the moments kernels' loop: y, the gate, the mask word, a callable per kept pair
+//   kept_cut          a trimmed iteration's gate: the smaller of D and the cut selected on the device
 //   robust_weight     a kept pair's weight from its squared residual (icp_set_robust)
 //   kept_transform    the transform kernels' body: every point moves, a callable gives a kept
 //                     point's squared residual
@@ -53,6 +54,15 @@ __device__ __forceinline__ void kept_pairs_pass(const int *__restrict__ idx, con
         const unsigned long long word = __ballot(keep);
         if (lane == 0) mask[i >> 6] = word;
     }
+}
+
+// D of an iteration: the gate's, or with a trim (icp_set_trim; cut not null) the smaller of it and
+// the cut the selection left in device memory (icp_select.hip).  A NaN cut leaves D.
+__device__ __forceinline__ double kept_cut(double D, const double *__restrict__ cut)
+{
+    if (!cut) return D;
+    const double C = *cut;
+    return C < D ? C : D;
 }
 
 // The robust weight of a kept pair from its squared residual r2 (icp_set_robust; k2 = k * k from the

@@ -792,6 +792,10 @@ void launch_reduce(const double *partials, int nblocks, int K, double *out, hipS
 // GateState::K); the residual's fold then writes its e there (kSumErr), as in the ungated loop.
 constexpr int kGateSums = 18, kGateCount = 17;
 constexpr int kGateTooFew = 1;
+// A trimmed run (icp_set_trim): the moments' launchers take cut, the device address of the
+// iteration's selected C (icp_select.hip), and keep d2 <= min(D, *cut); null: the gate alone, no
+// read.  The step launchers take trim_few: the trim's T is below the metric's least count, which
+// stops the run as K below it does.
 // Per-run state of a kept-pairs loop (the gated and the point-to-plane one), beside IterState
 // (whose layout every other kernel reads): device copy and mapped host mirror.
 struct GateState {
@@ -807,12 +811,13 @@ struct GateState {
 void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
                           int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
                           unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready);
+                          const double4 *m4kd, bool y_ready, const double *cut = nullptr);
 // nblocks > 0: sums[0..17] = the fold of the partial rows (reduce_kernel's tree); step: K < 4
 // sets done and the too-few status (the loop state mirrored to h_state), else the shifted Horn
 // step with N = K = sums[kGateCount]
 void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st);
+                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
+                       bool trim_few = false);
 // the first gated iteration's shifts: st->shift_p / shift_y (c, from run_init) += the folded
 // pre-pass sums' (p - c) / K and (y - c) / K, the kept pairs' centroids
 void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
@@ -842,12 +847,13 @@ void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t s
 void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
                           const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
                           const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready);
+                          const double4 *m4kd, bool y_ready, const double *cut = nullptr);
 // nblocks > 0: sums[0..27] = the fold of the partial rows (reduce_kernel's tree); step: K < 6 or a
 // degenerate system sets done and the status (the loop state mirrored to h_state), else the solve:
 // s = 1, R = exp([omega]x), t = (c + tau) - R c into the loop state
 void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st);
+                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
+                        bool trim_few = false);
 // p <- R p + t for every point (p32 nullable); partial [sum over the kept points of ((p' - y) . n)^2],
 // n = n4[idx[i]]
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
@@ -867,12 +873,13 @@ constexpr int kRobustPlaneSums = 30, kRobustPlaneW = 28, kRobustPlaneKpos = 29;
 void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
                                  const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
                                  const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready);
+                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready,
+                                 const double *cut = nullptr);
 // launch_gated_horn on rows of 20: K < 4 or K+ < 4 stops the run; else Horn's closed form on the
 // weighted sums with N = W, and h_wtrace[iter] = W, h_ptrace[iter] = K+ (mapped) for that iteration
 void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                              double *h_wtrace, long long *h_ptrace, hipStream_t st);
+                              double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few = false);
 // launch_gated_first_shift for the weighted pre-pass: the shifts += sum w (p - c) / W, sum w (y - c) / W
 void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
 // launch_plane_moments with the weights (r2 = r * r, r the residual along the normal); rows of 30
@@ -880,11 +887,48 @@ void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, 
                                  const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
                                  double *yz, const IterState *st_dev, double D, const double c[3],
                                  unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                 const double4 *m4kd, bool y_ready);
+                                 const double4 *m4kd, bool y_ready, const double *cut = nullptr);
 // launch_plane_solve on rows of 30: K < 6 or K+ < 6 stops the run; the same solve on the weighted sums
 void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
                                int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                               double *h_wtrace, long long *h_ptrace, hipStream_t st);
+                               double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few = false);
+
+// ---- the k-th smallest of n doubles (icp_select.hip; icp_set_trim, icp_select_kth) ---------------
+// An MSB-first radix select over the 64-bit keys of the doubles (the monotone map of their bit
+// patterns, every NaN last): kSelectPasses passes, pass p over the digit that starts at bit
+// kSelectShift[p] and ends below the pass before's (11, 11, 11, 11, 11 and 9 bits), at most
+// kSelectBins bins a pass.
+constexpr int kSelectBins = 2048, kSelectPasses = 6;
+constexpr int kSelectShift[kSelectPasses] = {53, 42, 31, 20, 9, 0};
+struct SelectState {
+    unsigned long long prefix;    // the digits chosen so far, in their places
+    unsigned long long remaining; // the rank sought (1-based) among the keys that carry the prefix
+};
+// keys[i] = the key of v[i]
+void launch_select_map(const double *v, int n, unsigned long long *keys, hipStream_t st);
+// The trimmed iteration's keys pass: y = m[idx] (stored unless y_ready, as launch_gated_moments
+// does), keys[i] = the key of d2_i = (dx*dx + dy*dy) + dz*dz; a no-op once *done
+void launch_select_keys(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz, int n,
+                        double *yx, double *yy, double *yz, const int *done, unsigned long long *keys, hipStream_t st,
+                        const int *kpos, const double4 *m4kd, bool y_ready);
+// bins[d] += the keys whose digit of this pass is d, of those that carry the state's prefix (pass
+// 0: of all); bins: kSelectBins words, zero before the pass.  done: nullable.  n = 0: no launch.
+void launch_select_count(const unsigned long long *keys, int n, int pass, const SelectState *state, const int *done,
+                         unsigned *bins, hipStream_t st);
+// out[d] = (double)bins[d], bins[d] = 0: the bins on their way through the all-reduce
+void launch_select_bins(unsigned *bins, double *out, const int *done, hipStream_t st);
+// One workgroup: the digit whose bin holds the rank sought (pass 0: rank, 1-based; later: the
+// state's) joins the prefix.  bins_reduced (nullable): the all-reduced bins, read instead of bins
+// (which this launch zeroes otherwise).  The last pass writes the selected value to *cut and, with
+// h_trace, to h_trace[s->iter].
+void launch_select_pick(unsigned *bins, const double *bins_reduced, int pass, unsigned long long rank, SelectState *state,
+                        const int *done, double *cut, const IterState *s, double *h_trace, hipStream_t st);
+
+// The whole selection on one rank: *cut = the value of the rank-th smallest key (1-based) of n, and
+// h_trace[s->iter] with h_trace.  Up to kRedSingle keys: one launch of one workgroup, the six passes
+// inside it; more: kSelectPasses x (launch_select_count, launch_select_pick).  bins as above.
+void launch_select_kth(const unsigned long long *keys, int n, unsigned long long rank, SelectState *state, const int *done,
+                       unsigned *bins, double *cut, const IterState *s, double *h_trace, hipStream_t st);
 
 // ---- the model's k nearest neighbours and estimated normals (icp_normals.hip) -------------------
 constexpr int kKnnMinK = 3, kKnnMaxK = 64;

@@ -50,14 +50,14 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, const double *__restrict__ cut)
 {
     if (st->done != 0) return;
     double a[kPlaneSums];
 #pragma unroll
     for (int k = 0; k < kPlaneSums; ++k) a[k] = 0.0;
     kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
         [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
             __attribute__((always_inline)) {
                 const double4 nn = n4[idx[i]]; // (idx is final here whichever search ran: kpos rides beside it)
@@ -90,14 +90,14 @@ __global__ __launch_bounds__(kBlock) void robust_plane_moments_kernel(
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, double k, double k2)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, double k, double k2, const double *__restrict__ cut)
 {
     if (st->done != 0) return;
     double a[kRobustPlaneSums];
 #pragma unroll
     for (int j = 0; j < kRobustPlaneSums; ++j) a[j] = 0.0;
     kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, D, mask, kpos, m4kd,
+        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
         [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
             __attribute__((always_inline)) {
                 const double4 nn = n4[idx[i]];
@@ -178,13 +178,14 @@ __device__ __forceinline__ bool plane_solve(const double *sums, double *A, doubl
 // a degenerate system freezes the run with its status (kept_stop); else s = 1, R, t of the solve.
 // WIDTH = kRobustPlaneSums, the weighted rows: K+ < 6 freezes the run as well, the system solved is
 // the weighted one, and a solved iteration's W and K+ join their mapped traces.
+// trim_few: the trim's T is below the least count (icp_set_trim), which stops the run like K.
 template <int WIDTH>
 __device__ __forceinline__ void plane_solve_body(const double *__restrict__ partials, int nblocks,
                                                  double *__restrict__ sums, int step, double c0, double c1, double c2,
                                                  int *__restrict__ cnt, IterState *__restrict__ s,
                                                  GateState *__restrict__ g, GateState *__restrict__ h_g,
                                                  IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
-                                                 long long *__restrict__ h_ptrace)
+                                                 long long *__restrict__ h_ptrace, int trim_few)
 {
     constexpr bool kRobust = WIDTH == kRobustPlaneSums;
     __shared__ double res[WIDTH];
@@ -202,7 +203,7 @@ __device__ __forceinline__ void plane_solve_body(const double *__restrict__ part
         h_g->K = (long long)K;
         int status = 0;
         double piv = 0.0;
-        bool few = !(K >= 6.0);
+        bool few = !(K >= 6.0) || trim_few != 0;
         if constexpr (kRobust) {
             const double W = res[kRobustPlaneW], Kpos = res[kRobustPlaneKpos];
             g->W = W;
@@ -261,18 +262,19 @@ __global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__res
                                                              double *__restrict__ sums, int step, double c0, double c1,
                                                              double c2, int *__restrict__ cnt, IterState *__restrict__ s,
                                                              GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                             IterState *__restrict__ h_state)
+                                                             IterState *__restrict__ h_state, int trim_few)
 {
-    plane_solve_body<kPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr);
+    plane_solve_body<kPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr,
+                                 trim_few);
 }
 
 __global__ __launch_bounds__(kBlock) void robust_plane_solve_kernel(
     const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
     int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
-    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace)
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
     plane_solve_body<kRobustPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
-                                       h_ptrace);
+                                       h_ptrace, trim_few);
 }
 
 // Every point moves, and the squared residual along the normal, gathered again through idx, is
@@ -303,21 +305,22 @@ void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t s
 void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
                           const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
                           const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready)
+                          const double4 *m4kd, bool y_ready, const double *cut)
 {
     if (y_ready)
         plane_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
-                                                                     c[1], c[2], mask, partials, kpos, m4kd);
+                                                                     c[1], c[2], mask, partials, kpos, m4kd, cut);
     else
         plane_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
-                                                                      c[1], c[2], mask, partials, kpos, m4kd);
+                                                                      c[1], c[2], mask, partials, kpos, m4kd, cut);
 }
 
 void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st)
+                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
+                        bool trim_few)
 {
     plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
-                                             gate, h_gate, h_state);
+                                             gate, h_gate, h_state, trim_few ? 1 : 0);
 }
 
 template <int KIND>
@@ -325,34 +328,34 @@ static void robust_plane_moments_of(double k, double k2, const int *idx, const d
                                     const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
                                     double *yz, const IterState *st_dev, double D, const double c[3],
                                     unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                    const double4 *m4kd, bool y_ready)
+                                    const double4 *m4kd, bool y_ready, const double *cut)
 {
     if (y_ready)
         robust_plane_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(
-            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2);
+            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2, cut);
     else
         robust_plane_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(
-            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2);
+            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2, cut);
 }
 
 void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
                                  const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
                                  double *yz, const IterState *st_dev, double D, const double c[3],
                                  unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                 const double4 *m4kd, bool y_ready)
+                                 const double4 *m4kd, bool y_ready, const double *cut)
 {
     const auto go = kind == kRobustHuber   ? robust_plane_moments_of<kRobustHuber>
                     : kind == kRobustTukey ? robust_plane_moments_of<kRobustTukey>
                                            : robust_plane_moments_of<kRobustCauchy>;
-    go(k, k2, idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c, mask, partials, st, kpos, m4kd, y_ready);
+    go(k, k2, idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c, mask, partials, st, kpos, m4kd, y_ready, cut);
 }
 
 void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
                                int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                               double *h_wtrace, long long *h_ptrace, hipStream_t st)
+                               double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few)
 {
     robust_plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
-                                                    st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace);
+                                                    st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace, trim_few ? 1 : 0);
 }
 
 void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,

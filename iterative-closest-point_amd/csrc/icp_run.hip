@@ -4,8 +4,8 @@
 //   icp_run -> run_loop: run_setup, then per iteration enqueue_canon (a scene in slot order: the
 //              canonical schedule) or enqueue_launches (every other scene: the launch loop),
 //              wait_one for the ring's oldest iteration, the drain and finish_run
-//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance, icp_set_robust) or run_persistent (the
-//              one-launch loops of small clouds) where they apply
+//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim)
+//              or run_persistent (the one-launch loops of small clouds) where they apply
 //   run_knobs / run_test_knobs: every environment switch of the run path (the table in icp_engine.h)
 #include <algorithm>
 #include <chrono>
@@ -681,6 +681,19 @@ int grow_rtrace(icp_ctx *ctx, int max_iter)
     return ICP_OK;
 }
 
+// the mapped C trace of a trimmed run, of at least max_iter entries
+int grow_ctrace(icp_ctx *ctx, int max_iter)
+{
+    if (ctx->ctrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
+    if (ctx->h_ctrace) HIPCHK(hipHostFree(ctx->h_ctrace)); // (the previous run ended with a sync)
+    ctx->h_ctrace = nullptr;
+    ctx->ctrace_cap = 0;
+    const size_t want = (size_t)std::max(max_iter, 64);
+    TRY(mapped_alloc(ctx, &ctx->h_ctrace, &ctx->d_ctrace, sizeof(double) * want));
+    ctx->ctrace_cap = want;
+    return ICP_OK;
+}
+
 // icp_run over the kept pairs: the max-correspondence-distance gate (icp_set_max_distance; kernels
 // in icp_gated.hip), the point-to-plane metric (icp_set_metric; icp_plane.hip), robust weights
 // (icp_set_robust; both files), or any of them together.
@@ -702,6 +715,13 @@ int grow_rtrace(icp_ctx *ctx, int max_iter)
 // (rows of 20 and 30: the sums, K, W = sum w, K+ = #{w > 0}; the pre-pass's shifts divide by W; the
 // step stops on K+ as on K and writes W and K+ to their mapped traces); the transform, the residual
 // and the error step, hence err = (e + e) / K, are the unweighted loop's.
+// With a trim (icp_set_trim) the iteration's gate is min(D, C), C the T-th smallest d2 over all
+// ranks, selected on the device (icp_select.hip) between the search and the moments: a keys pass
+// gathers and stores y and writes each point's d2 key, kSelectPasses passes of count + pick (one
+// launch of one workgroup up to kRedSingle points on one rank) leave C in device memory, and every
+// moments pass then runs in its streamed form with the cut's address.  With ranks each pass's bins are all-reduced before its pick (kSelectPasses more all-reduces an
+// iteration).  T below the metric's least count stops the run as K below it does.  A trimmed run
+// counts as a gated one for icp_get_inliers, and leaves icp_get_trim_trace its C trace.
 int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
              std::chrono::steady_clock::time_point wall0)
 {
@@ -711,8 +731,12 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
     const size_t n = ctx->scene.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
-    const bool gated = ctx->gate_dmax > 0.0;
-    const double D = gated ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
+    const bool trim = ctx->trim_fraction < 1.0;
+    const bool gated = ctx->gate_dmax > 0.0 || trim; // (what icp_get_inliers reports)
+    const double D = ctx->gate_dmax > 0.0 ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
+    // the trim's count, PCL's rule: the product in fp64 as written, truncated, once
+    const long long T = trim ? std::max(1LL, (long long)(ctx->trim_fraction * (double)ctx->np_total)) : 0;
+    const bool trim_few = trim && T < (ctx->metric == ICP_METRIC_POINT_TO_PLANE ? 6 : 4);
     const int robust = ctx->robust_kind; // (ICP_ROBUST_*; 0: the unweighted kernels, as without the setting)
     const double rk = ctx->robust_k, rk2 = ctx->robust_k2;
     const int width = plane ? (robust ? kRobustPlaneSums : kPlaneSums) : (robust ? kRobustGateSums : kGateSums);
@@ -725,6 +749,16 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     if (!ctx->h_kept) TRY(mapped_alloc(ctx, &ctx->h_kept, &ctx->d_kept_mirror, sizeof(GateState)));
     TRY(grow_ktrace(ctx, max_iter));
     if (robust) TRY(grow_rtrace(ctx, max_iter));
+    if (trim) {
+        TRY(grow_ctrace(ctx, max_iter));
+        TRY(grow(ctx, &ctx->trim_keys, &ctx->trim_keys_cap, n));
+        if (!ctx->trim_bins) HIPCHK(hipMalloc((void **)&ctx->trim_bins, sizeof(unsigned) * kSelectBins));
+        if (!ctx->trim_bins_d) HIPCHK(hipMalloc((void **)&ctx->trim_bins_d, sizeof(double) * kSelectBins));
+        if (!ctx->trim_state) HIPCHK(hipMalloc((void **)&ctx->trim_state, sizeof(SelectState)));
+        if (!ctx->trim_cut) HIPCHK(hipMalloc((void **)&ctx->trim_cut, sizeof(double)));
+        HIPCHK(hipMemsetAsync(ctx->trim_bins, 0, sizeof(unsigned) * kSelectBins, ctx->st)); // (each pick leaves them zero)
+    }
+    const double *cut = trim ? ctx->trim_cut : nullptr;
     std::memset(ctx->h_kept, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -737,31 +771,31 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     const auto step = [&](const double *part, int nblocks, bool do_step) {
         if (plane && robust)
             launch_robust_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                                      ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st);
+                                      ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st, trim_few);
         else if (robust)
             launch_robust_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                                     ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st);
+                                     ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st, trim_few);
         else if (plane)
             launch_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                               ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st);
+                               ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st, trim_few);
         else
             launch_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                              ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st);
+                              ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st, trim_few);
     };
     const auto moments = [&](bool y_ready, bool do_step) {
         const int *kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
         if (plane && robust)
             launch_robust_plane_moments(robust, rk, rk2, ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd,
-                                        D, ctx->c, ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+                                        D, ctx->c, ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
         else if (robust)
             launch_robust_gated_moments(robust, rk, rk2, ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D,
-                                        ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+                                        ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
         else if (plane)
             launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c,
-                                 ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+                                 ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
         else
             launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->kept_mask,
-                                 ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready);
+                                 ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
         step(ctx->kept_part, nb, do_step);
     };
     LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
@@ -781,8 +815,29 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             // around c a scan D from the model's centre cancels (D / sigma)^2 of the moments'
             // precision.  Later iterations get their shifts from the Horn step before them.
             const bool pre_pass = !plane && r.enqueued == 0;
+            // The trim's cut: the keys pass (y stored, each point's d2 key), then the selection of
+            // the T-th smallest key over all ranks into *cut; the moments below stream the stored y.
+            if (trim) {
+                launch_select_keys(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, &sd->done, ctx->trim_keys, ctx->st,
+                                   ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
+                LAUNCHCHK("select_keys");
+                if (!ranks) {
+                    launch_select_kth(ctx->trim_keys, (int)n, (unsigned long long)T, ctx->trim_state, &sd->done, ctx->trim_bins,
+                                      ctx->trim_cut, sd, ctx->d_ctrace, ctx->st);
+                    LAUNCHCHK("select_kth");
+                }
+                for (int pass = 0; ranks && pass < kSelectPasses; ++pass) { // (each pass's bins all-reduced before its pick)
+                    launch_select_count(ctx->trim_keys, (int)n, pass, ctx->trim_state, &sd->done, ctx->trim_bins, ctx->st);
+                    launch_select_bins(ctx->trim_bins, ctx->trim_bins_d, &sd->done, ctx->st);
+                    LAUNCHCHK("select_bins");
+                    TRY(allreduce(ctx, ctx->trim_bins_d, kSelectBins));
+                    launch_select_pick(ctx->trim_bins, ctx->trim_bins_d, pass, (unsigned long long)T, ctx->trim_state, &sd->done,
+                                       ctx->trim_cut, sd, ctx->d_ctrace, ctx->st);
+                    LAUNCHCHK("select_pick");
+                }
+            }
             if (pre_pass) {
-                moments(ctx->y_ready, false); // (the fold alone)
+                moments(ctx->y_ready || trim, false); // (the fold alone)
                 LAUNCHCHK("gated_moments (first shifts)");
                 if (ranks) TRY(allreduce(ctx, ctx->sums, width));
                 if (robust) launch_robust_first_shift(sd, ctx->sums, ctx->st);
@@ -791,7 +846,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             }
             // 2-4. the gate, the kept pairs' sums and count, the metric's step
             // (after the pre-pass y = m[idx] is stored: the pass streams it)
-            moments(ctx->y_ready || pre_pass, !ranks);
+            moments(ctx->y_ready || pre_pass || trim, !ranks);
             LAUNCHCHK(plane ? "plane_moments" : "gated_moments");
             if (ranks) {
                 TRY(allreduce(ctx, ctx->sums, width));
@@ -842,22 +897,31 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         ctx->gate_K = hk.K;
         ctx->gate_ktrace.assign(ctx->h_ktrace, ctx->h_ktrace + ctx->h_iter->iter);
     }
+    if (trim && r.enqueued > 0) { // (icp_get_trim_trace: the recorded iterations' C)
+        ctx->trim_have = true;
+        ctx->trim_ctrace.assign(ctx->h_ctrace, ctx->h_ctrace + ctx->h_iter->iter);
+    }
     if (robust && r.enqueued > 0) { // (icp_get_robust_trace: the recorded iterations' W and K+)
         ctx->robust_have = true;
         ctx->robust_wtrace.assign(ctx->h_wtrace, ctx->h_wtrace + ctx->h_iter->iter);
         ctx->robust_ptrace.assign(ctx->h_ptrace, ctx->h_ptrace + ctx->h_iter->iter);
     }
     TRY(finish_run(ctx, threshold, err_trace, res, wall0));
+    const std::string trimmed = trim ? " (the trim keeps T = " + std::to_string(T) + " of " + std::to_string(ctx->np_total) +
+                                           " pairs, ties at the cut included)"
+                                     : std::string();
     if (hk.status == kGateTooFew && robust)
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
                         " pairs, K+ = " + std::to_string(hk.Kpos) + " of them with a robust weight > 0; " +
-                        (plane ? "the point-to-plane metric needs at least 6 of both" : "need at least 4 of both"));
+                        (plane ? "the point-to-plane metric needs at least 6 of both" : "need at least 4 of both") + trimmed);
     if (hk.status == kGateTooFew)
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
                         (plane ? " pairs; the point-to-plane metric needs at least 6"
-                               : " pairs within the max correspondence distance; need at least 4"));
+                               : trim ? " pairs; need at least 4"
+                                      : " pairs within the max correspondence distance; need at least 4") +
+                        trimmed);
     if (hk.status == kPlaneDegenerate) {
         char piv[32];
         std::snprintf(piv, sizeof(piv), "%.3g", hk.min_pivot);
@@ -1144,9 +1208,9 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     r.threshold = threshold;
     TRY(run_setup_buffers(r));
     *handed = true;
-    // icp_set_metric, icp_set_max_distance, icp_set_robust: the kept-pairs loop (never the one-launch kernels or the
+    // icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim: the kept-pairs loop (never the one-launch kernels or the
     // fused iterations)
-    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0 || ctx->robust_kind != 0)
+    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0 || ctx->robust_kind != 0 || ctx->trim_fraction < 1.0)
         return run_kept(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     {
         size_t lds = 0;

@@ -80,6 +80,7 @@ EXPORTED = [
     "icp_model_knn", "icp_estimate_model_normals", "icp_get_model_normals",
     "icp_set_robust", "icp_get_robust_trace",
     "icp_voxel_downsample", "icp_voxel_downsample_device", "icp_get_transform", "icp_transform_scene",
+    "icp_set_trim", "icp_get_trim_trace", "icp_select_kth",
 ]
 
 
@@ -208,6 +209,10 @@ def lib() -> C.CDLL:
         L.icp_voxel_downsample_device.argtypes = [vp, vp, sz, C.c_double, dp, vp, vp, C.POINTER(sz)]
         L.icp_get_transform.argtypes = [vp, dp, dp, dp]
         L.icp_transform_scene.argtypes = [vp, C.c_double, dp, dp]
+    if hasattr(L, "icp_set_trim"):
+        L.icp_set_trim.argtypes = [vp, C.c_double]
+        L.icp_get_trim_trace.argtypes = [vp, dp, sz]
+        L.icp_select_kth.argtypes = [C.c_int, dp, sz, sz, dp]
     _lib = L
     return L
 
@@ -253,6 +258,17 @@ def sort_pairs(keys, bits: int, device: int = 0):
     if rc != ICP_OK:
         raise ICPError(rc, strerror(rc))
     return order, out
+
+
+def select_kth(values, k: int, device: int = 0) -> float:
+    """The engine's radix select (icp_select_kth): the k-th smallest (1-based) of the doubles in the
+    order -inf < ... < -0 < +0 < ... < +inf < NaN."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    out = C.c_double(0.0)
+    rc = lib().icp_select_kth(device, _dp(v) if v.size else None, v.size, int(k) if k >= 0 else 0, C.byref(out))
+    if rc != ICP_OK:
+        raise ICPError(rc, strerror(rc))
+    return out.value
 
 
 def horn_solve(S, mu_p, mu_y, d_caps: float, sp: float):
@@ -546,6 +562,22 @@ class Context:
             self._check(rc)
         return out[:n]
 
+    def set_trim(self, fraction: float):
+        """icp_set_trim: run() keeps, in every iteration, the fraction of the pairs with the smallest
+        distances (ties at the cut included); 1: off."""
+        self._check(lib().icp_set_trim(self._h, float(fraction)))
+
+    def trim_trace(self) -> np.ndarray:
+        """C, the selected squared distance, of each recorded iteration of the last trimmed run() (float64)."""
+        n = lib().icp_get_trim_trace(self._h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(max(n, 1))
+        rc = lib().icp_get_trim_trace(self._h, _dp(out), n)
+        if rc < 0:
+            self._check(rc)
+        return out[:n]
+
     def set_robust(self, kind: int, k: float = 0.0):
         """icp_set_robust: run() weighs every kept pair by ROBUST_HUBER / ROBUST_TUKEY / ROBUST_CAUCHY of
         its residual with the scale k (the clouds' units); ROBUST_NONE (k ignored): off."""
@@ -761,6 +793,7 @@ class ICP:
     normals: np.ndarray | None = None  # the model's normals: the point-to-plane metric (None: point-to-point)
     estimate_normals: int | None = None  # k: the normals estimated from the model (estimate_model_normals), same metric
     robust: tuple | None = None  # (kind, k): icp_set_robust (None: every kept pair with weight 1)
+    trim: float | None = None  # icp_set_trim: the fraction of the pairs each iteration keeps (None: all)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -778,6 +811,8 @@ class ICP:
         self._ctx.set_allow_unequal(self.allow_unequal)
         if self.max_distance is not None:
             self._ctx.set_max_distance(self.max_distance)
+        if self.trim is not None:
+            self._ctx.set_trim(self.trim)
         if self.robust is not None:
             self._ctx.set_robust(*self.robust)
         self._ctx.set_model(self.m)
