@@ -314,7 +314,7 @@ struct icp_ctx {
     double robust_k = 0.0, robust_k2 = 0.0;
     double *h_wtrace = nullptr, *d_wtrace = nullptr;
     long long *h_ptrace = nullptr, *d_ptrace = nullptr;
-    size_t rtrace_cap = 0;
+    size_t wtrace_cap = 0, ptrace_cap = 0;
     bool robust_have = false;
     std::vector<double> robust_wtrace;
     std::vector<long long> robust_ptrace;

@@ -12,9 +12,9 @@
 // The loop over the pairs with the gate and its mask, the transform's body, the fold and the freeze
 // of a stopped run are icp_kept.h's, shared with the point-to-plane kernels (icp_plane.hip); the
 // residual's fold and error step here (launch_gated_err) and the mask's unpacking serve both.
-// With robust weights (icp_set_robust) the moments and the fold + step have weighted twins here
-// (robust_gated_moments_kernel, robust_gated_horn_kernel, robust_first_shift_kernel): each kept
-// pair's terms enter as w * t, w a function of the pair's d2, beside W = sum w and K+ = #{w > 0}.
+// Robust weights (icp_set_robust) are a template parameter of the moments and of the fold + step:
+// each kept pair's terms enter as w * t, w a function of the pair's d2, beside W = sum w and
+// K+ = #{w > 0}.  The launchers of both metrics' loops are here (launch_kept_*).
 // Compiled with IEEE semantics like icp_step.hip (the error step's `err < threshold` and the
 // gate's `d2 <= D` must stay false for a NaN).
 #include <hip/hip_runtime.h>
@@ -31,84 +31,72 @@ namespace {
 // Modelled on shifted_moments_kernel: the 17 one-pass moment terms around the shifts of *st, of
 // the kept pairs only (kept_pairs_pass: the gate and its mask), and the kept count as an 18th sum
 // (a double: exact below 2^53).
+// KIND, a robust weight (icp_set_robust; kk = k, k2): each kept pair's 17 terms (moment_leaves:
+// shifted_moment_terms' arithmetic) enter as a += w * t with w = robust_weight<KIND>(d2), d2 the
+// gate's own, and W = sum w and K+ = #{w > 0} are the 19th and 20th sums (doubles: K+ exact below
+// 2^53).  A weight of exactly 1.0 adds the unweighted kind's bits.
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN>
+template <bool YIN, int KIND, class... K>
 __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ px,
     const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
     double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
-    const double4 *__restrict__ m4kd, const double *__restrict__ cut)
+    const double4 *__restrict__ m4kd, K... kk, const double *__restrict__ cut)
 {
-    if (st->done != 0) return;
-    const double cp0 = st->shift_p[0], cp1 = st->shift_p[1], cp2 = st->shift_p[2];
-    const double cy0 = st->shift_y[0], cy1 = st->shift_y[1], cy2 = st->shift_y[2];
-    double a[17];
-#pragma unroll
-    for (int k = 0; k < 17; ++k) a[k] = 0.0;
-    double kept = 0.0;
-    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
-                         [&](long long, double q0, double q1, double q2, const double4 &m, double, double, double)
-                             __attribute__((always_inline)) {
-                                 shifted_moment_terms(q0, q1, q2, m, cp0, cp1, cp2, cy0, cy1, cy2, a);
-                                 kept += 1.0;
-                             });
-    double b[kGateSums];
-#pragma unroll
-    for (int k = 0; k < 17; ++k) b[k] = a[k];
-    b[kGateCount] = kept;
-    block_sum_store<kGateSums>(b, partials + (size_t)blockIdx.x * kGateSums);
-}
-
-// gated_moments_kernel with robust weights (icp_set_robust): each kept pair's 17 terms (moment_leaves:
-// shifted_moment_terms' arithmetic) enter as a += w * t with w = robust_weight<KIND>(d2), d2 the
-// gate's own; the kept count stays the 18th sum, W = sum w and K+ = #{w > 0} are the 19th and 20th
-// (doubles: K+ exact below 2^53).  A weight of exactly 1.0 adds the unweighted kernel's bits.
-template <bool YIN, int KIND>
-__global__ __launch_bounds__(kBlock) void robust_gated_moments_kernel(
-    const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ px,
-    const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
-    double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
-    unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
-    const double4 *__restrict__ m4kd, double k, double k2, const double *__restrict__ cut)
-{
+    constexpr bool kRobust = KIND != kRobustNone;
+    constexpr int WIDTH = kept_width(false, kRobust);
     if (st->done != 0) return;
     const double cp[3] = {st->shift_p[0], st->shift_p[1], st->shift_p[2]};
     const double cy[3] = {st->shift_y[0], st->shift_y[1], st->shift_y[2]};
-    double a[kRobustGateSums];
+    // (unweighted: shifted_moment_terms' 17 sums and the count beside them, joined for the store --
+    // summed as one row of 18 the same pass compiles to another instruction stream)
+    double a[kRobust ? WIDTH : 17];
 #pragma unroll
-    for (int j = 0; j < kRobustGateSums; ++j) a[j] = 0.0;
+    for (double &v : a) v = 0.0;
+    double kept = 0.0;
     kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
                          [&](long long, double q0, double q1, double q2, const double4 &m, double dx, double dy, double dz)
                              __attribute__((always_inline)) {
-                                 const double w = robust_weight<KIND>((dx * dx + dy * dy) + dz * dz, k, k2);
-                                 double t[17];
-                                 moment_leaves(q0, q1, q2, m.x, m.y, m.z, cp, cy, t);
+                                 if constexpr (kRobust) {
+                                     const double w = robust_weight<KIND>((dx * dx + dy * dy) + dz * dz, kk...);
+                                     double t[17];
+                                     moment_leaves(q0, q1, q2, m.x, m.y, m.z, cp, cy, t);
 #pragma unroll
-                                 for (int j = 0; j < 17; ++j) a[j] += w * t[j];
-                                 a[kGateCount] += 1.0;
-                                 a[kRobustGateW] += w;
-                                 a[kRobustGateKpos] += w > 0.0 ? 1.0 : 0.0;
+                                     for (int j = 0; j < 17; ++j) a[j] += w * t[j];
+                                     a[kGateCount] += 1.0;
+                                     a[kRobustGateW] += w;
+                                     a[kRobustGateKpos] += w > 0.0 ? 1.0 : 0.0;
+                                 } else {
+                                     shifted_moment_terms(q0, q1, q2, m, cp[0], cp[1], cp[2], cy[0], cy[1], cy[2], a);
+                                     kept += 1.0;
+                                 }
                              });
-    block_sum_store<kRobustGateSums>(a, partials + (size_t)blockIdx.x * kRobustGateSums);
+    if constexpr (kRobust) {
+        block_sum_store<WIDTH>(a, partials + (size_t)blockIdx.x * WIDTH);
+    } else {
+        double b[WIDTH];
+#pragma unroll
+        for (int j = 0; j < 17; ++j) b[j] = a[j];
+        b[kGateCount] = kept;
+        block_sum_store<WIDTH>(b, partials + (size_t)blockIdx.x * WIDTH);
+    }
 }
 
-// The fold of the moments' partial rows into sums[0..WIDTH) (nblocks > 0) and / or the gated Horn
+// The fold of the moments' partial rows into sums[0..width) (nblocks > 0) and / or the gated Horn
 // step on sums (step; nblocks = 0: the sums as they are, all-reduced).  The step decides from the
 // global count K = sums[kGateCount], identical on every rank: K < 4 freezes the run with the
 // too-few status (kept_stop); else Horn's closed form over the kept pairs, N = K.
-// WIDTH = kRobustGateSums, the weighted rows: K+ < 4 freezes the run as well, N = W, and a solved
-// iteration's W and K+ join their mapped traces (the error step records that iteration's K and error).
+// ROBUST, the weighted rows: K+ < 4 freezes the run as well, N = W, and a solved iteration's W and
+// K+ join their mapped traces (the error step records that iteration's K and error).
 // trim_few: the trim's T is below the least count (icp_set_trim), which stops the run like K.
-template <int WIDTH>
-__device__ __forceinline__ void gated_horn_body(const double *__restrict__ partials, int nblocks,
-                                                double *__restrict__ sums, int step, double c0, double c1, double c2,
-                                                int *__restrict__ cnt, IterState *__restrict__ s,
-                                                GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
-                                                long long *__restrict__ h_ptrace, int trim_few)
+template <bool ROBUST>
+__device__ __forceinline__ void gated_horn_body(
+    const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
+    int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
-    constexpr bool kRobust = WIDTH == kRobustGateSums;
+    constexpr int WIDTH = kept_width(false, ROBUST);
     __shared__ double res[WIDTH];
     if (nblocks > 0) {
         fold_to<WIDTH>(partials, nblocks, sums, res);
@@ -122,7 +110,7 @@ __device__ __forceinline__ void gated_horn_body(const double *__restrict__ parti
         g->K = (long long)K;
         h_g->K = (long long)K;
         bool few = !(K >= 4.0) || trim_few != 0;
-        if constexpr (kRobust) {
+        if constexpr (ROBUST) {
             const double W = res[kRobustGateW], Kpos = res[kRobustGateKpos];
             g->W = W;
             g->Kpos = (long long)Kpos;
@@ -136,51 +124,35 @@ __device__ __forceinline__ void gated_horn_body(const double *__restrict__ parti
         }
         if (few) kept_stop(s, g, h_g, h_state, kGateTooFew, 0.0);
     }
-    horn_step_body(res, kRobust ? res[kRobustGateW] : K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
+    horn_step_body(res, ROBUST ? res[kRobustGateW] : K, c0, c1, c2, 1, cnt, s); // (done: the search's counters only)
 }
 
-__global__ __launch_bounds__(kBlock) void gated_horn_kernel(const double *__restrict__ partials, int nblocks,
-                                                            double *__restrict__ sums, int step, double c0, double c1,
-                                                            double c2, int *__restrict__ cnt, IterState *__restrict__ s,
-                                                            GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                            IterState *__restrict__ h_state, int trim_few)
-{
-    gated_horn_body<kGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr,
-                               trim_few);
-}
-
-__global__ __launch_bounds__(kBlock) void robust_gated_horn_kernel(
+// (The step is an inlined function under the kernel, not the kernel's own body: written straight
+// into the kernel the same text compiles to another instruction stream.)
+template <bool ROBUST>
+__global__ __launch_bounds__(kBlock) void gated_horn_kernel(
     const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
     int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
     IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
-    gated_horn_body<kRobustGateSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
-                                     h_ptrace, trim_few);
+    gated_horn_body<ROBUST>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace, h_ptrace, trim_few);
 }
 
 // The first gated iteration's shifts, from a pre-pass of the moments around the model's centre c
 // (where run_init put both shifts): the kept pairs' centroids, c + sum (p - c) / K and
-// c + sum (y - c) / K.  A partial-overlap scan D from c would otherwise cancel (D / sigma)^2 of the
-// one-pass moments' precision; sums of differences from c give the centroids to D eps, far closer
-// than a shift has to be.  sums: the folded (all ranks') pre-pass.  K = 0 leaves c (the step that
-// follows stops the run on the same count).
-__global__ void gated_first_shift_kernel(IterState *__restrict__ s, const double *__restrict__ sums)
+// c + sum (y - c) / K, K = sums[slot = kGateCount]; or from the weighted pre-pass their weighted
+// centroids, c + sum w (p - c) / W and c + sum w (y - c) / W, W = sums[slot = kRobustGateW] (the
+// weights do not depend on the shifts, so the pass that follows computes the same ones).  A
+// partial-overlap scan D from c would otherwise cancel (D / sigma)^2 of the one-pass moments'
+// precision; sums of differences from c give the centroids to D eps, far closer than a shift has
+// to be.  sums: the folded (all ranks') pre-pass.  A divisor not > 0 leaves c (the step that follows
+// stops the run on K or K+); K is an integer-valued double, so K > 0 is K >= 1.
+__global__ void kept_first_shift_kernel(IterState *__restrict__ s, const double *__restrict__ sums, int slot)
 {
-    const double K = sums[kGateCount];
-    if (threadIdx.x >= 3 || s->done || !(K >= 1.0)) return;
-    s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / K;
-    s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / K;
-}
-
-// gated_first_shift_kernel for the weighted pre-pass (rows of 20): the weighted centroids,
-// c + sum w (p - c) / W and c + sum w (y - c) / W.  The weights do not depend on the shifts, so the
-// pass that follows computes the same ones.  W not > 0 leaves c (K+ = 0: the step stops the run).
-__global__ void robust_first_shift_kernel(IterState *__restrict__ s, const double *__restrict__ sums)
-{
-    const double W = sums[kRobustGateW];
-    if (threadIdx.x >= 3 || s->done || !(W > 0.0)) return;
-    s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / W;
-    s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / W;
+    const double v = sums[slot];
+    if (threadIdx.x >= 3 || s->done || !(v > 0.0)) return;
+    s->shift_p[threadIdx.x] += sums[kSumP + threadIdx.x] / v;
+    s->shift_y[threadIdx.x] += sums[kSumY + threadIdx.x] / v;
 }
 
 // Modelled on the plain branch of transform_err_kernel: every point moves, the residual is
@@ -226,74 +198,38 @@ __global__ __launch_bounds__(kBlock) void gated_unpack_kernel(const unsigned lon
 
 } // namespace
 
-void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
-                          int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready, const double *cut)
+void launch_kept_moments(const KeptPass &a, bool y_ready)
 {
-    if (y_ready)
-        gated_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
-                                                                     partials, kpos, m4kd, cut);
-    else
-        gated_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask,
-                                                                      partials, kpos, m4kd, cut);
+    if (a.plane) return plane_moments(a, y_ready);
+    kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
+        const auto go = [&](auto... kk) {
+            gated_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
+                a.idx, a.m4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.mask, a.partials, a.kpos, a.m4kd, kk...,
+                a.cut);
+        };
+        if constexpr (kind() == kRobustNone) go();
+        else go(a.k, a.k2);
+    });
 }
 
-void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
-                       bool trim_few)
+void launch_kept_step(const KeptStep &a, const double *partials, int nblocks, bool step)
 {
-    gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
-                                            gate, h_gate, h_state, trim_few ? 1 : 0);
+    if (a.plane) return plane_step(a, partials, nblocks, step);
+    const auto kernel = a.robust ? gated_horn_kernel<true> : gated_horn_kernel<false>;
+    kernel<<<1, kBlock, 0, a.st>>>(partials, nblocks, a.sums, step ? 1 : 0, a.c[0], a.c[1], a.c[2], a.amb_count, a.st_dev,
+                                   a.gate, a.h_gate, a.h_state, a.h_wtrace, a.h_ptrace, a.trim_few ? 1 : 0);
 }
 
-void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
+void launch_kept_first_shift(IterState *st_dev, const double *sums, int slot, hipStream_t st)
 {
-    gated_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums);
+    kept_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums, slot);
 }
 
-template <int KIND>
-static void robust_gated_moments_of(double k, double k2, const int *idx, const double4 *m4, const double *px,
-                                    const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
-                                    const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                    hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready, const double *cut)
+void launch_kept_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
+                           int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
+                           const int *idx, const double4 *n4, double *partials, hipStream_t st)
 {
-    if (y_ready)
-        robust_gated_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
-                                                                                  D, mask, partials, kpos, m4kd, k, k2, cut);
-    else
-        robust_gated_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, px, py, pz, n, yx, yy, yz, st_dev,
-                                                                                   D, mask, partials, kpos, m4kd, k, k2, cut);
-}
-
-void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
-                                 const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
-                                 const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready, const double *cut)
-{
-    const auto go = kind == kRobustHuber   ? robust_gated_moments_of<kRobustHuber>
-                    : kind == kRobustTukey ? robust_gated_moments_of<kRobustTukey>
-                                           : robust_gated_moments_of<kRobustCauchy>;
-    go(k, k2, idx, m4, px, py, pz, n, yx, yy, yz, st_dev, D, mask, partials, st, kpos, m4kd, y_ready, cut);
-}
-
-void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
-                              int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                              double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few)
-{
-    robust_gated_horn_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
-                                                   st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace, trim_few ? 1 : 0);
-}
-
-void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st)
-{
-    robust_first_shift_kernel<<<1, 64, 0, st>>>(st_dev, sums);
-}
-
-void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
-                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            double *partials, hipStream_t st)
-{
+    if (n4) return plane_transform(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4, partials, st);
     gated_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, partials);
 }
 

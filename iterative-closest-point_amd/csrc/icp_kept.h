@@ -5,6 +5,7 @@
 //   kept_pairs_pass   the moments kernels' loop: y, the gate, the mask word, a callable per kept pair
 //   kept_cut          a trimmed iteration's gate: the smaller of D and the cut selected on the device
 //   robust_weight     a kept pair's weight from its squared residual (icp_set_robust)
+//   kept_dispatch     the moments kernels' instantiation for a pass: <stored y or gathered, robust kind>
 //   kept_transform    the transform kernels' body: every point moves, a callable gives a kept
 //                     point's squared residual
 //   fold_to           the fold of per-workgroup partial rows (reduce_kernel's tree)
@@ -12,10 +13,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "icp_device.h"
 #include "icp_kernels.h"
 
 namespace icp {
+
+// icp_plane.hip's side of launch_kept_moments, launch_kept_step and launch_kept_transform (icp_gated.hip)
+void plane_moments(const KeptPass &a, bool y_ready);
+void plane_step(const KeptStep &a, const double *partials, int nblocks, bool step);
+void plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,
+                     const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask, const int *idx,
+                     const double4 *n4, double *partials, hipStream_t st);
+
 namespace {
 
 // For every point i of this thread's grid stride: y_i = m[idx_i] (YIN: streamed from the copy the
@@ -80,6 +91,23 @@ __device__ __forceinline__ double robust_weight(double r2, double k, double k2)
         static_assert(KIND == kRobustCauchy, "robust_weight: unknown kind");
         return r2 == r2 ? 1.0 / (1.0 + r2 / k2) : 0.0;
     }
+}
+
+// f(YIN, KIND) with the pass's (y_ready, robust kind) as integral constants: a moments kernel's
+// template arguments.  A weighted KIND's kernel takes k and k2 behind m4kd, the unweighted one does
+// not (an unused pair costs its pairs' loop instructions).
+template <class F> void kept_dispatch(bool y_ready, int kind, F &&f)
+{
+    const auto of_kind = [&](auto yin) {
+        switch (kind) {
+        case kRobustNone: return f(yin, std::integral_constant<int, kRobustNone>());
+        case kRobustHuber: return f(yin, std::integral_constant<int, kRobustHuber>());
+        case kRobustTukey: return f(yin, std::integral_constant<int, kRobustTukey>());
+        default: return f(yin, std::integral_constant<int, kRobustCauchy>());
+        }
+    };
+    if (y_ready) of_kind(std::true_type());
+    else of_kind(std::false_type());
 }
 
 // A transform kernel's body: p <- sR p + t for every point (p32 nullable), and this workgroup's

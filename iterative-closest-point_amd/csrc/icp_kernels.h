@@ -786,18 +786,32 @@ void launch_nn_exact_few(const double *q_aos, int nq, const double4 *m4, int nm,
 void launch_reduce_pair(const double *part17, const double *part1, int nblocks, double *out, hipStream_t st);
 void launch_reduce(const double *partials, int nblocks, int K, double *out, hipStream_t st);
 
-// ---- the gated iteration (icp_gated.hip; icp_set_max_distance) ---------------------------------
-// The moments' sums of a gated iteration: the 17 one-pass terms over the kept pairs (sums slots
-// 0..16) and the kept count.  The count takes slot 17 until the Horn step has read it (into
+// ---- the kept-pairs iterations (icp_gated.hip, icp_plane.hip, icp_kept.h) ------------------------
+// icp_run over the kept pairs: the max-distance gate (icp_set_max_distance), the point-to-plane
+// metric (icp_set_metric), robust weights (icp_set_robust), a trim (icp_set_trim), or any together.
+// The moments' sums of a point-to-point iteration: the 17 one-pass terms over the kept pairs (sums
+// slots 0..16) and the kept count.  The count takes slot 17 until the step has read it (into
 // GateState::K); the residual's fold then writes its e there (kSumErr), as in the ungated loop.
 constexpr int kGateSums = 18, kGateCount = 17;
 constexpr int kGateTooFew = 1;
-// A trimmed run (icp_set_trim): the moments' launchers take cut, the device address of the
-// iteration's selected C (icp_select.hip), and keep d2 <= min(D, *cut); null: the gate alone, no
-// read.  The step launchers take trim_few: the trim's T is below the metric's least count, which
-// stops the run as K below it does.
-// Per-run state of a kept-pairs loop (the gated and the point-to-plane one), beside IterState
-// (whose layout every other kernel reads): device copy and mapped host mirror.
+// ... of a point-to-plane iteration, a = [(p - c) x n ; n], r = (p - y) . n: the upper triangle of
+// sum a a^T by rows (slots 0..20), sum a r (kPlaneB..; the solve negates it) and the kept count.
+constexpr int kPlaneSums = 28, kPlaneB = 21, kPlaneCount = 27;
+constexpr int kPlaneDegenerate = 2; // (GateState::status, beside kGateTooFew: here K < 6)
+// A robust iteration multiplies each kept pair's terms in the moments by w(r2), r2 the pair's squared
+// residual at the current pose (point-to-point: the gate's d2; point-to-plane: (d . n)^2), and sums
+// W = sum w and K+ = #{w > 0} behind the kept count K: rows of 20 and of 30.  K keeps its slot, so the
+// error step and the residual's fold are the unweighted loop's.
+constexpr int kRobustNone = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3; // (ICP_ROBUST_*)
+constexpr int kRobustGateSums = 20, kRobustGateW = 18, kRobustGateKpos = 19;
+constexpr int kRobustPlaneSums = 30, kRobustPlaneW = 28, kRobustPlaneKpos = 29;
+// the width of a moments row and of the sums
+constexpr int kept_width(bool plane, bool robust)
+{
+    return plane ? (robust ? kRobustPlaneSums : kPlaneSums) : (robust ? kRobustGateSums : kGateSums);
+}
+// Per-run state of a kept-pairs loop, beside IterState (whose layout every other kernel reads):
+// device copy and mapped host mirror.
 struct GateState {
     int status;       // 0, kGateTooFew or kPlaneDegenerate: an iteration that could not be solved froze the run
     int fail_iter;    // ... the iteration (0-based) that found it
@@ -806,25 +820,60 @@ struct GateState {
     double W;         // a robust run (icp_set_robust): the kept pairs' weights summed, all ranks', of that gate
     long long Kpos;   // ... and the kept pairs with a weight > 0
 };
-// y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; mask word w = the ballot of points
-// 64 w ..; partial [17 shifted moment terms of the kept pairs, their count]; a no-op once done
-void launch_gated_moments(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz,
-                          int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready, const double *cut = nullptr);
-// nblocks > 0: sums[0..17] = the fold of the partial rows (reduce_kernel's tree); step: K < 4
-// sets done and the too-few status (the loop state mirrored to h_state), else the shifted Horn
-// step with N = K = sums[kGateCount]
-void launch_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                       IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
-                       bool trim_few = false);
-// the first gated iteration's shifts: st->shift_p / shift_y (c, from run_init) += the folded
-// pre-pass sums' (p - c) / K and (y - c) / K, the kept pairs' centroids
-void launch_gated_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
-// p <- sR p + t for every point (p32 nullable); partial [sum over the kept points of ||y - p'||^2]
-void launch_gated_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
-                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            double *partials, hipStream_t st);
+// What a moments pass reads and writes (host side: the launcher hands the kernels plain arguments).
+struct KeptPass {
+    bool plane;                    // the point-to-plane metric: n4 and c are read
+    int robust_kind;               // kRobust*; with a weight, k and k2 = k * k
+    double k, k2;
+    const int *idx;                // the search's correspondences; kpos / m4kd: its kd-ordered form, or null
+    const int *kpos;
+    const double4 *m4, *m4kd, *n4; // the model, its kd-ordered copy, its normals
+    const double *px, *py, *pz;    // the scene, n points on this rank
+    int n;
+    double *yx, *yy, *yz;          // y = m[idx]
+    const IterState *st_dev;
+    double D;                      // the gate, squared (+inf: none)
+    const double *cut;             // a trimmed run: the device address of the iteration's selected C
+                                   // (icp_select.hip), and the pass keeps d2 <= min(D, *cut); null: D alone, no read
+    double c[3];                   // the model's centre
+    unsigned long long *mask;
+    double *partials;
+    hipStream_t st;
+};
+// y = m[idx] (stored unless y_ready, else streamed); keep = D64(p, y) <= D; mask word w = the ballot
+// of points 64 w ..; one partial row of kept_width() a workgroup: the metric's sums over the kept pairs
+// (the 17 shifted moment terms; the 27 of the normal equations with the normals n4[idx]), weighted
+// with a robust kind, then their count K, then with a robust kind W and K+.  A no-op once done.
+void launch_kept_moments(const KeptPass &a, bool y_ready);
+// What the fold + step of the moments reads and writes.
+struct KeptStep {
+    bool plane, robust;
+    bool trim_few;                 // the trim's T is below the metric's least count: stops the run as K below it
+    double *sums;
+    double c[3];
+    int *amb_count;
+    IterState *st_dev, *h_state;   // the loop state and its mapped mirror
+    GateState *gate, *h_gate;
+    double *h_wtrace;              // robust: the mapped W and K+ traces
+    long long *h_ptrace;
+    hipStream_t st;
+};
+// nblocks > 0: sums[0..kept_width()) = the fold of the partial rows (reduce_kernel's tree); step, on
+// the sums (nblocks = 0: as they are, all-reduced): K, and with weights K+, below the metric's least
+// count (4; plane: 6), trim_few, or a degenerate plane system set done and the status (the loop
+// state mirrored to h_state); else the metric's step into the loop state: the shifted Horn step
+// with N = K (weighted: N = W), or the 6 x 6 solve: s = 1, R = exp([omega]x), t = (c + tau) - R c.
+// A solved weighted iteration writes h_wtrace[iter] = W and h_ptrace[iter] = K+.
+void launch_kept_step(const KeptStep &a, const double *partials, int nblocks, bool step);
+// the first point-to-point iteration's shifts: st->shift_p / shift_y (c, from run_init) += the folded
+// pre-pass sums' (p - c) / v and (y - c) / v, v = sums[slot]: the kept pairs' centroids with
+// kGateCount, their weighted centroids with kRobustGateW
+void launch_kept_first_shift(IterState *st_dev, const double *sums, int slot, hipStream_t st);
+// p <- sR p + t for every point (p32 nullable); partial [sum over the kept points (the mask) of the
+// metric's squared residual: ||y - p'||^2, or with n4 (the plane metric) ((p' - y) . n)^2, n = n4[idx[i]]]
+void launch_kept_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
+                           int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
+                           const int *idx, const double4 *n4, double *partials, hipStream_t st);
 // nblocks > 0: sums[kSumErr] = the fold of the partial rows; step: launch_err_step's with N =
 // gate->K, and h_ktrace[iter] = K for a recorded iteration
 void launch_gated_err(const double *partials, int nblocks, double *sums, bool step, double threshold, int max_iter,
@@ -832,66 +881,8 @@ void launch_gated_err(const double *partials, int nblocks, double *sums, bool st
                       int ticket, IterState *h_state_dev, double *h_trace_dev, hipStream_t st);
 // out[order ? order[i] : i] = bit i of the mask (bytes, the caller's point order)
 void launch_gated_unpack(const unsigned long long *mask, const int *order, int n, unsigned char *out, hipStream_t st);
-
-// ---- the point-to-plane iteration (icp_plane.hip; icp_set_metric) ------------------------------
-// The moments' sums of a point-to-plane iteration over the kept pairs, a = [(p - c) x n ; n],
-// r = (p - y) . n: the upper triangle of sum a a^T by rows (slots 0..20), sum a r (kPlaneB..; the
-// solve negates it) and the kept count.  The residual's fold then writes its e to kSumErr, as in
-// the gated loop (the solve has read the sums by then).
-constexpr int kPlaneSums = 28, kPlaneB = 21, kPlaneCount = 27;
-constexpr int kPlaneDegenerate = 2; // (GateState::status, beside kGateTooFew: here K < 6)
 // n4[i] = (n_i, 0) from nm interleaved xyz normals in device memory
 void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t st);
-// y = m[idx] (stored unless y_ready); keep = D64(p, y) <= D; the mask as launch_gated_moments;
-// partial [the 27 sums of the kept pairs with their normals n4[idx], their count]; a no-op once done
-void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
-                          const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready, const double *cut = nullptr);
-// nblocks > 0: sums[0..27] = the fold of the partial rows (reduce_kernel's tree); step: K < 6 or a
-// degenerate system sets done and the status (the loop state mirrored to h_state), else the solve:
-// s = 1, R = exp([omega]x), t = (c + tau) - R c into the loop state
-void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
-                        bool trim_few = false);
-// p <- R p + t for every point (p32 nullable); partial [sum over the kept points of ((p' - y) . n)^2],
-// n = n4[idx[i]]
-void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
-                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            const int *idx, const double4 *n4, double *partials, hipStream_t st);
-
-// ---- robust weights on the kept pairs (icp_set_robust; kernels beside their unweighted twins) ----
-// A robust iteration multiplies each kept pair's terms in the moments by w(r2), r2 the pair's squared
-// residual at the current pose (point-to-point: the gate's d2; point-to-plane: (d . n)^2), and sums
-// W = sum w and K+ = #{w > 0} beside the kept count K: rows of 20 (17 terms, K, W, K+) and of 30
-// (27 sums, K, W, K+).  K keeps its slot, so the error step and the residual's fold are the
-// unweighted loop's.  The step solves with N = W (point-to-point) and stops like too-few on K+ too.
-constexpr int kRobustNone = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3; // (ICP_ROBUST_*)
-constexpr int kRobustGateSums = 20, kRobustGateW = 18, kRobustGateKpos = 19;
-constexpr int kRobustPlaneSums = 30, kRobustPlaneW = 28, kRobustPlaneKpos = 29;
-// launch_gated_moments with the weights: kind (kRobust*, not None), k and k2 = k * k; rows of 20
-void launch_robust_gated_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double *px,
-                                 const double *py, const double *pz, int n, double *yx, double *yy, double *yz,
-                                 const IterState *st_dev, double D, unsigned long long *mask, double *partials,
-                                 hipStream_t st, const int *kpos, const double4 *m4kd, bool y_ready,
-                                 const double *cut = nullptr);
-// launch_gated_horn on rows of 20: K < 4 or K+ < 4 stops the run; else Horn's closed form on the
-// weighted sums with N = W, and h_wtrace[iter] = W, h_ptrace[iter] = K+ (mapped) for that iteration
-void launch_robust_gated_horn(const double *partials, int nblocks, double *sums, bool step, const double c[3],
-                              int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                              double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few = false);
-// launch_gated_first_shift for the weighted pre-pass: the shifts += sum w (p - c) / W, sum w (y - c) / W
-void launch_robust_first_shift(IterState *st_dev, const double *sums, hipStream_t st);
-// launch_plane_moments with the weights (r2 = r * r, r the residual along the normal); rows of 30
-void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
-                                 const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
-                                 double *yz, const IterState *st_dev, double D, const double c[3],
-                                 unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                 const double4 *m4kd, bool y_ready, const double *cut = nullptr);
-// launch_plane_solve on rows of 30: K < 6 or K+ < 6 stops the run; the same solve on the weighted sums
-void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
-                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                               double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few = false);
 
 // ---- the k-th smallest of n doubles (icp_select.hip; icp_set_trim, icp_select_kth) ---------------
 // An MSB-first radix select over the 64-bit keys of the doubles (the monotone map of their bit
@@ -906,7 +897,7 @@ struct SelectState {
 };
 // keys[i] = the key of v[i]
 void launch_select_map(const double *v, int n, unsigned long long *keys, hipStream_t st);
-// The trimmed iteration's keys pass: y = m[idx] (stored unless y_ready, as launch_gated_moments
+// The trimmed iteration's keys pass: y = m[idx] (stored unless y_ready, as launch_kept_moments
 // does), keys[i] = the key of d2_i = (dx*dx + dy*dy) + dz*dz; a no-op once *done
 void launch_select_keys(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz, int n,
                         double *yx, double *yy, double *yz, const int *done, unsigned long long *keys, hipStream_t st,

@@ -15,10 +15,10 @@
 //   moves by q = R p + t, and err = (e + e) / K with e = sum over the kept pairs of ((q - y) . n)^2.
 // The loop over the pairs with the gate and its mask (one 64-bit word per wave of points), the
 // transform's body, the fold and the freeze of a stopped run are icp_kept.h's, shared with
-// icp_gated.hip; the residual's fold and error step are that file's launch_gated_err.
-// With robust weights (icp_set_robust) the moments and the fold + solve have weighted twins here
-// (robust_plane_moments_kernel, robust_plane_solve_kernel): A = sum w a a^T, b = -sum w a r with w a
-// function of r * r, beside W = sum w and K+ = #{w > 0}.
+// icp_gated.hip; the residual's fold and error step are that file's launch_gated_err, and its
+// launch_kept_* reach the kernels here through plane_moments, plane_step and plane_transform.
+// Robust weights (icp_set_robust) are a template parameter of the moments and of the fold + solve:
+// A = sum w a a^T, b = -sum w a r with w a function of r * r, beside W = sum w and K+ = #{w > 0}.
 // Compiled with IEEE semantics like icp_gated.hip (`d2 <= D`, `A_kk > 0` and `pivot > 1e-12` must
 // stay false for a NaN).
 #include <hip/hip_runtime.h>
@@ -43,19 +43,24 @@ __global__ __launch_bounds__(kBlock) void plane_normals4_kernel(const double *__
 // The sums over the kept pairs (kept_pairs_pass: the gate and its mask, as the gated moments): the
 // 21 + 6 of the normal equations and the kept count as the 28th (a double: exact below 2^53).  No
 // shifts: r is a difference of near points, and (p - c) is taken before any product.
+// KIND, a robust weight (icp_set_robust; kk = k, k2): each of the pair's 27 terms enters as
+// a += w * t with w = robust_weight<KIND>(r * r), r the residual along the normal, and W = sum w and
+// K+ = #{w > 0} are the 29th and 30th sums.
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN>
+template <bool YIN, int KIND, class... K>
 __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, const double *__restrict__ cut)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, K... kk, const double *__restrict__ cut)
 {
+    constexpr bool kRobust = KIND != kRobustNone;
+    constexpr int WIDTH = kept_width(true, kRobust);
     if (st->done != 0) return;
-    double a[kPlaneSums];
+    double a[WIDTH];
 #pragma unroll
-    for (int k = 0; k < kPlaneSums; ++k) a[k] = 0.0;
+    for (int j = 0; j < WIDTH; ++j) a[j] = 0.0;
     kept_pairs_pass<YIN>(
         idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
         [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
@@ -70,59 +75,25 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
                 v[4] = nn.y;
                 v[5] = nn.z;
                 const double r = (dx * nn.x + dy * nn.y) + dz * nn.z;
+                double w = 1.0; // (unweighted: not multiplied)
+                if constexpr (kRobust) w = robust_weight<KIND>(r * r, kk...);
+                const auto add = [&](double &sum, double t) __attribute__((always_inline)) {
+                    if constexpr (kRobust) sum += w * t;
+                    else sum += t;
+                };
 #pragma unroll
                 for (int row = 0; row < 6; ++row)
 #pragma unroll
-                    for (int col = row; col < 6; ++col) a[6 * row - row * (row - 1) / 2 + (col - row)] += v[row] * v[col];
+                    for (int col = row; col < 6; ++col) add(a[6 * row - row * (row - 1) / 2 + (col - row)], v[row] * v[col]);
 #pragma unroll
-                for (int row = 0; row < 6; ++row) a[kPlaneB + row] += v[row] * r;
+                for (int row = 0; row < 6; ++row) add(a[kPlaneB + row], v[row] * r);
                 a[kPlaneCount] += 1.0;
+                if constexpr (kRobust) {
+                    a[kRobustPlaneW] += w;
+                    a[kRobustPlaneKpos] += w > 0.0 ? 1.0 : 0.0;
+                }
             });
-    block_sum_store<kPlaneSums>(a, partials + (size_t)blockIdx.x * kPlaneSums);
-}
-
-// plane_moments_kernel with robust weights (icp_set_robust): each of the pair's 27 terms, computed
-// as there, enters as a += w * t with w = robust_weight<KIND>(r * r), r the residual along the
-// normal; the kept count stays the 28th sum, W = sum w and K+ = #{w > 0} are the 29th and 30th.
-template <bool YIN, int KIND>
-__global__ __launch_bounds__(kBlock) void robust_plane_moments_kernel(
-    const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
-    const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
-    double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
-    double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, double k, double k2, const double *__restrict__ cut)
-{
-    if (st->done != 0) return;
-    double a[kRobustPlaneSums];
-#pragma unroll
-    for (int j = 0; j < kRobustPlaneSums; ++j) a[j] = 0.0;
-    kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
-        [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
-            __attribute__((always_inline)) {
-                const double4 nn = n4[idx[i]];
-                const double u0 = q0 - c0, u1 = q1 - c1, u2 = q2 - c2;
-                double v[6];
-                v[0] = u1 * nn.z - u2 * nn.y;
-                v[1] = u2 * nn.x - u0 * nn.z;
-                v[2] = u0 * nn.y - u1 * nn.x;
-                v[3] = nn.x;
-                v[4] = nn.y;
-                v[5] = nn.z;
-                const double r = (dx * nn.x + dy * nn.y) + dz * nn.z;
-                const double w = robust_weight<KIND>(r * r, k, k2);
-#pragma unroll
-                for (int row = 0; row < 6; ++row)
-#pragma unroll
-                    for (int col = row; col < 6; ++col)
-                        a[6 * row - row * (row - 1) / 2 + (col - row)] += w * (v[row] * v[col]);
-#pragma unroll
-                for (int row = 0; row < 6; ++row) a[kPlaneB + row] += w * (v[row] * r);
-                a[kPlaneCount] += 1.0;
-                a[kRobustPlaneW] += w;
-                a[kRobustPlaneKpos] += w > 0.0 ? 1.0 : 0.0;
-            });
-    block_sum_store<kRobustPlaneSums>(a, partials + (size_t)blockIdx.x * kRobustPlaneSums);
+    block_sum_store<WIDTH>(a, partials + (size_t)blockIdx.x * WIDTH);
 }
 
 // The 6 x 6 solve of one thread.  sums: the 28 folded sums; A (36) and w (12: g, then x) are the
@@ -172,22 +143,20 @@ __device__ __forceinline__ bool plane_solve(const double *sums, double *A, doubl
     return true;
 }
 
-// The fold of the moments' partial rows into sums[0..WIDTH) (nblocks > 0; one row in flight: 28 columns
+// The fold of the moments' partial rows into sums[0..width) (nblocks > 0; one row in flight: 28 columns
 // leave no registers for four) and / or the solve and step on sums (step; nblocks = 0: the sums as
 // they are, all-reduced).  The step decides from the global sums, identical on every rank: K < 6 or
 // a degenerate system freezes the run with its status (kept_stop); else s = 1, R, t of the solve.
-// WIDTH = kRobustPlaneSums, the weighted rows: K+ < 6 freezes the run as well, the system solved is
-// the weighted one, and a solved iteration's W and K+ join their mapped traces.
+// ROBUST, the weighted rows: K+ < 6 freezes the run as well, the system solved is the weighted one,
+// and a solved iteration's W and K+ join their mapped traces.
 // trim_few: the trim's T is below the least count (icp_set_trim), which stops the run like K.
-template <int WIDTH>
-__device__ __forceinline__ void plane_solve_body(const double *__restrict__ partials, int nblocks,
-                                                 double *__restrict__ sums, int step, double c0, double c1, double c2,
-                                                 int *__restrict__ cnt, IterState *__restrict__ s,
-                                                 GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                 IterState *__restrict__ h_state, double *__restrict__ h_wtrace,
-                                                 long long *__restrict__ h_ptrace, int trim_few)
+template <bool ROBUST>
+__device__ __forceinline__ void plane_solve_body(
+    const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
+    int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
+    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
-    constexpr bool kRobust = WIDTH == kRobustPlaneSums;
+    constexpr int WIDTH = kept_width(true, ROBUST);
     __shared__ double res[WIDTH];
     __shared__ double A[36], w[12];
     if (nblocks > 0) {
@@ -204,7 +173,7 @@ __device__ __forceinline__ void plane_solve_body(const double *__restrict__ part
         int status = 0;
         double piv = 0.0;
         bool few = !(K >= 6.0) || trim_few != 0;
-        if constexpr (kRobust) {
+        if constexpr (ROBUST) {
             const double W = res[kRobustPlaneW], Kpos = res[kRobustPlaneKpos];
             g->W = W;
             g->Kpos = (long long)Kpos;
@@ -215,7 +184,7 @@ __device__ __forceinline__ void plane_solve_body(const double *__restrict__ part
         if (few) status = kGateTooFew;
         else if (!plane_solve(res, A, w, &piv)) status = kPlaneDegenerate;
         if (status) kept_stop(s, g, h_g, h_state, status, piv);
-        if constexpr (kRobust) {
+        if constexpr (ROBUST) {
             if (!status) {
                 h_wtrace[s->iter] = res[kRobustPlaneW];
                 h_ptrace[s->iter] = (long long)res[kRobustPlaneKpos];
@@ -258,23 +227,15 @@ __device__ __forceinline__ void plane_solve_body(const double *__restrict__ part
     compose_srt(inc, s->tot, &s->tot_n);
 }
 
-__global__ __launch_bounds__(kBlock) void plane_solve_kernel(const double *__restrict__ partials, int nblocks,
-                                                             double *__restrict__ sums, int step, double c0, double c1,
-                                                             double c2, int *__restrict__ cnt, IterState *__restrict__ s,
-                                                             GateState *__restrict__ g, GateState *__restrict__ h_g,
-                                                             IterState *__restrict__ h_state, int trim_few)
-{
-    plane_solve_body<kPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, nullptr, nullptr,
-                                 trim_few);
-}
-
-__global__ __launch_bounds__(kBlock) void robust_plane_solve_kernel(
+// (The step is an inlined function under the kernel, not the kernel's own body: written straight
+// into the kernel the same text compiles to another instruction stream.)
+template <bool ROBUST>
+__global__ __launch_bounds__(kBlock) void plane_solve_kernel(
     const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
     int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
     IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
-    plane_solve_body<kRobustPlaneSums>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace,
-                                       h_ptrace, trim_few);
+    plane_solve_body<ROBUST>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace, h_ptrace, trim_few);
 }
 
 // Every point moves, and the squared residual along the normal, gathered again through idx, is
@@ -302,65 +263,29 @@ void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t s
     plane_normals4_kernel<<<(nm + kBlock - 1) / kBlock, kBlock, 0, st>>>(aos, nm, n4);
 }
 
-void launch_plane_moments(const int *idx, const double4 *m4, const double4 *n4, const double *px, const double *py,
-                          const double *pz, int n, double *yx, double *yy, double *yz, const IterState *st_dev, double D,
-                          const double c[3], unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                          const double4 *m4kd, bool y_ready, const double *cut)
+void plane_moments(const KeptPass &a, bool y_ready)
 {
-    if (y_ready)
-        plane_moments_kernel<true><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
-                                                                     c[1], c[2], mask, partials, kpos, m4kd, cut);
-    else
-        plane_moments_kernel<false><<<red_blocks(n), kBlock, 0, st>>>(idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0],
-                                                                      c[1], c[2], mask, partials, kpos, m4kd, cut);
+    kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
+        const auto go = [&](auto... kk) {
+            plane_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
+                a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
+                a.partials, a.kpos, a.m4kd, kk..., a.cut);
+        };
+        if constexpr (kind() == kRobustNone) go();
+        else go(a.k, a.k2);
+    });
 }
 
-void launch_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3], int *amb_count,
-                        IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state, hipStream_t st,
-                        bool trim_few)
+void plane_step(const KeptStep &a, const double *partials, int nblocks, bool step)
 {
-    plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count, st_dev,
-                                             gate, h_gate, h_state, trim_few ? 1 : 0);
+    const auto kernel = a.robust ? plane_solve_kernel<true> : plane_solve_kernel<false>;
+    kernel<<<1, kBlock, 0, a.st>>>(partials, nblocks, a.sums, step ? 1 : 0, a.c[0], a.c[1], a.c[2], a.amb_count, a.st_dev,
+                                   a.gate, a.h_gate, a.h_state, a.h_wtrace, a.h_ptrace, a.trim_few ? 1 : 0);
 }
 
-template <int KIND>
-static void robust_plane_moments_of(double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
-                                    const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
-                                    double *yz, const IterState *st_dev, double D, const double c[3],
-                                    unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                    const double4 *m4kd, bool y_ready, const double *cut)
-{
-    if (y_ready)
-        robust_plane_moments_kernel<true, KIND><<<red_blocks(n), kBlock, 0, st>>>(
-            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2, cut);
-    else
-        robust_plane_moments_kernel<false, KIND><<<red_blocks(n), kBlock, 0, st>>>(
-            idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c[0], c[1], c[2], mask, partials, kpos, m4kd, k, k2, cut);
-}
-
-void launch_robust_plane_moments(int kind, double k, double k2, const int *idx, const double4 *m4, const double4 *n4,
-                                 const double *px, const double *py, const double *pz, int n, double *yx, double *yy,
-                                 double *yz, const IterState *st_dev, double D, const double c[3],
-                                 unsigned long long *mask, double *partials, hipStream_t st, const int *kpos,
-                                 const double4 *m4kd, bool y_ready, const double *cut)
-{
-    const auto go = kind == kRobustHuber   ? robust_plane_moments_of<kRobustHuber>
-                    : kind == kRobustTukey ? robust_plane_moments_of<kRobustTukey>
-                                           : robust_plane_moments_of<kRobustCauchy>;
-    go(k, k2, idx, m4, n4, px, py, pz, n, yx, yy, yz, st_dev, D, c, mask, partials, st, kpos, m4kd, y_ready, cut);
-}
-
-void launch_robust_plane_solve(const double *partials, int nblocks, double *sums, bool step, const double c[3],
-                               int *amb_count, IterState *st_dev, GateState *gate, GateState *h_gate, IterState *h_state,
-                               double *h_wtrace, long long *h_ptrace, hipStream_t st, bool trim_few)
-{
-    robust_plane_solve_kernel<<<1, kBlock, 0, st>>>(partials, nblocks, sums, step ? 1 : 0, c[0], c[1], c[2], amb_count,
-                                                    st_dev, gate, h_gate, h_state, h_wtrace, h_ptrace, trim_few ? 1 : 0);
-}
-
-void launch_plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
-                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                            const int *idx, const double4 *n4, double *partials, hipStream_t st)
+void plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,
+                     const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask, const int *idx,
+                     const double4 *n4, double *partials, hipStream_t st)
 {
     plane_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4,
                                                              partials);

@@ -652,45 +652,16 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     return finish_run(ctx, threshold, err_trace, res, wall0);
 }
 
-// the mapped K trace of at least max_iter entries
-int grow_ktrace(icp_ctx *ctx, int max_iter)
+// a mapped trace of T (the kept-pairs loop's K, W, K+ and C) of at least max_iter entries
+template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int max_iter)
 {
-    if (ctx->ktrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
-    if (ctx->h_ktrace) HIPCHK(hipHostFree(ctx->h_ktrace)); // (the previous run ended with a sync)
-    ctx->h_ktrace = nullptr;
-    ctx->ktrace_cap = 0;
+    if (*cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
+    if (*h) HIPCHK(hipHostFree(*h)); // (the previous run ended with a sync)
+    *h = nullptr;
+    *cap = 0;
     const size_t want = (size_t)std::max(max_iter, 64);
-    TRY(mapped_alloc(ctx, &ctx->h_ktrace, &ctx->d_ktrace, sizeof(long long) * want));
-    ctx->ktrace_cap = want;
-    return ICP_OK;
-}
-
-// the mapped W and K+ traces of a robust run, of at least max_iter entries each
-int grow_rtrace(icp_ctx *ctx, int max_iter)
-{
-    if (ctx->rtrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
-    if (ctx->h_wtrace) HIPCHK(hipHostFree(ctx->h_wtrace)); // (the previous run ended with a sync)
-    ctx->h_wtrace = nullptr;
-    if (ctx->h_ptrace) HIPCHK(hipHostFree(ctx->h_ptrace));
-    ctx->h_ptrace = nullptr;
-    ctx->rtrace_cap = 0;
-    const size_t want = (size_t)std::max(max_iter, 64);
-    TRY(mapped_alloc(ctx, &ctx->h_wtrace, &ctx->d_wtrace, sizeof(double) * want));
-    TRY(mapped_alloc(ctx, &ctx->h_ptrace, &ctx->d_ptrace, sizeof(long long) * want));
-    ctx->rtrace_cap = want;
-    return ICP_OK;
-}
-
-// the mapped C trace of a trimmed run, of at least max_iter entries
-int grow_ctrace(icp_ctx *ctx, int max_iter)
-{
-    if (ctx->ctrace_cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
-    if (ctx->h_ctrace) HIPCHK(hipHostFree(ctx->h_ctrace)); // (the previous run ended with a sync)
-    ctx->h_ctrace = nullptr;
-    ctx->ctrace_cap = 0;
-    const size_t want = (size_t)std::max(max_iter, 64);
-    TRY(mapped_alloc(ctx, &ctx->h_ctrace, &ctx->d_ctrace, sizeof(double) * want));
-    ctx->ctrace_cap = want;
+    TRY(mapped_alloc(ctx, h, d, sizeof(T) * want));
+    *cap = want;
     return ICP_OK;
 }
 
@@ -708,13 +679,13 @@ int grow_ctrace(icp_ctx *ctx, int max_iter)
 // host does not synchronise inside an iteration.
 // The metrics differ in: the normals (plane), the least K (4 / 6, in the step kernels), D (the
 // plane metric runs ungated with D = +inf), the first iteration's pre-pass (point-to-point only:
-// the plane sums need no shifts), the launchers, and the closing messages.
+// the plane sums need no shifts), the kernels behind the launchers, and the closing messages.
 // A gated run leaves icp_get_inliers its last gate and K trace; an ungated one leaves the last
 // gated run's.
-// With robust weights (icp_set_robust) the moments and the fold + step are the weighted kernels
-// (rows of 20 and 30: the sums, K, W = sum w, K+ = #{w > 0}; the pre-pass's shifts divide by W; the
-// step stops on K+ as on K and writes W and K+ to their mapped traces); the transform, the residual
-// and the error step, hence err = (e + e) / K, are the unweighted loop's.
+// With robust weights (icp_set_robust) the moments and the fold + step are their weighted
+// instantiations (rows of 20 and 30: the sums, K, W = sum w, K+ = #{w > 0}; the pre-pass's shifts
+// divide by W; the step stops on K+ as on K and writes W and K+ to their mapped traces); the
+// transform, the residual and the error step, hence err = (e + e) / K, are the unweighted loop's.
 // With a trim (icp_set_trim) the iteration's gate is min(D, C), C the T-th smallest d2 over all
 // ranks, selected on the device (icp_select.hip) between the search and the moments: a keys pass
 // gathers and stores y and writes each point's d2 key, kSelectPasses passes of count + pick (one
@@ -738,8 +709,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     const long long T = trim ? std::max(1LL, (long long)(ctx->trim_fraction * (double)ctx->np_total)) : 0;
     const bool trim_few = trim && T < (ctx->metric == ICP_METRIC_POINT_TO_PLANE ? 6 : 4);
     const int robust = ctx->robust_kind; // (ICP_ROBUST_*; 0: the unweighted kernels, as without the setting)
-    const double rk = ctx->robust_k, rk2 = ctx->robust_k2;
-    const int width = plane ? (robust ? kRobustPlaneSums : kPlaneSums) : (robust ? kRobustGateSums : kGateSums);
+    const int width = kept_width(plane, robust != 0);
     const bool ranks = lag_run(ctx);
     const int nb = red_blocks(n);
     TRY(grow(ctx, &ctx->kept_mask, &ctx->kept_mask_cap, (n + 63) / 64));
@@ -747,10 +717,13 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     TRY(grow(ctx, &ctx->kept_part, &ctx->kept_part_cap, (size_t)kRedMaxBlocksCap * kRobustPlaneSums));
     if (!ctx->kept_state) HIPCHK(hipMalloc((void **)&ctx->kept_state, sizeof(GateState)));
     if (!ctx->h_kept) TRY(mapped_alloc(ctx, &ctx->h_kept, &ctx->d_kept_mirror, sizeof(GateState)));
-    TRY(grow_ktrace(ctx, max_iter));
-    if (robust) TRY(grow_rtrace(ctx, max_iter));
+    TRY(grow_trace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
+    if (robust) {
+        TRY(grow_trace(ctx, &ctx->h_wtrace, &ctx->d_wtrace, &ctx->wtrace_cap, max_iter));
+        TRY(grow_trace(ctx, &ctx->h_ptrace, &ctx->d_ptrace, &ctx->ptrace_cap, max_iter));
+    }
     if (trim) {
-        TRY(grow_ctrace(ctx, max_iter));
+        TRY(grow_trace(ctx, &ctx->h_ctrace, &ctx->d_ctrace, &ctx->ctrace_cap, max_iter));
         TRY(grow(ctx, &ctx->trim_keys, &ctx->trim_keys_cap, n));
         if (!ctx->trim_bins) HIPCHK(hipMalloc((void **)&ctx->trim_bins, sizeof(unsigned) * kSelectBins));
         if (!ctx->trim_bins_d) HIPCHK(hipMalloc((void **)&ctx->trim_bins_d, sizeof(double) * kSelectBins));
@@ -758,7 +731,6 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         if (!ctx->trim_cut) HIPCHK(hipMalloc((void **)&ctx->trim_cut, sizeof(double)));
         HIPCHK(hipMemsetAsync(ctx->trim_bins, 0, sizeof(unsigned) * kSelectBins, ctx->st)); // (each pick leaves them zero)
     }
-    const double *cut = trim ? ctx->trim_cut : nullptr;
     std::memset(ctx->h_kept, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -766,37 +738,35 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
     const int *digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
     ctx->stats.run_path_bits = 0;
-    // the metric's launches: the fold of the moments' partial rows and / or the step on the folded
-    // (all ranks') sums; the moments' pass with its fold
-    const auto step = [&](const double *part, int nblocks, bool do_step) {
-        if (plane && robust)
-            launch_robust_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                                      ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st, trim_few);
-        else if (robust)
-            launch_robust_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                                     ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->d_wtrace, ctx->d_ptrace, ctx->st, trim_few);
-        else if (plane)
-            launch_plane_solve(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                               ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st, trim_few);
-        else
-            launch_gated_horn(part, nblocks, ctx->sums, do_step, ctx->c, ctx->amb_count, sd, ctx->kept_state,
-                              ctx->d_kept_mirror, ctx->d_iter_mirror, ctx->st, trim_few);
-    };
+    // The metric's launches: the moments' pass with its fold, and the fold of the moments' partial
+    // rows and / or the step on the folded (all ranks') sums.  Their arguments hold for the run, but
+    // for what a search leaves (it may allocate idx and the kd-ordered form): taken at each pass.
+    KeptPass pass = {};
+    pass.plane = plane;
+    pass.robust_kind = robust;
+    pass.k = ctx->robust_k, pass.k2 = ctx->robust_k2;
+    pass.m4 = ctx->m4, pass.n4 = ctx->n4;
+    pass.px = P.x, pass.py = P.y, pass.pz = P.z, pass.n = (int)n;
+    pass.yx = Y.x, pass.yy = Y.y, pass.yz = Y.z;
+    pass.st_dev = sd;
+    pass.D = D;
+    pass.cut = trim ? ctx->trim_cut : nullptr;
+    pass.mask = ctx->kept_mask, pass.partials = ctx->kept_part;
+    pass.st = ctx->st;
+    KeptStep fold = {};
+    fold.plane = plane, fold.robust = robust != 0, fold.trim_few = trim_few;
+    fold.sums = ctx->sums, fold.amb_count = ctx->amb_count;
+    fold.st_dev = sd, fold.h_state = ctx->d_iter_mirror;
+    fold.gate = ctx->kept_state, fold.h_gate = ctx->d_kept_mirror;
+    fold.h_wtrace = ctx->d_wtrace, fold.h_ptrace = ctx->d_ptrace;
+    fold.st = ctx->st;
+    for (int k = 0; k < 3; ++k) pass.c[k] = fold.c[k] = ctx->c[k];
     const auto moments = [&](bool y_ready, bool do_step) {
-        const int *kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
-        if (plane && robust)
-            launch_robust_plane_moments(robust, rk, rk2, ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd,
-                                        D, ctx->c, ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
-        else if (robust)
-            launch_robust_gated_moments(robust, rk, rk2, ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D,
-                                        ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
-        else if (plane)
-            launch_plane_moments(ctx->idx, ctx->m4, ctx->n4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->c,
-                                 ctx->kept_mask, ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
-        else
-            launch_gated_moments(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, sd, D, ctx->kept_mask,
-                                 ctx->kept_part, ctx->st, kpos, ctx->m4kd, y_ready, cut);
-        step(ctx->kept_part, nb, do_step);
+        pass.idx = ctx->idx;
+        pass.kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
+        pass.m4kd = ctx->m4kd;
+        launch_kept_moments(pass, y_ready);
+        launch_kept_step(fold, ctx->kept_part, nb, do_step);
     };
     LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
     r.ctx = ctx;
@@ -840,8 +810,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                 moments(ctx->y_ready || trim, false); // (the fold alone)
                 LAUNCHCHK("gated_moments (first shifts)");
                 if (ranks) TRY(allreduce(ctx, ctx->sums, width));
-                if (robust) launch_robust_first_shift(sd, ctx->sums, ctx->st);
-                else launch_gated_first_shift(sd, ctx->sums, ctx->st);
+                launch_kept_first_shift(sd, ctx->sums, robust ? kRobustGateW : kGateCount, ctx->st);
                 LAUNCHCHK("gated_first_shift");
             }
             // 2-4. the gate, the kept pairs' sums and count, the metric's step
@@ -850,16 +819,12 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             LAUNCHCHK(plane ? "plane_moments" : "gated_moments");
             if (ranks) {
                 TRY(allreduce(ctx, ctx->sums, width));
-                step(nullptr, 0, true);
+                launch_kept_step(fold, nullptr, 0, true);
                 LAUNCHCHK(plane ? "plane_solve" : "gated_horn");
             }
             // 5-6. every point moves; the kept points' residual; err = (e + e) / K
-            if (plane)
-                launch_plane_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                       ctx->kept_mask, ctx->idx, ctx->n4, ctx->partials, ctx->st);
-            else
-                launch_gated_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                       ctx->kept_mask, ctx->partials, ctx->st);
+            launch_kept_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                  ctx->kept_mask, ctx->idx, plane ? ctx->n4 : nullptr, ctx->partials, ctx->st);
             if (!need_p32) ctx->p32_stale = true;
             const int sl = r.enqueued % kRing;
             r.slot_ticket[sl] = ++ctx->flag_ticket;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Everything the kept-pairs loop (icp_run under icp_set_max_distance and / or icp_set_metric)
-computes on the cases of tests/test_gpu_gated.py and tests/test_gpu_plane.py, dumped for a
+"""Everything the kept-pairs loop (icp_run under icp_set_max_distance, icp_set_metric, icp_set_robust
+and / or icp_set_trim) computes on the cases of tests/test_gpu_gated.py and tests/test_gpu_plane.py
+and on every combination of its options at one small size (matrix()), dumped for a
 bit-for-bit comparison of two libraries (ICP_AMD_LIB picks the library; tools/build_ab.sh builds
 another revision's):
 
@@ -9,8 +10,8 @@ another revision's):
   python3 tools/kept_dump.py --compare a.npz b.npz      (exit status 1 if anything differs)
 
 One process.  Per run: the return code and message, errs, the scene, s / R / t, the iterations, with
-a gate the K trace, the mask and k, and the integer counters of stats() (run_path_bits, the
-searches' queue counts).
+a gate the K trace, the mask and k, with weights the W and K+ traces, with a trim the C trace, and
+the integer counters of stats() (run_path_bits, the searches' queue counts).
 """
 import argparse
 import os
@@ -53,11 +54,28 @@ def record(tag, ctx, iters, threshold=-1.0):
         OUT[tag + "/inlier_trace"] = ctx.inlier_trace()
     except amd.ICPError as e:  # (no gated run since set_scene)
         OUT[tag + "/inliers_rc"] = np.array(e.code)
+    for name, get in (("robust_trace", ctx.robust_trace), ("trim_trace", ctx.trim_trace)):
+        try:
+            got = get()
+            for j, v in enumerate(got if isinstance(got, tuple) else (got,)):
+                OUT[f"{tag}/{name}{j}"] = v
+        except amd.ICPError as e:  # (no such run since set_scene)
+            OUT[f"{tag}/{name}_rc"] = np.array(e.code)
     st = ctx.stats()
     OUT[tag + "/stats"] = np.array([int(v) & (2**64 - 1) for k, v in sorted(st.items()) if not isinstance(v, float)], dtype=np.uint64)
 
 
-def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, **ctx_args):
+def options(ctx, dmax, robust, trim):
+    """robust: (kind, k) or None; trim: the fraction or None"""
+    if dmax:
+        ctx.set_max_distance(dmax)
+    if robust:
+        ctx.set_robust(*robust)
+    if trim:
+        ctx.set_trim(trim)
+
+
+def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, robust=None, trim=None, **ctx_args):
     with amd.Context(0, mode, **ctx_args) as ctx:
         if variant is not None:
             ctx.set_nn_variant(variant)
@@ -66,12 +84,11 @@ def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None
             ctx.set_model_normals(nrm)
             ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
         ctx.set_scene(p)
-        if dmax:
-            ctx.set_max_distance(dmax)
+        options(ctx, dmax, robust, trim)
         record(tag, ctx, iters, threshold)
 
 
-def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0):
+def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None, trim=None):
     red = HostAllReduce(world)
     errors = []
 
@@ -84,7 +101,7 @@ def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0):
                     ctx.set_model_normals(nrm)
                     ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
                 ctx.set_scene(p[b:b + c], np_total=p.shape[0])
-                ctx.set_max_distance(dmax)
+                options(ctx, dmax, robust, trim)
                 record(f"{tag}/rank{r}", ctx, iters, threshold)
         except Exception as e:
             errors.append(e)
@@ -109,9 +126,49 @@ def slot_scene(n=65536):
     return m, p, nrm
 
 
+MATRIX_N, MATRIX_ITERS, MATRIX_K, MATRIX_F, MATRIX_DMAX = 193, 3, 0.1, 0.75, 0.08
+KINDS = (("none", amd.ROBUST_NONE), ("huber", amd.ROBUST_HUBER), ("tukey", amd.ROBUST_TUKEY), ("cauchy", amd.ROBUST_CAUCHY))
+
+
+def matrix(clump):
+    """Every cell of metric x weights x trim x gate at n = 193 (three full waves and a partial fourth: the
+    last mask word and the last ballot are partial) on one rank, and without and with Tukey weights on
+    two (the fold-only pass, the all-reduce at each row width, the step on all-reduced sums); the cow
+    clump with Tukey weights and a trim to convergence; the stops through the weighted and trimmed paths."""
+    m, nrm, p = P.gate_case(MATRIX_N)
+    for metric in ("point", "plane"):
+        for kname, kind in KINDS:
+            for trim in (None, MATRIX_F):
+                for dmax in (0.0, MATRIX_DMAX):
+                    cell = f"{metric}_{kname}_trim{trim or 'off'}_gate{dmax or 'off'}"
+                    args = dict(nrm=nrm if metric == "plane" else None, robust=(kind, MATRIX_K) if kind else None, trim=trim)
+                    fresh(f"matrix/{cell}", m, p, dmax, MATRIX_ITERS, **args)
+                    if kname in ("none", "tukey"):
+                        sharded(f"matrix/world2/{cell}", m, p, dmax, 2, MATRIX_ITERS, **args)
+    tukey = (amd.ROBUST_TUKEY, 0.25 * G.cow_ext(clump[0]))
+    fresh("matrix/clump_tukey_trim", clump[0], clump[1], 0.0, 60, threshold=1e-5, robust=tukey, trim=MATRIX_F)
+    # K+ below the least count with K above it
+    sm, sn, sp, _src = P.synth(MATRIX_N, 100 + MATRIX_N, 0.01)
+    for metric in ("point", "plane"):
+        for trim in (None, MATRIX_F):
+            fresh(f"matrix/stop/no_weight_{metric}_trim{trim or 'off'}", sm, sp, 0.0, 5, nrm=sn if metric == "plane" else None,
+                  robust=(amd.ROBUST_TUKEY, 1e-9), trim=trim)
+    # the trim's T below the least count
+    fm, fp = G.synth(5, 105, 0.25)
+    for kname, kind in KINDS[::2]:
+        fresh(f"matrix/stop/trim_few_point_{kname}", fm, fp, 0.0, 5, robust=(kind, 1.0) if kind else None, trim=0.7)
+        fresh(f"matrix/stop/trim_few_plane_{kname}", *P.five()[::2], 0.0, 5, nrm=P.five()[1], robust=(kind, 1.0) if kind else None,
+              trim=MATRIX_F)
+    # a degenerate weighted plane system
+    dm, dn, dp = P.planar()
+    for trim in (None, MATRIX_F):
+        fresh(f"matrix/stop/degenerate_tukey_trim{trim or 'off'}", dm, dp, 0.0, 5, nrm=dn, robust=(amd.ROBUST_TUKEY, 1.0), trim=trim)
+
+
 def dump():
     cow = [amd.load_matrix(datasets.path(k)) for k in ("cow_ref", "cow_tr2")]
     clump = (cow[0], G.cow_clump(*cow), 0.25 * G.cow_ext(cow[0]))
+    matrix(clump)
     # the gated suite
     for n in G.SIZES:
         m, p = G.synth(n, 100 + n, 0.25)
