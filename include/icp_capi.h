@@ -72,7 +72,9 @@ typedef struct icp_ctx icp_ctx;
 typedef struct icp_result {
     int iterations; /* ICP iterations executed                                       */
     int converged;  /* 1 if err < threshold stopped the loop (src/GPU/gpu.cc:79-80)   */
-    double err;     /* last err = (e_align + e_apply) / np, as printed (gpu.cc:76)    */
+    double err;     /* last err = (e_align + e_apply) / np, as printed (gpu.cc:76);
+                       with icp_set_plane_symmetric the residual is along a sum of two
+                       normals: up to four times the one-sided metric's           */
     double s;       /* last increment's scale       (GPU::ICP::s, gpu.hh:91); 1 with
                        ICP_METRIC_POINT_TO_PLANE                                      */
     double R[9];    /* last increment's rotation, row-major (GPU::ICP::r, gpu.hh:93)  */
@@ -373,6 +375,65 @@ int icp_get_trim_trace(icp_ctx *ctx, double *cut_d2_out, size_t cap);
 int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2);
 int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate);
 int icp_get_model_normals(icp_ctx *ctx, double *n_xyz);
+
+/* ---- the symmetric point-to-plane iteration: the scene's normals too -------- */
+/* icp_set_plane_symmetric(ctx, 1): with ICP_METRIC_POINT_TO_PLANE every iteration of icp_run minimises
+ * the symmetric objective (Rusinkiewicz, "A Symmetric Objective Function for ICP", SIGGRAPH 2019):
+ * the plane iteration with a second normal, the scene's.  It is exact to second order where
+ * point-to-plane is exact only on a flat model, and converges from larger rotations.  One iteration,
+ * with N the model's normals, u0 the scene's as given, c the model's centroid and Q the rotation of
+ * icp_get_transform at the iteration's start:
+ * 1. The search, y_j = m[idx_j], d = p_j - y_j, the gate, the trim, the mask and K: unchanged.
+ * 2. N_j = N[idx_j], u_j = Q u0_j (each row summed as ((Q0 u0 + Q1 u1) + Q2 u2)), h = (Nx ux + Ny uy)
+ *    + Nz uz.  If N_j is all zero or u0_j is all zero, n_j = 0: the pair counts in K and adds nothing
+ *    else.  Otherwise n_j = h < 0 ? N_j - u_j : N_j + u_j, so the sign of any normal of either cloud
+ *    changes no bit of a run (estimated normals have no consistent orientation).
+ * 3. v_j = (p_j - c) + (y_j - c), a_j = [v_j x n_j ; n_j], r_j = (dx nx + dy ny) + dz nz; A = sum a a^T,
+ *    b = -sum a r, the count, and with robust weights w(r * r), W and K+: the plane metric's sums.
+ * 4. The least counts (K, K+, the trim's T >= 6), the scaled Cholesky, the 1e-12 pivot,
+ *    ICP_E_TOO_FEW_POINTS and ICP_E_DEGENERATE: the plane metric's.
+ * 5. With a~ = x[0..2], t~ = x[3..5]: aa = (a~0^2 + a~1^2) + a~2^2, g = 1 / sqrt(1 + aa), k2 = g g / (1 + g),
+ *    R_h = I + g [a~]x + k2 [a~]x^2 (the half rotation; g is the half angle's cosine: no trigonometry),
+ *    R = R_h R_h, t = ((R_h (g t~)) + c) - R c, s = 1: q = c + R_h (R_h (p - c) + g t~) -- the scene turns
+ *    half way towards the model and the model, implicitly, half way back.
+ * 6. Every point moves by (R, t); the step is composed into icp_get_transform's total.
+ * 7. err = (e + e) / K with e = sum over the kept pairs of ((q_j - y_j) . n'_j)^2, n'_j formed by rule 2
+ *    from N_j and u'_j = Q' u0_j, Q' the total's rotation with this step composed.  n is a sum of two
+ *    unit normals, so this err -- icp_result.err, the error trace, and what the threshold of icp_run
+ *    is compared with -- is up to FOUR TIMES the one-sided metric's for the same pose.
+ * It works with the gate, the trim, robust weights, ranks and communicators as the plane metric
+ * does, in the same launch loop.  on = 0 (the default), or the point-to-point metric: icp_run
+ * exactly as without this call, whether or not scene normals are resident.  A value other than 0
+ * or 1 is ICP_E_ARG.  The setting survives icp_set_scene / icp_set_model, like the metric.  With it on,
+ * icp_run without model normals or without scene normals returns ICP_E_NO_MODEL, and icp_last_error
+ * names the missing setter. */
+int icp_set_plane_symmetric(icp_ctx *ctx, int on);
+/* The resident scene's normals: n_xyz is a host array, 3 x np_local column-major like a cloud, row j
+ * belonging to point j of this rank's scene as icp_set_scene* received it, in that scene's frame.
+ * The context keeps them AS GIVEN (u0): never renormalised, never rewritten.  The CURRENT normal of
+ * point j is u_j = Q u0_j with Q the rotation of icp_get_transform, so the normals follow every applied
+ * iteration of every icp_run (whatever its loop or metric) and every icp_transform_scene; a frozen
+ * iteration does not move them.  ICP_E_NO_MODEL without a scene, ICP_E_SIZE_MISMATCH if np_local
+ * differs from the resident scene's, ICP_E_ARG for a null pointer or a non-finite value.  Every
+ * icp_set_scene* call drops them, and icp_voxel_downsample* does not carry them. */
+int icp_set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t np_local);
+/* The same array already in device memory, read like icp_set_scene_device's (after the work of any
+ * stream; valid until the call returns); its values are not checked for finiteness. */
+int icp_set_scene_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t np_local);
+/* The CURRENT normals Q u0, in the caller's point order, to a host array (3 x np_local);
+ * ICP_E_NO_MODEL without a scene or without scene normals. */
+int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz);
+/* The normals of the resident scene, estimated from the scene itself with icp_estimate_model_normals'
+ * kernels over a temporary grid of the scene: steps 1-4 of that contract with "model" read as
+ * "scene", ties going to the lower index in the caller's point order.  The result is bit for bit
+ * what icp_estimate_model_normals(k, viewpoint) gives on a fresh context whose model is these scene
+ * points, and becomes the context's scene normals as icp_set_scene_normals_device leaves them.
+ * Allowed only on an unsharded scene (np_local == np_total) that no icp_run or icp_transform_scene
+ * has touched since icp_set_scene*: otherwise ICP_E_ARG, and icp_last_error says which.  k as the
+ * model's estimator checks it (3 <= k <= 64, k <= np_local); ICP_E_NO_MODEL without a scene;
+ * ICP_E_RANGE for a scene with a non-finite coordinate.  It touches nothing a run depends on except
+ * the scene normals, and needs no model. */
+int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate);
 
 /* ---- coarse-to-fine: the total transform, a pose for the scene, a voxel downsample -- */
 /* icp_get_transform: the similarity q = s R p + t (R row-major) that maps the scene as icp_set_scene*

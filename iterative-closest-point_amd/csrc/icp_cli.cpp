@@ -22,6 +22,15 @@
 //   --estimate-normals K  the model's normals estimated from its own K nearest neighbours (3 <= K <= 64,
 //                      K <= the model's size; icp_estimate_model_normals): the same metric as --normals,
 //                      which it excludes
+//   --symmetric        the symmetric point-to-plane iteration (icp_set_plane_symmetric): needs one source of
+//                      model normals (--normals | --estimate-normals) and one of scene normals
+//                      (--scene-normals | --estimate-scene-normals); its error is along a sum of two normals,
+//                      up to four times the one-sided metric's (--threshold compares with it)
+//   --scene-normals FILE  the scene's normals, a CSV in the clouds' format with one row per scene point, in
+//                      the frame of the scene file; excludes --estimate-scene-normals and --pyramid
+//   --estimate-scene-normals K  the scene's normals estimated from its own K nearest neighbours (3 <= K <= 64,
+//                      K <= the scene's size; icp_estimate_scene_normals); with --pyramid per level
+//   --write-scene-normals FILE  writes the scene's current normals after the run (icp_get_scene_normals)
 //   --robust huber|tukey|cauchy  robust weights on the kept pairs (icp_set_robust): needs --robust-k
 //   --robust-k K       the weights' scale, in the clouds' units (> 0); needs --robust
 //   --write-normals FILE  writes the normals the run used (either option's) in the clouds' format
@@ -62,6 +71,7 @@ int main(int argc, char **argv)
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
         std::printf("       options: [--max-dist X] [--trim F] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
+                    "[--symmetric] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
         return -1;
@@ -73,6 +83,8 @@ int main(int argc, char **argv)
     double threshold = 1e-5, max_dist = 0.0;
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
     const char *robust = nullptr, *robust_k = nullptr, *trim = nullptr;
+    const char *scene_normals = nullptr, *estimate_scene = nullptr, *write_scene_normals = nullptr;
+    bool symmetric = false;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
@@ -88,6 +100,10 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
         else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
+        else if (!std::strcmp(argv[a], "--symmetric")) symmetric = true;
+        else if (!std::strcmp(argv[a], "--scene-normals") && a + 1 < argc) scene_normals = argv[++a];
+        else if (!std::strcmp(argv[a], "--estimate-scene-normals") && a + 1 < argc) estimate_scene = argv[++a];
+        else if (!std::strcmp(argv[a], "--write-scene-normals") && a + 1 < argc) write_scene_normals = argv[++a];
         else if (!std::strcmp(argv[a], "--robust") && a + 1 < argc) robust = argv[++a];
         else if (!std::strcmp(argv[a], "--robust-k") && a + 1 < argc) robust_k = argv[++a];
         else if (!std::strcmp(argv[a], "--pyramid") && a + 1 < argc) pyramid = argv[++a];
@@ -118,6 +134,31 @@ int main(int argc, char **argv)
     }
     if (write_normals && !normals && !estimate) {
         std::fprintf(stderr, "[error] --write-normals needs --normals or --estimate-normals\n");
+        return -1;
+    }
+
+    // the scene normals' options and the symmetric switch, likewise
+    int est_scene_k = 0;
+    if (estimate_scene) {
+        char *end = nullptr;
+        const long v = std::strtol(estimate_scene, &end, 10);
+        if (end == estimate_scene || *end || v < 3 || v > 64) {
+            std::fprintf(stderr, "[error] --estimate-scene-normals: K = %s is not an integer in [3, 64]\n", estimate_scene);
+            return -1;
+        }
+        est_scene_k = (int)v;
+        if (scene_normals) {
+            std::fprintf(stderr, "[error] --estimate-scene-normals and --scene-normals exclude each other\n");
+            return -1;
+        }
+    }
+    if (symmetric && (!(normals || estimate) || !(scene_normals || estimate_scene))) {
+        std::fprintf(stderr, "[error] --symmetric needs the model's normals (--normals or --estimate-normals) and the "
+                             "scene's (--scene-normals or --estimate-scene-normals)\n");
+        return -1;
+    }
+    if (write_scene_normals && !scene_normals && !estimate_scene) {
+        std::fprintf(stderr, "[error] --write-scene-normals needs --scene-normals or --estimate-scene-normals\n");
         return -1;
     }
 
@@ -175,6 +216,11 @@ int main(int argc, char **argv)
                                  "full model): use --estimate-normals\n");
             return -1;
         }
+        if (scene_normals) {
+            std::fprintf(stderr, "[error] --pyramid and --scene-normals exclude each other (the file's rows belong to the "
+                                 "full scene): use --estimate-scene-normals\n");
+            return -1;
+        }
     }
     if (pyramid_iters) {
         char *end = nullptr;
@@ -194,6 +240,17 @@ int main(int argc, char **argv)
     double *nrm = normals ? load_or_exit(normals, &nn) : nullptr;
     if (normals && nn != nm) {
         std::fprintf(stderr, "[error] --normals: %zu rows for a model of %zu points\n", nn, nm);
+        return -1;
+    }
+
+    size_t nsn = 0;
+    double *snrm = scene_normals ? load_or_exit(scene_normals, &nsn) : nullptr;
+    if (scene_normals && nsn != np) {
+        std::fprintf(stderr, "[error] --scene-normals: %zu rows for a scene of %zu points\n", nsn, np);
+        return -1;
+    }
+    if (estimate_scene && (size_t)est_scene_k > np) {
+        std::fprintf(stderr, "[error] --estimate-scene-normals: K = %d exceeds the scene's %zu points\n", est_scene_k, np);
         return -1;
     }
 
@@ -235,6 +292,16 @@ int main(int argc, char **argv)
     const auto die = [&](const char *what) {
         std::fprintf(stderr, "[error] %s: %s: %s\n", what, icp_strerror(rc), icp_last_error(ctx));
         return 3;
+    };
+    if ((rc = icp_set_plane_symmetric(ctx, symmetric ? 1 : 0)) != ICP_OK) return die("--symmetric");
+    const auto write_scene = [&]() { // --write-scene-normals: the current normals, the clouds' format
+        std::vector<double> nout(3 * np);
+        if ((rc = icp_get_scene_normals(ctx, nout.data())) != ICP_OK) return die("--write-scene-normals");
+        if (icp_write_matrix(write_scene_normals, nout.data(), np) != ICP_OK) {
+            std::fprintf(stderr, "[error] cannot write %s\n", write_scene_normals);
+            return 2;
+        }
+        return 0;
     };
     const auto write_total = [&]() { // --write-transform: [sR t; 0 0 0 1] in the CSV style
         double s = 1.0, R[9], t[3];
@@ -278,6 +345,14 @@ int main(int argc, char **argv)
                                  est_k, L.m.size() / 3, L.h);
                     return -1;
                 }
+        if (estimate_scene)
+            for (const Level &L : levels)
+                if (L.p.size() / 3 < (size_t)est_scene_k) {
+                    std::fprintf(stderr,
+                                 "[error] --estimate-scene-normals: K = %d exceeds the %zu scene points of the level h=%g\n",
+                                 est_scene_k, L.p.size() / 3, L.h);
+                    return -1;
+                }
         if (estimate && (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK) return die("--estimate-normals");
         double s = 1.0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
         double *errs = (double *)std::calloc((size_t)(max_iter > level_iter ? max_iter : level_iter) + 1, sizeof(double));
@@ -290,8 +365,10 @@ int main(int argc, char **argv)
             if ((rc = icp_set_model(ctx, lm, lnm)) != ICP_OK) return die("--pyramid");
             if (estimate && (rc = icp_estimate_model_normals(ctx, est_k, nullptr, nullptr)) != ICP_OK)
                 return die("--estimate-normals");
-            if ((rc = icp_set_scene(ctx, lp, lnp, lnp)) != ICP_OK || (rc = icp_transform_scene(ctx, s, R, t)) != ICP_OK)
-                return die("--pyramid");
+            if ((rc = icp_set_scene(ctx, lp, lnp, lnp)) != ICP_OK) return die("--pyramid");
+            if (estimate_scene && (rc = icp_estimate_scene_normals(ctx, est_scene_k, nullptr, nullptr)) != ICP_OK)
+                return die("--estimate-scene-normals");
+            if ((rc = icp_transform_scene(ctx, s, R, t)) != ICP_OK) return die("--pyramid");
             if (full) // the fine run's lines, as a plain run prints them
                 icp_set_progress(
                     ctx,
@@ -312,6 +389,10 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "[error] cannot write %s\n", write_normals);
                 return 2;
             }
+        }
+        if (write_scene_normals) {
+            const int w = write_scene();
+            if (w) return w;
         }
         if (write_transform) {
             const int w = write_total();
@@ -348,6 +429,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[normals] estimated from %d neighbours; %lld of %zu undetermined (zero)\n", est_k,
                      degenerate, nm);
     }
+    if (scene_normals && (rc = icp_set_scene_normals(ctx, snrm, nsn)) != ICP_OK) return die("--scene-normals");
+    if (estimate_scene) {
+        long long degenerate = 0;
+        if ((rc = icp_estimate_scene_normals(ctx, est_scene_k, nullptr, &degenerate)) != ICP_OK)
+            return die("--estimate-scene-normals");
+        std::fprintf(stderr, "[normals] the scene's estimated from %d neighbours; %lld of %zu undetermined (zero)\n",
+                     est_scene_k, degenerate, np);
+    }
     if (write_normals) {
         double *nout = (double *)std::malloc(sizeof(double) * 3 * nm);
         if (!nout || (rc = icp_get_model_normals(ctx, nout)) != ICP_OK) {
@@ -371,6 +460,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
     }
+    if (write_scene_normals) {
+        const int w = write_scene();
+        if (w) return w;
+    }
     if (write_transform) {
         const int w = write_total();
         if (w) return w;
@@ -389,5 +482,6 @@ int main(int argc, char **argv)
     icp_free(m);
     icp_free(p);
     icp_free(nrm);
+    icp_free(snrm);
     return 0;
 }

@@ -325,6 +325,15 @@ struct icp_ctx {
     double4 *n4 = nullptr;
     size_t n4_cap = 0;
     bool has_normals = false;
+    // The symmetric form (icp_set_plane_symmetric): the scene's normals u0 as given, in the caller's
+    // order (sn; dropped with the scene, kept across icp_transform_scene), and for a scene in slot
+    // order their copy in that order (sn_slot, made at the first symmetric run that needs it;
+    // sn_slot_valid falls with every change of the scene's order).  scene_pristine: no icp_run or
+    // icp_transform_scene since icp_set_scene* (icp_estimate_scene_normals' condition).
+    bool plane_symmetric = false;
+    DevCloud sn, sn_slot;
+    bool has_scene_normals = false, sn_slot_valid = false;
+    bool scene_pristine = false;
     // icp_model_knn's nm x k lists and the estimator's counters (icp_normals.hip): scratch of those two
     // calls alone, so that they leave everything a run reads as they found it
     int *knn_idx = nullptr;
@@ -501,6 +510,7 @@ int grid_budget(const icp_ctx *ctx);
 bool want_slot_order(const icp_ctx *ctx, size_t n);
 int scene_revert_now(icp_ctx *ctx);
 int scene_to_slot_order(icp_ctx *ctx);
+int scene_normals_current(icp_ctx *ctx, const DevCloud **out);
 int fold_cert_counts(icp_ctx *ctx);
 int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipEvent_t ev0, hipEvent_t ev1,
                     bool zero_counts = true, const SeedState *ws = nullptr, const int *stop = nullptr,

@@ -391,6 +391,7 @@ int scene_revert_now(icp_ctx *ctx)
     ctx->scene_slot = false;
     ctx->scene_revert = false;
     ctx->p32_stale = false;
+    ctx->sn_slot_valid = false;
     return ICP_OK;
 }
 
@@ -419,6 +420,25 @@ int scene_to_slot_order(icp_ctx *ctx)
         std::swap(ctx->idx_cap, ctx->s_tmp_idx_cap);
     }
     ctx->scene_slot = true;
+    ctx->sn_slot_valid = false;
+    return ICP_OK;
+}
+
+// u0 in the scene's current order: the caller's, or for a scene in slot order its copy in that
+// order, permuted as the scene was (once per order: sn_slot_valid)
+int scene_normals_current(icp_ctx *ctx, const DevCloud **out)
+{
+    *out = &ctx->sn;
+    const size_t n = ctx->scene.n;
+    if (!ctx->scene_slot || !n) return ICP_OK;
+    if (!ctx->sn_slot_valid) {
+        TRY(grow_cloud(ctx, ctx->sn_slot, n, false));
+        launch_permute_cloud(ctx->s_order, (int)n, 0, ctx->sn.x, ctx->sn.y, ctx->sn.z, nullptr, nullptr, ctx->sn_slot.x,
+                             ctx->sn_slot.y, ctx->sn_slot.z, nullptr, nullptr, ctx->st);
+        LAUNCHCHK("scene_normals_to_slot_order");
+        ctx->sn_slot_valid = true;
+    }
+    *out = &ctx->sn_slot;
     return ICP_OK;
 }
 
@@ -1243,6 +1263,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
     free_cloud(ctx->qa);
     free_cloud(ctx->qb);
     free_cloud(ctx->s_tmp);
+    free_cloud(ctx->sn);
+    free_cloud(ctx->sn_slot);
     for (void *p : {(void *)ctx->m32, (void *)ctx->mperm, (void *)ctx->mm, (void *)ctx->mimg16,
                     (void *)ctx->mms16, ctx->part2,
                     (void *)ctx->amb1, (void *)ctx->idx, ctx->part, (void *)ctx->amb_count,
@@ -1887,6 +1909,9 @@ static int set_scene_common(icp_ctx *ctx, size_t np_local, size_t np_total, bool
     ctx->scene_slot = slot;     // (else in the caller's order)
     ctx->scene_revert = false;
     ctx->p32_stale = false;
+    ctx->has_scene_normals = false; // (the scene's normals belong to the scene they were given for)
+    ctx->sn_slot_valid = false;
+    ctx->scene_pristine = true;
     // ICP_EAGER_BUNDLE=1: a shard against a model of at least twice its points (C5's 8-way shards)
     // gets the bundle images here instead of at their first use.  Round 4 built them here always:
     // its far rule sent a C5 shard's first searches to the bundle cascade.  With the box rule
@@ -1917,6 +1942,178 @@ int icp_get_scene(icp_ctx *ctx, double *p_xyz_out)
         return download_cloud(ctx, ctx->s_tmp, P.n, p_xyz_out);
     }
     return download_cloud(ctx, ctx->scene, ctx->scene.n, p_xyz_out);
+}
+
+// ---- the scene's normals (the symmetric point-to-plane iteration) ------------------------
+
+int icp_set_plane_symmetric(icp_ctx *ctx, int on)
+{
+    if (!ctx || (on != 0 && on != 1)) return ICP_E_ARG;
+    ctx->plane_symmetric = on == 1;
+    return ICP_OK;
+}
+
+static int scene_normals_args(icp_ctx *ctx, const double *n_xyz, size_t np_local)
+{
+    if (!ctx || !n_xyz) return ICP_E_ARG;
+    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, "icp_set_scene_normals: no scene (icp_set_scene)");
+    if (np_local != ctx->scene.n)
+        return fail(ctx, ICP_E_SIZE_MISMATCH, "icp_set_scene_normals: " + std::to_string(np_local) +
+                                                  " normals for a scene of " + std::to_string(ctx->scene.n) + " points");
+    HIPCHK(hipSetDevice(ctx->device));
+    return ICP_OK;
+}
+
+// u0 (the caller's order) from the interleaved array in device memory
+static int set_scene_normals_from(icp_ctx *ctx, const double *aos_dev, size_t n)
+{
+    ctx->has_scene_normals = false; // (until the new ones are complete)
+    ctx->sn_slot_valid = false;
+    TRY(grow_cloud(ctx, ctx->sn, n, false));
+    if (n) launch_aos_to_soa(aos_dev, n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
+    LAUNCHCHK("scene_normals");
+    HIPCHK(hipStreamSynchronize(ctx->st)); // (the caller's array, or the stage, is free again)
+    ctx->has_scene_normals = true;
+    return ICP_OK;
+}
+
+int icp_set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t np_local)
+{
+    TRY(scene_normals_args(ctx, n_xyz, np_local));
+    for (size_t k = 0; k < 3 * np_local; ++k)
+        if (!std::isfinite(n_xyz[k]))
+            return fail(ctx, ICP_E_ARG, "icp_set_scene_normals: normal " + std::to_string(k / 3) + " is not finite");
+    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * np_local));
+    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * np_local, hipMemcpyHostToDevice, ctx->st));
+    return set_scene_normals_from(ctx, ctx->stage, np_local);
+}
+
+int icp_set_scene_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t np_local)
+{
+    TRY(scene_normals_args(ctx, n_xyz_dev, np_local));
+    HIPCHK(hipDeviceSynchronize()); // (as icp_set_scene_device: after the work of any stream)
+    return set_scene_normals_from(ctx, n_xyz_dev, np_local);
+}
+
+int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
+{
+    if (!ctx) return ICP_E_ARG;
+    if (!n_xyz && ctx->scene.n) return fail(ctx, ICP_E_ARG, "icp_get_scene_normals: n_xyz is null");
+    if (!ctx->has_scene || !ctx->has_scene_normals)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_get_scene_normals: the scene has no normals (icp_set_scene_normals, "
+                                         "icp_estimate_scene_normals)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = ctx->scene.n;
+    TRY(download_cloud(ctx, ctx->sn, n, n_xyz)); // u0, the caller's order
+    if (ctx->tot_n == 0) return ICP_OK;
+    const double *Q = ctx->tot + 1; // u = Q u0, each row ((Q0 u0 + Q1 u1) + Q2 u2) as the kernels sum it
+    for (size_t j = 0; j < n; ++j) {
+        const double a0 = n_xyz[3 * j], a1 = n_xyz[3 * j + 1], a2 = n_xyz[3 * j + 2];
+        for (int r = 0; r < 3; ++r) n_xyz[3 * j + r] = (Q[3 * r] * a0 + Q[3 * r + 1] * a1) + Q[3 * r + 2] * a2;
+    }
+    return ICP_OK;
+}
+
+int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
+{
+    if (!ctx) return ICP_E_ARG;
+    const char *who = "icp_estimate_scene_normals";
+    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, std::string(who) + ": no scene (icp_set_scene)");
+    const size_t n = ctx->scene.n;
+    if (n != ctx->np_total)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": the scene is sharded (" + std::to_string(n) + " of " +
+                                        std::to_string(ctx->np_total) + " points on this rank)");
+    if (!ctx->scene_pristine)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": an icp_run or icp_transform_scene has moved the scene since "
+                                                       "icp_set_scene");
+    if (k < kKnnMinK || k > kKnnMaxK)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " is outside [" +
+                                        std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
+    if ((size_t)k > n)
+        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " exceeds the scene's " +
+                                        std::to_string(n) + " points");
+    if (viewpoint)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(viewpoint[a]))
+                return fail(ctx, ICP_E_ARG, std::string(who) + ": viewpoint[" + std::to_string(a) + "] = " +
+                                                std::to_string(viewpoint[a]) + " is not finite");
+    HIPCHK(hipSetDevice(ctx->device));
+    static const bool debug = getenv("ICP_NORMALS_DEBUG") != nullptr;
+    // the scene in the caller's order (a copy when it is resident in slot order), its interleaved
+    // copy for the box, its double4 rows: what icp_set_model makes of a model's upload
+    const DevCloud *P = &ctx->scene;
+    if (ctx->scene_slot) {
+        TRY(grow_cloud(ctx, ctx->s_tmp, n, true));
+        launch_permute_cloud(ctx->s_order, (int)n, 1, ctx->scene.x, ctx->scene.y, ctx->scene.z, nullptr, nullptr,
+                             ctx->s_tmp.x, ctx->s_tmp.y, ctx->s_tmp.z, nullptr, nullptr, ctx->st);
+        LAUNCHCHK("scene_to_file_order");
+        P = &ctx->s_tmp;
+    }
+    if (!ctx->mstat_part) {
+        HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
+        HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
+        HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
+    }
+    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+    launch_soa_to_aos(P->x, P->y, P->z, n, ctx->stage, ctx->st);
+    launch_model_stats(ctx->stage, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
+    LAUNCHCHK("scene_stats");
+    HIPCHK(hipMemcpyAsync(ctx->h_mstat, ctx->mstat_out, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, std::string(who) + ": the scene has non-finite coordinates");
+    const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
+    const long long ncell = grid_cells(gp);
+    const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
+    // the temporary grid and rows: freed before the call returns, whatever it returns
+    struct Temp {
+        void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Temp()
+        {
+            for (void *q : p)
+                if (q) (void)hipFree(q);
+        }
+    } tmp;
+    HIPCHK(hipMalloc(&tmp.p[0], sizeof(double4) * n));                 // the scene's rows
+    HIPCHK(hipMalloc(&tmp.p[1], sizeof(int) * ((size_t)ncell + 1)));   // the grid's offsets
+    HIPCHK(hipMalloc(&tmp.p[2], sizeof(double4) * n));                 // its points
+    HIPCHK(hipMalloc(&tmp.p[3], sizeof(float4) * n));                  // their fp32 image
+    HIPCHK(hipMalloc(&tmp.p[4], gbytes ? gbytes : 1));                 // the build's sort scratch
+    HIPCHK(hipMalloc(&tmp.p[5], sizeof(double4) * n));                 // the normals' rows
+    double4 *rows = (double4 *)tmp.p[0], *nrm = (double4 *)tmp.p[5];
+    launch_make_aos4(P->x, P->y, P->z, (int)n, rows, ctx->st);
+    if (launch_grid_build(P->x, P->y, P->z, rows, (int)n, gp, tmp.p[4], gbytes, (int *)tmp.p[1], (double4 *)tmp.p[2],
+                          (float4 *)tmp.p[3], ctx->st) != 0)
+        return fail(ctx, ICP_E_HIP, std::string(who) + ": grid build: radix sort failed");
+    LAUNCHCHK("scene_grid_build");
+    GridView gv{};
+    gv.pts = (const double4 *)tmp.p[2];
+    gv.start = (const int *)tmp.p[1];
+    for (int a = 0; a < 3; ++a) {
+        gv.g[a] = gp.g[a];
+        gv.lo[a] = gp.lo[a];
+        gv.c32[a] = gp.c32[a];
+    }
+    gv.inv_h = gp.inv_h;
+    gv.pts32 = (const float4 *)tmp.p[3];
+    gv.em32 = gp.em32;
+    const int budget = run_knobs().grid_budget
+                           ? run_knobs().grid_budget
+                           : (int)std::min<size_t>(std::max<size_t>(kGridBudget, n / 4), (size_t)1 << 16); // (grid_budget's rule)
+    TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
+    HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
+    launch_model_normals(gv, rows, (int)n, k, budget, viewpoint, nrm, ctx->knn_counters, debug, ctx->st);
+    LAUNCHCHK("scene_normals");
+    ctx->has_scene_normals = false; // (until the new ones are complete)
+    ctx->sn_slot_valid = false;
+    TRY(grow_cloud(ctx, ctx->sn, n, false));
+    launch_rows4_to_soa(nrm, (int)n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
+    LAUNCHCHK("scene_normals_rows");
+    unsigned long long c[kKnnCounters];
+    HIPCHK(hipMemcpyAsync(c, ctx->knn_counters, sizeof(c), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    ctx->has_scene_normals = true;
+    if (degenerate) *degenerate = (long long)c[0];
+    return ICP_OK;
 }
 
 // ---- the total transform, a pose for the resident scene, the voxel downsample -----------
@@ -1979,10 +2176,13 @@ int icp_transform_scene(icp_ctx *ctx, double s, const double R[9], const double 
     }
     double tot[13];
     const int tot_n = ctx->tot_n;
+    const bool normals = ctx->has_scene_normals; // (u0 stays as given: the total turns it)
     std::memcpy(tot, ctx->tot, sizeof(tot));
     TRY(set_scene_common(ctx, n, ctx->np_total, slot));
     std::memcpy(ctx->tot, tot, sizeof(tot));
     ctx->tot_n = tot_n;
+    ctx->has_scene_normals = normals;
+    ctx->scene_pristine = false;
     compose_srt(step, ctx->tot, &ctx->tot_n);
     return ICP_OK;
 }

@@ -227,9 +227,9 @@ void launch_kept_first_shift(IterState *st_dev, const double *sums, int slot, hi
 
 void launch_kept_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                           const int *idx, const double4 *n4, double *partials, hipStream_t st)
+                           const int *idx, const double4 *n4, double *partials, hipStream_t st, const SymmArgs *symm)
 {
-    if (n4) return plane_transform(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4, partials, st);
+    if (n4) return plane_transform(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4, partials, st, symm);
     gated_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, partials);
 }
 

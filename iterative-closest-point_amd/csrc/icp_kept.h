@@ -20,12 +20,13 @@
 
 namespace icp {
 
-// icp_plane.hip's side of launch_kept_moments, launch_kept_step and launch_kept_transform (icp_gated.hip)
+// icp_plane.hip's side of launch_kept_moments, launch_kept_step and launch_kept_transform (icp_gated.hip);
+// with KeptPass::symm / KeptStep::symm / symm set, the symmetric form's kernels (icp_set_plane_symmetric)
 void plane_moments(const KeptPass &a, bool y_ready);
 void plane_step(const KeptStep &a, const double *partials, int nblocks, bool step);
 void plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,
                      const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask, const int *idx,
-                     const double4 *n4, double *partials, hipStream_t st);
+                     const double4 *n4, double *partials, hipStream_t st, const SymmArgs *symm);
 
 namespace {
 

@@ -820,9 +820,20 @@ struct GateState {
     double W;         // a robust run (icp_set_robust): the kept pairs' weights summed, all ranks', of that gate
     long long Kpos;   // ... and the kept pairs with a weight > 0
 };
+// The symmetric form of the point-to-plane iteration (icp_set_plane_symmetric): the scene's normals u0 as
+// given, in the scene's current order, and what the current ones u = Q u0 need -- Q is the rotation of
+// the total since icp_set_scene*: the run's so far (st->tot) composed onto the context's at the run's
+// start (q0 row-major; have_q0 = 0: the identity, not multiplied).  Passed to the kernels by value.
+struct SymmArgs {
+    const double *ux, *uy, *uz;
+    const IterState *st;
+    double q0[9];
+    int have_q0;
+};
 // What a moments pass reads and writes (host side: the launcher hands the kernels plain arguments).
 struct KeptPass {
     bool plane;                    // the point-to-plane metric: n4 and c are read
+    const SymmArgs *symm;          // ... in its symmetric form (null: one-sided)
     int robust_kind;               // kRobust*; with a weight, k and k2 = k * k
     double k, k2;
     const int *idx;                // the search's correspondences; kpos / m4kd: its kd-ordered form, or null
@@ -848,6 +859,7 @@ void launch_kept_moments(const KeptPass &a, bool y_ready);
 // What the fold + step of the moments reads and writes.
 struct KeptStep {
     bool plane, robust;
+    bool symm;                     // the plane metric's symmetric step (the half rotation, twice)
     bool trim_few;                 // the trim's T is below the metric's least count: stops the run as K below it
     double *sums;
     double c[3];
@@ -870,10 +882,12 @@ void launch_kept_step(const KeptStep &a, const double *partials, int nblocks, bo
 // kGateCount, their weighted centroids with kRobustGateW
 void launch_kept_first_shift(IterState *st_dev, const double *sums, int slot, hipStream_t st);
 // p <- sR p + t for every point (p32 nullable); partial [sum over the kept points (the mask) of the
-// metric's squared residual: ||y - p'||^2, or with n4 (the plane metric) ((p' - y) . n)^2, n = n4[idx[i]]]
+// metric's squared residual: ||y - p'||^2, or with n4 (the plane metric) ((p' - y) . n)^2, n = n4[idx[i]],
+// or with symm the pair's normal from n4[idx[i]] and the scene's own, turned by the total with this step]
 void launch_kept_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
-                           const int *idx, const double4 *n4, double *partials, hipStream_t st);
+                           const int *idx, const double4 *n4, double *partials, hipStream_t st,
+                           const SymmArgs *symm = nullptr);
 // nblocks > 0: sums[kSumErr] = the fold of the partial rows; step: launch_err_step's with N =
 // gate->K, and h_ktrace[iter] = K for a recorded iteration
 void launch_gated_err(const double *partials, int nblocks, double *sums, bool step, double threshold, int max_iter,
@@ -883,6 +897,8 @@ void launch_gated_err(const double *partials, int nblocks, double *sums, bool st
 void launch_gated_unpack(const unsigned long long *mask, const int *order, int n, unsigned char *out, hipStream_t st);
 // n4[i] = (n_i, 0) from nm interleaved xyz normals in device memory
 void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t st);
+// (x, y, z)[i] = rows[i].xyz (icp_estimate_scene_normals: the estimator's rows into the scene normals' streams)
+void launch_rows4_to_soa(const double4 *rows, int n, double *x, double *y, double *z, hipStream_t st);
 
 // ---- the k-th smallest of n doubles (icp_select.hip; icp_set_trim, icp_select_kth) ---------------
 // An MSB-first radix select over the 64-bit keys of the doubles (the monotone map of their bit

@@ -693,12 +693,20 @@ template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int m
 // moments pass then runs in its streamed form with the cut's address.  With ranks each pass's bins are all-reduced before its pick (kSelectPasses more all-reduces an
 // iteration).  T below the metric's least count stops the run as K below it does.  A trimmed run
 // counts as a gated one for icp_get_inliers, and leaves icp_get_trim_trace its C trace.
+// With icp_set_plane_symmetric the plane metric's three launches are their symmetric kernels
+// (icp_plane.hip: symm_*), which also read the scene's normals u0 in the scene's current order and the
+// total since icp_set_scene* (SymmArgs: the context's at the run's start, the run's own from the loop
+// state); everything else of the loop, the sums' width and the all-reduces included, is the plane metric's.
 int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
              std::chrono::steady_clock::time_point wall0)
 {
     const bool plane = ctx->metric == ICP_METRIC_POINT_TO_PLANE;
     if (plane && !ctx->has_normals)
         return fail(ctx, ICP_E_NO_MODEL, "icp_run: the point-to-plane metric needs the model's normals (icp_set_model_normals)");
+    const bool symm = plane && ctx->plane_symmetric;
+    if (symm && !ctx->has_scene_normals)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_run: the symmetric point-to-plane iteration needs the scene's normals "
+                                         "(icp_set_scene_normals, icp_estimate_scene_normals)");
     if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
     const size_t n = ctx->scene.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
@@ -741,8 +749,21 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     // The metric's launches: the moments' pass with its fold, and the fold of the moments' partial
     // rows and / or the step on the folded (all ranks') sums.  Their arguments hold for the run, but
     // for what a search leaves (it may allocate idx and the kd-ordered form): taken at each pass.
+    // The symmetric form: u0 in the scene's current order (a scene in slot order: its copy in that
+    // order, made once per order), and the context's total at the run's start, which the kernels
+    // compose the run's own onto.
+    SymmArgs sy = {};
+    if (symm) {
+        const DevCloud *U = nullptr;
+        TRY(scene_normals_current(ctx, &U));
+        sy.ux = U->x, sy.uy = U->y, sy.uz = U->z;
+        sy.st = sd;
+        sy.have_q0 = ctx->tot_n > 0 ? 1 : 0;
+        for (int k = 0; k < 9; ++k) sy.q0[k] = sy.have_q0 ? ctx->tot[1 + k] : (k % 4 == 0 ? 1.0 : 0.0);
+    }
     KeptPass pass = {};
     pass.plane = plane;
+    pass.symm = symm ? &sy : nullptr;
     pass.robust_kind = robust;
     pass.k = ctx->robust_k, pass.k2 = ctx->robust_k2;
     pass.m4 = ctx->m4, pass.n4 = ctx->n4;
@@ -755,6 +776,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     pass.st = ctx->st;
     KeptStep fold = {};
     fold.plane = plane, fold.robust = robust != 0, fold.trim_few = trim_few;
+    fold.symm = symm;
     fold.sums = ctx->sums, fold.amb_count = ctx->amb_count;
     fold.st_dev = sd, fold.h_state = ctx->d_iter_mirror;
     fold.gate = ctx->kept_state, fold.h_gate = ctx->d_kept_mirror;
@@ -824,7 +846,8 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             }
             // 5-6. every point moves; the kept points' residual; err = (e + e) / K
             launch_kept_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                  ctx->kept_mask, ctx->idx, plane ? ctx->n4 : nullptr, ctx->partials, ctx->st);
+                                  ctx->kept_mask, ctx->idx, plane ? ctx->n4 : nullptr, ctx->partials, ctx->st,
+                                  symm ? &sy : nullptr);
             if (!need_p32) ctx->p32_stale = true;
             const int sl = r.enqueued % kRing;
             r.slot_ticket[sl] = ++ctx->flag_ticket;
@@ -1766,6 +1789,7 @@ extern "C" int icp_run(icp_ctx *ctx, int max_iter, double threshold, double *err
     // (icp_set_progress: reset once per icp_run -- a rerun below replays the same iterations bit for
     // bit, and report_progress skips the ones the aborted attempt already reported)
     if (ctx) ctx->progress_next = 0;
+    if (ctx) ctx->scene_pristine = false; // (icp_estimate_scene_normals: the scene as icp_set_scene* received it only)
     const int r = run_loop(ctx, max_iter, threshold, err_trace, res, false);
     if (r != kTailAborted) return r;
     // A grid barrier of the fused mid-size tail timed out (its workgroups were not all resident:

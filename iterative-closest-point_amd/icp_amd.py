@@ -81,6 +81,8 @@ EXPORTED = [
     "icp_set_robust", "icp_get_robust_trace",
     "icp_voxel_downsample", "icp_voxel_downsample_device", "icp_get_transform", "icp_transform_scene",
     "icp_set_trim", "icp_get_trim_trace", "icp_select_kth",
+    "icp_set_plane_symmetric", "icp_set_scene_normals", "icp_set_scene_normals_device", "icp_get_scene_normals",
+    "icp_estimate_scene_normals",
 ]
 
 
@@ -213,6 +215,12 @@ def lib() -> C.CDLL:
         L.icp_set_trim.argtypes = [vp, C.c_double]
         L.icp_get_trim_trace.argtypes = [vp, dp, sz]
         L.icp_select_kth.argtypes = [C.c_int, dp, sz, sz, dp]
+    if hasattr(L, "icp_set_plane_symmetric"):
+        L.icp_set_plane_symmetric.argtypes = [vp, C.c_int]
+        L.icp_set_scene_normals.argtypes = [vp, dp, sz]
+        L.icp_set_scene_normals_device.argtypes = [vp, vp, sz]
+        L.icp_get_scene_normals.argtypes = [vp, dp]
+        L.icp_estimate_scene_normals.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong)]
     _lib = L
     return L
 
@@ -544,6 +552,38 @@ class Context:
         self._check(lib().icp_get_model_normals(self._h, _dp(out)))
         return out[:nm]
 
+    def set_plane_symmetric(self, on):
+        """icp_set_plane_symmetric: with METRIC_POINT_TO_PLANE, run() minimises the symmetric objective
+        (needs set_model_normals and set_scene_normals; its err is up to four times the one-sided one)."""
+        self._check(lib().icp_set_plane_symmetric(self._h, int(on)))
+
+    def set_scene_normals(self, n):
+        """icp_set_scene_normals: one normal per point of the resident scene as set_scene received it,
+        kept as given; the current normals follow the scene (scene_normals)."""
+        n = _cloud(n)
+        self._check(lib().icp_set_scene_normals(self._h, _dp(n), n.shape[0]))
+
+    def set_scene_normals_device(self, ptr: int, np_local: int):
+        """icp_set_scene_normals_device: the normals' AoS fp64 array already in device memory."""
+        self._check(lib().icp_set_scene_normals_device(self._h, C.c_void_p(ptr), np_local))
+
+    def scene_normals(self) -> np.ndarray:
+        """icp_get_scene_normals: the CURRENT normals (np_local, 3), the given ones turned by the
+        rotation of transform(), in the caller's point order."""
+        n = getattr(self, "_np_local", 0)
+        out = np.empty((max(n, 1), 3))
+        self._check(lib().icp_get_scene_normals(self._h, _dp(out)))
+        return out[:n]
+
+    def estimate_scene_normals(self, k: int, viewpoint=None) -> int:
+        """icp_estimate_scene_normals: the resident scene's normals from its own k-neighbourhoods, as
+        estimate_model_normals makes the model's; only on an unsharded scene no run() or
+        transform_scene() has touched.  Returns how many points got a zero normal."""
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        deg = C.c_longlong(0)
+        self._check(lib().icp_estimate_scene_normals(self._h, int(k), None if v is None else _dp(v), C.byref(deg)))
+        return int(deg.value)
+
     def inliers(self):
         """The last gate of the last gated run() -> (mask: bool (np_local,), caller's order; K over all ranks)."""
         mask = np.zeros(self._np_local, dtype=np.uint8)
@@ -732,7 +772,8 @@ class Context:
 # ---------------------------------------------------------------------------------
 
 def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int | None = None,
-                     threshold: float = 1e-5, estimate_normals: int | None = None):
+                     threshold: float = 1e-5, estimate_normals: int | None = None,
+                     estimate_scene_normals: int | None = None):
     """Coarse-to-fine registration of the scene p onto the model m from the engine's own calls (the
     icp-gpu CLI's --pyramid makes the same calls in the same order).  For each voxel size, in the
     order given (coarse to fine): downsample both clouds, set them with the unequal-size check
@@ -741,6 +782,9 @@ def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int 
     (transform).  Then the full clouds: set them, apply the pose, run max_iter iterations.
     estimate_normals = K: the model's normals are estimated at every level (and for the full
     clouds) from K neighbours; a level whose model has fewer than K points raises before any run.
+    estimate_scene_normals = K: likewise the scene's normals (the symmetric iteration,
+    set_plane_symmetric), estimated after each level's set_scene and before its transform_scene; a
+    level whose scene has fewer than K points raises before any run.
     -> (the fine run's Result, the total (s, R, t), the records: one dict per level -- voxel,
     model_points, scene_points, iterations, err, converged, errs -- and a last one, voxel None, for
     the fine run)."""
@@ -757,6 +801,11 @@ def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int 
             if mc.shape[0] < estimate_normals:
                 raise ValueError(f"--estimate-normals {estimate_normals}: the level h={h:g} has a model of "
                                  f"{mc.shape[0]} points")
+    if estimate_scene_normals is not None:
+        for h, _, pc in clouds:
+            if pc.shape[0] < estimate_scene_normals:
+                raise ValueError(f"--estimate-scene-normals {estimate_scene_normals}: the level h={h:g} has a scene of "
+                                 f"{pc.shape[0]} points")
     clouds.append((None, m, p))
     pose = (1.0, np.eye(3), np.zeros(3))
     records = []
@@ -768,6 +817,8 @@ def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int 
             if estimate_normals is not None:
                 ctx.estimate_model_normals(estimate_normals)
             ctx.set_scene(pc)
+            if estimate_scene_normals is not None:
+                ctx.estimate_scene_normals(estimate_scene_normals)
             ctx.transform_scene(*pose)
             res, errs = ctx.run(max_iter if h is None else k_iter, threshold)
             pose = ctx.transform()
@@ -794,6 +845,7 @@ class ICP:
     estimate_normals: int | None = None  # k: the normals estimated from the model (estimate_model_normals), same metric
     robust: tuple | None = None  # (kind, k): icp_set_robust (None: every kept pair with weight 1)
     trim: float | None = None  # icp_set_trim: the fraction of the pairs each iteration keeps (None: all)
+    scene_normals: np.ndarray | None = None  # the scene's normals too: the symmetric iteration (needs model normals)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -823,6 +875,11 @@ class ICP:
             self._ctx.estimate_model_normals(self.estimate_normals)
             self._ctx.set_metric(METRIC_POINT_TO_PLANE)
         self._ctx.set_scene(self.p)
+        if self.scene_normals is not None:
+            if self.normals is None and self.estimate_normals is None:
+                raise ValueError("ICP: scene_normals need the model's normals (normals or estimate_normals)")
+            self._ctx.set_scene_normals(self.scene_normals)
+            self._ctx.set_plane_symmetric(True)
 
     def find_corresponding_opti(self):
         res, errs = self._ctx.run(self.max_iter, self.threshold)
