@@ -65,6 +65,19 @@ static double *load_or_exit(const char *path, size_t *n)
     return xyz;
 }
 
+// K of --estimate-normals / --estimate-scene-normals: an integer in [3, 64], else the message and false
+static bool parse_k(const char *option, const char *text, int *k)
+{
+    char *end = nullptr;
+    const long v = std::strtol(text, &end, 10);
+    if (end == text || *end || v < 3 || v > 64) {
+        std::fprintf(stderr, "[error] %s: K = %s is not an integer in [3, 64]\n", option, text);
+        return false;
+    }
+    *k = (int)v;
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     const char *prog = std::strrchr(argv[0], '/') ? std::strrchr(argv[0], '/') + 1 : argv[0];
@@ -120,13 +133,7 @@ int main(int argc, char **argv)
     // the normals' options, checked before any file or device is touched
     int est_k = 0;
     if (estimate) {
-        char *end = nullptr;
-        const long v = std::strtol(estimate, &end, 10);
-        if (end == estimate || *end || v < 3 || v > 64) {
-            std::fprintf(stderr, "[error] --estimate-normals: K = %s is not an integer in [3, 64]\n", estimate);
-            return -1;
-        }
-        est_k = (int)v;
+        if (!parse_k("--estimate-normals", estimate, &est_k)) return -1;
         if (normals) {
             std::fprintf(stderr, "[error] --estimate-normals and --normals exclude each other\n");
             return -1;
@@ -140,13 +147,7 @@ int main(int argc, char **argv)
     // the scene normals' options and the symmetric switch, likewise
     int est_scene_k = 0;
     if (estimate_scene) {
-        char *end = nullptr;
-        const long v = std::strtol(estimate_scene, &end, 10);
-        if (end == estimate_scene || *end || v < 3 || v > 64) {
-            std::fprintf(stderr, "[error] --estimate-scene-normals: K = %s is not an integer in [3, 64]\n", estimate_scene);
-            return -1;
-        }
-        est_scene_k = (int)v;
+        if (!parse_k("--estimate-scene-normals", estimate_scene, &est_scene_k)) return -1;
         if (scene_normals) {
             std::fprintf(stderr, "[error] --estimate-scene-normals and --scene-normals exclude each other\n");
             return -1;
@@ -294,11 +295,12 @@ int main(int argc, char **argv)
         return 3;
     };
     if ((rc = icp_set_plane_symmetric(ctx, symmetric ? 1 : 0)) != ICP_OK) return die("--symmetric");
-    const auto write_scene = [&]() { // --write-scene-normals: the current normals, the clouds' format
-        std::vector<double> nout(3 * np);
-        if ((rc = icp_get_scene_normals(ctx, nout.data())) != ICP_OK) return die("--write-scene-normals");
-        if (icp_write_matrix(write_scene_normals, nout.data(), np) != ICP_OK) {
-            std::fprintf(stderr, "[error] cannot write %s\n", write_scene_normals);
+    // --write-normals / --write-scene-normals: a cloud's current normals, the clouds' format
+    const auto write_normals_file = [&](const char *option, int (*get)(icp_ctx *, double *), size_t rows, const char *path) {
+        std::vector<double> nout(3 * rows);
+        if ((rc = get(ctx, nout.data())) != ICP_OK) return die(option);
+        if (icp_write_matrix(path, nout.data(), rows) != ICP_OK) {
+            std::fprintf(stderr, "[error] cannot write %s\n", path);
             return 2;
         }
         return 0;
@@ -315,6 +317,32 @@ int main(int argc, char **argv)
             std::fprintf(f, "%g,%g,%g,%g\n", s * R[3 * r], s * R[3 * r + 1], s * R[3 * r + 2], t[r]);
         std::fprintf(f, "0,0,0,1\n");
         std::fclose(f);
+        return 0;
+    };
+    // What a run ends with: the files asked for, the moved scene, the [output] line.  get_scene: how a
+    // failing icp_get_scene is named (null: not at all).
+    const auto finish = [&](double *errs, const char *get_scene) {
+        int w = 0;
+        if (write_scene_normals &&
+            (w = write_normals_file("--write-scene-normals", icp_get_scene_normals, np, write_scene_normals)) != 0)
+            return w;
+        if (write_transform && (w = write_total()) != 0) return w;
+        if ((rc = icp_get_scene(ctx, p)) != ICP_OK) {
+            if (get_scene) return die(get_scene);
+            std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
+            return 3;
+        }
+        if (icp_write_matrix(out, p, np) != ICP_OK) { // load.cc:68-81
+            std::fprintf(stderr, "[error] cannot write %s\n", out);
+            return 2;
+        }
+        std::fprintf(stderr, "[output] output file \"%s\" was generated.\n", out);
+        icp_ctx_destroy(ctx);
+        std::free(errs);
+        icp_free(m);
+        icp_free(p);
+        icp_free(nrm);
+        icp_free(snrm);
         return 0;
     };
     if (pyramid) {
@@ -338,21 +366,18 @@ int main(int argc, char **argv)
             L.m.resize(3 * cm);
             L.p.resize(3 * cp);
         }
-        if (estimate)
+        // an estimator's K against every level's cloud
+        const auto k_fits = [&](const char *option, int k, const char *word, std::vector<double> Level::*cloud) {
             for (const Level &L : levels)
-                if (L.m.size() / 3 < (size_t)est_k) {
-                    std::fprintf(stderr, "[error] --estimate-normals: K = %d exceeds the %zu model points of the level h=%g\n",
-                                 est_k, L.m.size() / 3, L.h);
-                    return -1;
+                if ((L.*cloud).size() / 3 < (size_t)k) {
+                    std::fprintf(stderr, "[error] %s: K = %d exceeds the %zu %s points of the level h=%g\n", option, k,
+                                 (L.*cloud).size() / 3, word, L.h);
+                    return false;
                 }
-        if (estimate_scene)
-            for (const Level &L : levels)
-                if (L.p.size() / 3 < (size_t)est_scene_k) {
-                    std::fprintf(stderr,
-                                 "[error] --estimate-scene-normals: K = %d exceeds the %zu scene points of the level h=%g\n",
-                                 est_scene_k, L.p.size() / 3, L.h);
-                    return -1;
-                }
+            return true;
+        };
+        if (estimate && !k_fits("--estimate-normals", est_k, "model", &Level::m)) return -1;
+        if (estimate_scene && !k_fits("--estimate-scene-normals", est_scene_k, "scene", &Level::p)) return -1;
         if (estimate && (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK) return die("--estimate-normals");
         double s = 1.0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
         double *errs = (double *)std::calloc((size_t)(max_iter > level_iter ? max_iter : level_iter) + 1, sizeof(double));
@@ -383,32 +408,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[pyramid] total s=%.17g R=%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g t=%.17g,%.17g,%.17g\n", s,
                      R[0], R[1], R[2], R[3], R[4], R[5], R[6], R[7], R[8], t[0], t[1], t[2]);
         if (write_normals) {
-            std::vector<double> nout(3 * nm);
-            if ((rc = icp_get_model_normals(ctx, nout.data())) != ICP_OK) return die("--write-normals");
-            if (icp_write_matrix(write_normals, nout.data(), nm) != ICP_OK) {
-                std::fprintf(stderr, "[error] cannot write %s\n", write_normals);
-                return 2;
-            }
-        }
-        if (write_scene_normals) {
-            const int w = write_scene();
+            const int w = write_normals_file("--write-normals", icp_get_model_normals, nm, write_normals);
             if (w) return w;
         }
-        if (write_transform) {
-            const int w = write_total();
-            if (w) return w;
-        }
-        if ((rc = icp_get_scene(ctx, p)) != ICP_OK) return die("icp_get_scene");
-        if (icp_write_matrix(out, p, np) != ICP_OK) {
-            std::fprintf(stderr, "[error] cannot write %s\n", out);
-            return 2;
-        }
-        std::fprintf(stderr, "[output] output file \"%s\" was generated.\n", out);
-        icp_ctx_destroy(ctx);
-        std::free(errs);
-        icp_free(m);
-        icp_free(p);
-        return 0;
+        return finish(errs, "icp_get_scene");
     }
     if ((rc = icp_set_model(ctx, m, nm)) != ICP_OK || (rc = icp_set_scene(ctx, p, np, np)) != ICP_OK) {
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
@@ -438,16 +441,8 @@ int main(int argc, char **argv)
                      est_scene_k, degenerate, np);
     }
     if (write_normals) {
-        double *nout = (double *)std::malloc(sizeof(double) * 3 * nm);
-        if (!nout || (rc = icp_get_model_normals(ctx, nout)) != ICP_OK) {
-            std::fprintf(stderr, "[error] --write-normals: %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
-            return 3;
-        }
-        if (icp_write_matrix(write_normals, nout, nm) != ICP_OK) {
-            std::fprintf(stderr, "[error] cannot write %s\n", write_normals);
-            return 2;
-        }
-        std::free(nout);
+        const int w = write_normals_file("--write-normals", icp_get_model_normals, nm, write_normals);
+        if (w) return w;
     }
     double *errs = (double *)std::calloc(max_iter > 0 ? (size_t)max_iter : 1, sizeof(double));
     icp_result res{};
@@ -460,28 +455,5 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
         return 3;
     }
-    if (write_scene_normals) {
-        const int w = write_scene();
-        if (w) return w;
-    }
-    if (write_transform) {
-        const int w = write_total();
-        if (w) return w;
-    }
-    if ((rc = icp_get_scene(ctx, p)) != ICP_OK) {
-        std::fprintf(stderr, "[error] %s: %s\n", icp_strerror(rc), icp_last_error(ctx));
-        return 3;
-    }
-    if (icp_write_matrix(out, p, np) != ICP_OK) { // load.cc:68-81
-        std::fprintf(stderr, "[error] cannot write %s\n", out);
-        return 2;
-    }
-    std::fprintf(stderr, "[output] output file \"%s\" was generated.\n", out);
-    icp_ctx_destroy(ctx);
-    std::free(errs);
-    icp_free(m);
-    icp_free(p);
-    icp_free(nrm);
-    icp_free(snrm);
-    return 0;
+    return finish(errs, nullptr);
 }

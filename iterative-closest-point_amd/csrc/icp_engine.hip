@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <climits>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -310,20 +311,26 @@ int level1_kind(const icp_ctx *ctx, size_t n)
     return 0;
 }
 
-GridView grid_view(const icp_ctx *ctx)
+// a built grid as the kernels take it: its geometry, offsets, points and their fp32 image
+static GridView grid_view_of(const GridParams &p, const int *start, const double4 *pts, const float4 *pts32)
 {
     GridView gv{};
-    gv.pts = ctx->g_pts;
-    gv.start = ctx->g_start;
+    gv.pts = pts;
+    gv.start = start;
     for (int a = 0; a < 3; ++a) {
-        gv.g[a] = ctx->grid.g[a];
-        gv.lo[a] = ctx->grid.lo[a];
+        gv.g[a] = p.g[a];
+        gv.lo[a] = p.lo[a];
+        gv.c32[a] = p.c32[a];
     }
-    gv.inv_h = ctx->grid.inv_h;
-    gv.pts32 = ctx->g_pts32;
-    for (int a = 0; a < 3; ++a) gv.c32[a] = ctx->grid.c32[a];
-    gv.em32 = ctx->grid.em32;
+    gv.inv_h = p.inv_h;
+    gv.pts32 = pts32;
+    gv.em32 = p.em32;
     return gv;
+}
+
+GridView grid_view(const icp_ctx *ctx)
+{
+    return grid_view_of(ctx->grid, ctx->g_start, ctx->g_pts, ctx->g_pts32);
 }
 
 // Cells a query box may span before the query goes to the brute-force levels.  A box costs
@@ -332,10 +339,16 @@ GridView grid_view(const icp_ctx *ctx)
 // fallback nm.  Measured (profiles/r01dr/, cells): horse (48,485 points, 25,840 cells) 1,024 ->
 // 6,060 -> 12,000 took the grid variant 3,700 -> 4,277 -> 5,003 it/s and the default 5,560 ->
 // 5,977 -> 6,012, with no gain beyond; bunny likewise.  ICP_GRID_BUDGET overrides.
-int grid_budget(const icp_ctx *ctx)
+// (n: the points the grid holds.)
+static int grid_budget_for(size_t n)
 {
     if (run_knobs().grid_budget) return run_knobs().grid_budget;
-    return (int)std::min<size_t>(std::max<size_t>(kGridBudget, ctx->nm / 4), (size_t)1 << 16);
+    return (int)std::min<size_t>(std::max<size_t>(kGridBudget, n / 4), (size_t)1 << 16);
+}
+
+int grid_budget(const icp_ctx *ctx)
+{
+    return grid_budget_for(ctx->nm);
 }
 
 // The bundle filter's processing order of the n queries in q (a Morton order over the model's
@@ -1432,9 +1445,36 @@ int icp_set_metric(icp_ctx *ctx, int metric)
     return ICP_OK;
 }
 
-// the normals' double4 rows from their interleaved array in device memory
-static int set_normals_from(icp_ctx *ctx, const double *aos_dev, size_t nm)
+// What icp_set_{model,scene}_normals[_device] share: the checks (who: the host function's name, which
+// its _device form reports under too; word: the cloud's; present, count: the cloud's) and, of a host
+// array, the finite check and the upload to the stage.  *aos_dev: the interleaved array in device memory.
+static int normals_upload(icp_ctx *ctx, const std::string &who, const std::string &word, bool present, size_t count,
+                          const double *n_xyz, size_t n, bool host, const double **aos_dev)
 {
+    if (!present) return fail(ctx, ICP_E_NO_MODEL, who + ": no " + word + " (icp_set_" + word + ")");
+    if (n != count)
+        return fail(ctx, ICP_E_SIZE_MISMATCH, who + ": " + std::to_string(n) + " normals for a " + word + " of " +
+                                                  std::to_string(count) + " points");
+    HIPCHK(hipSetDevice(ctx->device));
+    *aos_dev = n_xyz;
+    if (!host) {
+        HIPCHK(hipDeviceSynchronize()); // (as icp_set_model_device / icp_set_scene_device: after the work of any stream)
+        return ICP_OK;
+    }
+    for (size_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(n_xyz[k])) return fail(ctx, ICP_E_ARG, who + ": normal " + std::to_string(k / 3) + " is not finite");
+    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
+    *aos_dev = ctx->stage;
+    return ICP_OK;
+}
+
+// the model's normals as double4 rows, from its interleaved array (host or device memory)
+static int set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm, bool host)
+{
+    if (!ctx || !n_xyz) return ICP_E_ARG;
+    const double *aos_dev = nullptr;
+    TRY(normals_upload(ctx, "icp_set_model_normals", "model", ctx->has_model, ctx->nm, n_xyz, nm, host, &aos_dev));
     TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, nm));
     launch_plane_normals4(aos_dev, (int)nm, ctx->n4, ctx->st);
     LAUNCHCHK("plane_normals4");
@@ -1443,55 +1483,41 @@ static int set_normals_from(icp_ctx *ctx, const double *aos_dev, size_t nm)
     return ICP_OK;
 }
 
-static int normals_args(icp_ctx *ctx, const double *n_xyz, size_t nm)
-{
-    if (!ctx || !n_xyz) return ICP_E_ARG;
-    if (!ctx->has_model) return fail(ctx, ICP_E_NO_MODEL, "icp_set_model_normals: no model (icp_set_model)");
-    if (nm != ctx->nm)
-        return fail(ctx, ICP_E_SIZE_MISMATCH, "icp_set_model_normals: " + std::to_string(nm) + " normals for a model of " +
-                                                  std::to_string(ctx->nm) + " points");
-    HIPCHK(hipSetDevice(ctx->device));
-    return ICP_OK;
-}
-
-int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm)
-{
-    TRY(normals_args(ctx, n_xyz, nm));
-    for (size_t k = 0; k < 3 * nm; ++k)
-        if (!std::isfinite(n_xyz[k]))
-            return fail(ctx, ICP_E_ARG, "icp_set_model_normals: normal " + std::to_string(k / 3) + " is not finite");
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * nm));
-    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * nm, hipMemcpyHostToDevice, ctx->st));
-    return set_normals_from(ctx, ctx->stage, nm);
-}
+int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm) { return set_model_normals(ctx, n_xyz, nm, true); }
 
 int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm)
 {
-    TRY(normals_args(ctx, n_xyz_dev, nm));
-    HIPCHK(hipDeviceSynchronize()); // (as icp_set_model_device: after the work of any stream)
-    return set_normals_from(ctx, n_xyz_dev, nm);
+    return set_model_normals(ctx, n_xyz_dev, nm, false);
 }
 
-// the checks icp_model_knn and icp_estimate_model_normals share; nothing has run when they fail
-static int knn_args(icp_ctx *ctx, int k, const char *who)
+// the checks of a k-NN call over a cloud (word, present, count: the model or the scene) and of an
+// estimator's viewpoint (nullable); nothing has run when they fail
+static int knn_args(icp_ctx *ctx, const std::string &who, const std::string &word, bool present, size_t count, int k,
+                    const double *viewpoint)
 {
-    if (!ctx->has_model || !ctx->g_start || !ctx->g_pts || !ctx->m4)
-        return fail(ctx, ICP_E_NO_MODEL, std::string(who) + ": no model (icp_set_model)");
+    if (!present) return fail(ctx, ICP_E_NO_MODEL, who + ": no " + word + " (icp_set_" + word + ")");
     if (k < kKnnMinK || k > kKnnMaxK)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " is outside [" +
-                                        std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
-    if ((size_t)k > ctx->nm)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " exceeds the model's " +
-                                        std::to_string(ctx->nm) + " points");
+        return fail(ctx, ICP_E_ARG, who + ": k = " + std::to_string(k) + " is outside [" + std::to_string(kKnnMinK) + ", " +
+                                        std::to_string(kKnnMaxK) + "]");
+    if ((size_t)k > count)
+        return fail(ctx, ICP_E_ARG, who + ": k = " + std::to_string(k) + " exceeds the " + word + "'s " +
+                                        std::to_string(count) + " points");
+    if (viewpoint)
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(viewpoint[a]))
+                return fail(ctx, ICP_E_ARG, who + ": viewpoint[" + std::to_string(a) + "] = " + std::to_string(viewpoint[a]) +
+                                                " is not finite");
     HIPCHK(hipSetDevice(ctx->device));
     return ICP_OK;
 }
+
+static bool model_gridded(const icp_ctx *ctx) { return ctx->has_model && ctx->g_start && ctx->g_pts && ctx->m4; }
 
 int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2)
 {
     if (!ctx) return ICP_E_ARG;
     if (!idx) return fail(ctx, ICP_E_ARG, "icp_model_knn: idx is null");
-    TRY(knn_args(ctx, k, "icp_model_knn"));
+    TRY(knn_args(ctx, "icp_model_knn", "model", model_gridded(ctx), ctx->nm, k, nullptr));
     const size_t cnt = ctx->nm * (size_t)k;
     TRY(grow(ctx, &ctx->knn_idx, &ctx->knn_idx_cap, cnt));
     if (d2) TRY(grow(ctx, &ctx->knn_d2, &ctx->knn_d2_cap, cnt));
@@ -1504,32 +1530,39 @@ int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2)
     return ICP_OK;
 }
 
-int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
+// What both estimators run on a grid gv over the n rows: the counters zeroed, the k-NN + PCA kernel
+// (the rows' normals into out), then() (what the caller enqueues behind it), the counters read back:
+// *degenerate and, with ICP_NORMALS_DEBUG set, the search's counts of this call to stderr
+// (tools/normals_probe.py).  label: "model" or "scene".
+static int estimate_normals(icp_ctx *ctx, const GridView &gv, const double4 *rows, size_t n, int k, int budget,
+                            const double *viewpoint, double4 *out, const std::string &label, long long *degenerate,
+                            const std::function<int()> &then)
 {
-    if (!ctx) return ICP_E_ARG;
-    TRY(knn_args(ctx, k, "icp_estimate_model_normals"));
-    if (viewpoint)
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(viewpoint[a]))
-                return fail(ctx, ICP_E_ARG, "icp_estimate_model_normals: viewpoint[" + std::to_string(a) + "] = " +
-                                                std::to_string(viewpoint[a]) + " is not finite");
-    // ICP_NORMALS_DEBUG (set): the search's counts of this call, to stderr (tools/normals_probe.py)
     static const bool debug = getenv("ICP_NORMALS_DEBUG") != nullptr;
-    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, ctx->nm));
     TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
-    ctx->has_normals = false; // (until the new ones are complete)
     HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
-    launch_model_normals(grid_view(ctx), ctx->m4, (int)ctx->nm, k, grid_budget(ctx), viewpoint, ctx->n4, ctx->knn_counters,
-                         debug, ctx->st);
-    LAUNCHCHK("model_normals");
+    launch_model_normals(gv, rows, (int)n, k, budget, viewpoint, out, ctx->knn_counters, debug, ctx->st);
+    LAUNCHCHK(label + "_normals");
+    TRY(then());
     unsigned long long c[kKnnCounters];
     HIPCHK(hipMemcpyAsync(c, ctx->knn_counters, sizeof(c), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
-    ctx->has_normals = true;
     if (degenerate) *degenerate = (long long)c[0];
     if (debug)
-        std::fprintf(stderr, "[normals] nm=%zu k=%d degenerate=%llu second_scans=%llu full_scans=%llu candidates=%llu\n",
-                     ctx->nm, k, c[0], c[1], c[2], c[3]);
+        std::fprintf(stderr, "[normals] %s=%zu k=%d degenerate=%llu second_scans=%llu full_scans=%llu candidates=%llu\n",
+                     label == "model" ? "nm" : "scene n", n, k, c[0], c[1], c[2], c[3]);
+    return ICP_OK;
+}
+
+int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
+{
+    if (!ctx) return ICP_E_ARG;
+    TRY(knn_args(ctx, "icp_estimate_model_normals", "model", model_gridded(ctx), ctx->nm, k, viewpoint));
+    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, ctx->nm));
+    ctx->has_normals = false; // (until the new ones are complete)
+    TRY(estimate_normals(ctx, grid_view(ctx), ctx->m4, ctx->nm, k, grid_budget(ctx), viewpoint, ctx->n4, "model", degenerate,
+                         [] { return (int)ICP_OK; }));
+    ctx->has_normals = true;
     return ICP_OK;
 }
 
@@ -1568,6 +1601,16 @@ static bool kd_host()
     return on;
 }
 
+// launch_model_stats' scratch, its 16 outputs and their host copy, at the first use
+static int ensure_model_stats(icp_ctx *ctx)
+{
+    if (ctx->mstat_part) return ICP_OK;
+    HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
+    HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
+    HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
+    return ICP_OK;
+}
+
 // icp_set_model from the staged AoS copy: every image of the model is built on the device
 // (icp_model.hip); the host reads back 13 doubles and, for models that fit the one-launch
 // loops (<= 64k points), builds their Morton image.  Nothing of the context changes before the
@@ -1581,11 +1624,7 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
                             bool stream_ordered = false)
 {
     const double *aos = aos_dev ? aos_dev : ctx->stage;
-    if (!ctx->mstat_part) {
-        HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
-        HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
-        HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
-    }
+    TRY(ensure_model_stats(ctx));
     // 1. sum, box, finiteness; the centring point c = the model's centroid (any c is valid for
     // the certificate; the centroid keeps |coordinates| and hence the fp32 error bound small)
     launch_model_stats(aos, (int)nm, ctx->mstat_part, ctx->mstat_out, ctx->st);
@@ -1953,20 +1992,12 @@ int icp_set_plane_symmetric(icp_ctx *ctx, int on)
     return ICP_OK;
 }
 
-static int scene_normals_args(icp_ctx *ctx, const double *n_xyz, size_t np_local)
+// u0 (the caller's order) from the scene's interleaved normals (host or device memory)
+static int set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t n, bool host)
 {
     if (!ctx || !n_xyz) return ICP_E_ARG;
-    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, "icp_set_scene_normals: no scene (icp_set_scene)");
-    if (np_local != ctx->scene.n)
-        return fail(ctx, ICP_E_SIZE_MISMATCH, "icp_set_scene_normals: " + std::to_string(np_local) +
-                                                  " normals for a scene of " + std::to_string(ctx->scene.n) + " points");
-    HIPCHK(hipSetDevice(ctx->device));
-    return ICP_OK;
-}
-
-// u0 (the caller's order) from the interleaved array in device memory
-static int set_scene_normals_from(icp_ctx *ctx, const double *aos_dev, size_t n)
-{
+    const double *aos_dev = nullptr;
+    TRY(normals_upload(ctx, "icp_set_scene_normals", "scene", ctx->has_scene, ctx->scene.n, n_xyz, n, host, &aos_dev));
     ctx->has_scene_normals = false; // (until the new ones are complete)
     ctx->sn_slot_valid = false;
     TRY(grow_cloud(ctx, ctx->sn, n, false));
@@ -1979,20 +2010,12 @@ static int set_scene_normals_from(icp_ctx *ctx, const double *aos_dev, size_t n)
 
 int icp_set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t np_local)
 {
-    TRY(scene_normals_args(ctx, n_xyz, np_local));
-    for (size_t k = 0; k < 3 * np_local; ++k)
-        if (!std::isfinite(n_xyz[k]))
-            return fail(ctx, ICP_E_ARG, "icp_set_scene_normals: normal " + std::to_string(k / 3) + " is not finite");
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * np_local));
-    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * np_local, hipMemcpyHostToDevice, ctx->st));
-    return set_scene_normals_from(ctx, ctx->stage, np_local);
+    return set_scene_normals(ctx, n_xyz, np_local, true);
 }
 
 int icp_set_scene_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t np_local)
 {
-    TRY(scene_normals_args(ctx, n_xyz_dev, np_local));
-    HIPCHK(hipDeviceSynchronize()); // (as icp_set_scene_device: after the work of any stream)
-    return set_scene_normals_from(ctx, n_xyz_dev, np_local);
+    return set_scene_normals(ctx, n_xyz_dev, np_local, false);
 }
 
 int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
@@ -2017,28 +2040,15 @@ int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
 int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
 {
     if (!ctx) return ICP_E_ARG;
-    const char *who = "icp_estimate_scene_normals";
-    if (!ctx->has_scene) return fail(ctx, ICP_E_NO_MODEL, std::string(who) + ": no scene (icp_set_scene)");
+    const std::string who = "icp_estimate_scene_normals";
     const size_t n = ctx->scene.n;
-    if (n != ctx->np_total)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": the scene is sharded (" + std::to_string(n) + " of " +
+    // (these two refusals come before the checks on k; with no scene knn_args' first check answers)
+    if (ctx->has_scene && n != ctx->np_total)
+        return fail(ctx, ICP_E_ARG, who + ": the scene is sharded (" + std::to_string(n) + " of " +
                                         std::to_string(ctx->np_total) + " points on this rank)");
-    if (!ctx->scene_pristine)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": an icp_run or icp_transform_scene has moved the scene since "
-                                                       "icp_set_scene");
-    if (k < kKnnMinK || k > kKnnMaxK)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " is outside [" +
-                                        std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
-    if ((size_t)k > n)
-        return fail(ctx, ICP_E_ARG, std::string(who) + ": k = " + std::to_string(k) + " exceeds the scene's " +
-                                        std::to_string(n) + " points");
-    if (viewpoint)
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(viewpoint[a]))
-                return fail(ctx, ICP_E_ARG, std::string(who) + ": viewpoint[" + std::to_string(a) + "] = " +
-                                                std::to_string(viewpoint[a]) + " is not finite");
-    HIPCHK(hipSetDevice(ctx->device));
-    static const bool debug = getenv("ICP_NORMALS_DEBUG") != nullptr;
+    if (ctx->has_scene && !ctx->scene_pristine)
+        return fail(ctx, ICP_E_ARG, who + ": an icp_run or icp_transform_scene has moved the scene since icp_set_scene");
+    TRY(knn_args(ctx, who, "scene", ctx->has_scene, n, k, viewpoint));
     // the scene in the caller's order (a copy when it is resident in slot order), its interleaved
     // copy for the box, its double4 rows: what icp_set_model makes of a model's upload
     const DevCloud *P = &ctx->scene;
@@ -2049,18 +2059,14 @@ int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, lon
         LAUNCHCHK("scene_to_file_order");
         P = &ctx->s_tmp;
     }
-    if (!ctx->mstat_part) {
-        HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
-        HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
-        HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
-    }
+    TRY(ensure_model_stats(ctx));
     TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
     launch_soa_to_aos(P->x, P->y, P->z, n, ctx->stage, ctx->st);
     launch_model_stats(ctx->stage, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
     LAUNCHCHK("scene_stats");
     HIPCHK(hipMemcpyAsync(ctx->h_mstat, ctx->mstat_out, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
-    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, std::string(who) + ": the scene has non-finite coordinates");
+    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, who + ": the scene has non-finite coordinates");
     const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
     const long long ncell = grid_cells(gp);
     const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
@@ -2083,36 +2089,18 @@ int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, lon
     launch_make_aos4(P->x, P->y, P->z, (int)n, rows, ctx->st);
     if (launch_grid_build(P->x, P->y, P->z, rows, (int)n, gp, tmp.p[4], gbytes, (int *)tmp.p[1], (double4 *)tmp.p[2],
                           (float4 *)tmp.p[3], ctx->st) != 0)
-        return fail(ctx, ICP_E_HIP, std::string(who) + ": grid build: radix sort failed");
+        return fail(ctx, ICP_E_HIP, who + ": grid build: radix sort failed");
     LAUNCHCHK("scene_grid_build");
-    GridView gv{};
-    gv.pts = (const double4 *)tmp.p[2];
-    gv.start = (const int *)tmp.p[1];
-    for (int a = 0; a < 3; ++a) {
-        gv.g[a] = gp.g[a];
-        gv.lo[a] = gp.lo[a];
-        gv.c32[a] = gp.c32[a];
-    }
-    gv.inv_h = gp.inv_h;
-    gv.pts32 = (const float4 *)tmp.p[3];
-    gv.em32 = gp.em32;
-    const int budget = run_knobs().grid_budget
-                           ? run_knobs().grid_budget
-                           : (int)std::min<size_t>(std::max<size_t>(kGridBudget, n / 4), (size_t)1 << 16); // (grid_budget's rule)
-    TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
-    HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
-    launch_model_normals(gv, rows, (int)n, k, budget, viewpoint, nrm, ctx->knn_counters, debug, ctx->st);
-    LAUNCHCHK("scene_normals");
-    ctx->has_scene_normals = false; // (until the new ones are complete)
-    ctx->sn_slot_valid = false;
-    TRY(grow_cloud(ctx, ctx->sn, n, false));
-    launch_rows4_to_soa(nrm, (int)n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
-    LAUNCHCHK("scene_normals_rows");
-    unsigned long long c[kKnnCounters];
-    HIPCHK(hipMemcpyAsync(c, ctx->knn_counters, sizeof(c), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
+    const GridView gv = grid_view_of(gp, (const int *)tmp.p[1], (const double4 *)tmp.p[2], (const float4 *)tmp.p[3]);
+    TRY(estimate_normals(ctx, gv, rows, n, k, grid_budget_for(n), viewpoint, nrm, "scene", degenerate, [&] {
+        ctx->has_scene_normals = false; // (until the new ones are complete)
+        ctx->sn_slot_valid = false;
+        TRY(grow_cloud(ctx, ctx->sn, n, false));
+        launch_rows4_to_soa(nrm, (int)n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
+        LAUNCHCHK("scene_normals_rows");
+        return (int)ICP_OK;
+    }));
     ctx->has_scene_normals = true;
-    if (degenerate) *degenerate = (long long)c[0];
     return ICP_OK;
 }
 

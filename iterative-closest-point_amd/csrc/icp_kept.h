@@ -21,7 +21,7 @@
 namespace icp {
 
 // icp_plane.hip's side of launch_kept_moments, launch_kept_step and launch_kept_transform (icp_gated.hip);
-// with KeptPass::symm / KeptStep::symm / symm set, the symmetric form's kernels (icp_set_plane_symmetric)
+// with KeptPass::symm / KeptStep::symm / symm set, the kernels' symmetric instantiations (icp_set_plane_symmetric)
 void plane_moments(const KeptPass &a, bool y_ready);
 void plane_step(const KeptStep &a, const double *partials, int nblocks, bool step);
 void plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,

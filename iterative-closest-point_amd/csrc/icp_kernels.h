@@ -823,7 +823,8 @@ struct GateState {
 // The symmetric form of the point-to-plane iteration (icp_set_plane_symmetric): the scene's normals u0 as
 // given, in the scene's current order, and what the current ones u = Q u0 need -- Q is the rotation of
 // the total since icp_set_scene*: the run's so far (st->tot) composed onto the context's at the run's
-// start (q0 row-major; have_q0 = 0: the identity, not multiplied).  Passed to the kernels by value.
+// start (q0 row-major; have_q0 = 0: the identity, not multiplied).  Passed by value to the symmetric
+// instantiations of the plane metric's moments and transform kernels, which alone take it.
 struct SymmArgs {
     const double *ux, *uy, *uz;
     const IterState *st;
@@ -883,7 +884,8 @@ void launch_kept_step(const KeptStep &a, const double *partials, int nblocks, bo
 void launch_kept_first_shift(IterState *st_dev, const double *sums, int slot, hipStream_t st);
 // p <- sR p + t for every point (p32 nullable); partial [sum over the kept points (the mask) of the
 // metric's squared residual: ||y - p'||^2, or with n4 (the plane metric) ((p' - y) . n)^2, n = n4[idx[i]],
-// or with symm the pair's normal from n4[idx[i]] and the scene's own, turned by the total with this step]
+// or with symm (the same kernel's other instantiation) n = the pair's normal from n4[idx[i]] and the scene's
+// own, turned by the total with this step]
 void launch_kept_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz,
                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
                            const int *idx, const double4 *n4, double *partials, hipStream_t st,

@@ -29,7 +29,8 @@
 //   the half angle's cosine), R = R_h R_h, t = ((R_h (g t~)) + c) - R c, s = 1;
 //   err = (e + e) / K with e = sum over the kept pairs of ((q - y) . n')^2, n' from u' = Q' u0, Q' the
 //   total's rotation with this step composed.
-// Its kernels are their own (symm_*): the one-sided kernels keep their instruction streams.
+// It is a template parameter of the three kernels (the moments and the transform take SymmArgs behind
+// their one-sided arguments): under `if constexpr`, so the one-sided instantiations carry none of it.
 // Compiled with IEEE semantics like icp_gated.hip (`d2 <= D`, `A_kk > 0` and `pivot > 1e-12` must
 // stay false for a NaN).
 #include <hip/hip_runtime.h>
@@ -49,62 +50,6 @@ __global__ __launch_bounds__(kBlock) void plane_normals4_kernel(const double *__
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= nm) return;
     n4[i] = make_double4(aos[3 * i], aos[3 * i + 1], aos[3 * i + 2], 0.0);
-}
-
-// The sums over the kept pairs (kept_pairs_pass: the gate and its mask, as the gated moments): the
-// 21 + 6 of the normal equations and the kept count as the 28th (a double: exact below 2^53).  No
-// shifts: r is a difference of near points, and (p - c) is taken before any product.
-// KIND, a robust weight (icp_set_robust; kk = k, k2): each of the pair's 27 terms enters as
-// a += w * t with w = robust_weight<KIND>(r * r), r the residual along the normal, and W = sum w and
-// K+ = #{w > 0} are the 29th and 30th sums.
-// A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN, int KIND, class... K>
-__global__ __launch_bounds__(kBlock) void plane_moments_kernel(
-    const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
-    const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
-    double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
-    double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, K... kk, const double *__restrict__ cut)
-{
-    constexpr bool kRobust = KIND != kRobustNone;
-    constexpr int WIDTH = kept_width(true, kRobust);
-    if (st->done != 0) return;
-    double a[WIDTH];
-#pragma unroll
-    for (int j = 0; j < WIDTH; ++j) a[j] = 0.0;
-    kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
-        [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
-            __attribute__((always_inline)) {
-                const double4 nn = n4[idx[i]]; // (idx is final here whichever search ran: kpos rides beside it)
-                const double u0 = q0 - c0, u1 = q1 - c1, u2 = q2 - c2;
-                double v[6];
-                v[0] = u1 * nn.z - u2 * nn.y;
-                v[1] = u2 * nn.x - u0 * nn.z;
-                v[2] = u0 * nn.y - u1 * nn.x;
-                v[3] = nn.x;
-                v[4] = nn.y;
-                v[5] = nn.z;
-                const double r = (dx * nn.x + dy * nn.y) + dz * nn.z;
-                double w = 1.0; // (unweighted: not multiplied)
-                if constexpr (kRobust) w = robust_weight<KIND>(r * r, kk...);
-                const auto add = [&](double &sum, double t) __attribute__((always_inline)) {
-                    if constexpr (kRobust) sum += w * t;
-                    else sum += t;
-                };
-#pragma unroll
-                for (int row = 0; row < 6; ++row)
-#pragma unroll
-                    for (int col = row; col < 6; ++col) add(a[6 * row - row * (row - 1) / 2 + (col - row)], v[row] * v[col]);
-#pragma unroll
-                for (int row = 0; row < 6; ++row) add(a[kPlaneB + row], v[row] * r);
-                a[kPlaneCount] += 1.0;
-                if constexpr (kRobust) {
-                    a[kRobustPlaneW] += w;
-                    a[kRobustPlaneKpos] += w > 0.0 ? 1.0 : 0.0;
-                }
-            });
-    block_sum_store<WIDTH>(a, partials + (size_t)blockIdx.x * WIDTH);
 }
 
 // ---- the symmetric form's pairs (icp_set_plane_symmetric) ---------------------------------------
@@ -152,25 +97,49 @@ __device__ __forceinline__ bool symm_normal(const double4 &N, double a0, double 
     return true;
 }
 
-// plane_moments_kernel with the pair's normal and the sum of both lever arms: the same columns in
-// the same order.  Q goes through LDS, read from the loop state by one thread of the workgroup.
-template <bool YIN, int KIND, class... K>
-__global__ __launch_bounds__(kBlock) void symm_moments_kernel(
+// What a moments kernel's trailing arguments ([SymmArgs,] [k, k2]) hold: the symmetric form's, and the
+// pair's weight.
+template <class... K> __device__ __forceinline__ const SymmArgs &symm_of(const SymmArgs &sy, K...) { return sy; }
+template <int KIND> __device__ __forceinline__ double plane_weight(double r2, double k, double k2)
+{
+    return robust_weight<KIND>(r2, k, k2);
+}
+template <int KIND> __device__ __forceinline__ double plane_weight(double r2, const SymmArgs &, double k, double k2)
+{
+    return robust_weight<KIND>(r2, k, k2);
+}
+
+// The sums over the kept pairs (kept_pairs_pass: the gate and its mask, as the gated moments): the
+// 21 + 6 of the normal equations and the kept count as the 28th (a double: exact below 2^53).  No
+// shifts: r is a difference of near points, and (p - c) is taken before any product.
+// KIND, a robust weight (icp_set_robust; k, k2): each of the pair's 27 terms enters as
+// a += w * t with w = robust_weight<KIND>(r * r), r the residual along the normal, and W = sum w and
+// K+ = #{w > 0} are the 29th and 30th sums.
+// SYMM, the symmetric form: the pair's normal (symm_normal) and the sum of both lever arms, the same
+// columns in the same order; Q goes through LDS, read from the loop state by one thread of the
+// workgroup.  A pair without a normal counts in K and adds nothing else.
+// X, what the form and the kind add to the arguments: [SymmArgs,] [k, k2] (an unused one costs the
+// pairs' loop instructions).
+// A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
+template <bool YIN, int KIND, bool SYMM, class... X>
+__global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, SymmArgs sy, K... kk, const double *__restrict__ cut)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, X... xx, const double *__restrict__ cut)
 {
     constexpr bool kRobust = KIND != kRobustNone;
     constexpr int WIDTH = kept_width(true, kRobust);
-    __shared__ double sq[9];
     if (st->done != 0) return;
-    if (threadIdx.x == 0) symm_total_rotation(st, sy, sq);
-    __syncthreads();
-    double Q[9]; // (the same in every lane: kept in scalar registers)
+    [[maybe_unused]] double Q[SYMM ? 9 : 1]; // (the same in every lane: kept in scalar registers)
+    if constexpr (SYMM) {
+        __shared__ double sq[9];
+        if (threadIdx.x == 0) symm_total_rotation(st, symm_of(xx...), sq);
+        __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Q[k] = wave_uniform(sq[k]);
+        for (int k = 0; k < 9; ++k) Q[k] = wave_uniform(sq[k]);
+    }
     double a[WIDTH];
 #pragma unroll
     for (int j = 0; j < WIDTH; ++j) a[j] = 0.0;
@@ -178,16 +147,28 @@ __global__ __launch_bounds__(kBlock) void symm_moments_kernel(
         idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
         [&](long long i, double q0, double q1, double q2, const double4 &y, double dx, double dy, double dz)
             __attribute__((always_inline)) {
-                a[kPlaneCount] += 1.0;
                 double v[6];
-                if (!symm_normal(n4[idx[i]], sy.ux[i], sy.uy[i], sy.uz[i], Q, v[3], v[4], v[5])) return;
-                const double l0 = (q0 - c0) + (y.x - c0), l1 = (q1 - c1) + (y.y - c1), l2 = (q2 - c2) + (y.z - c2);
-                v[0] = l1 * v[5] - l2 * v[4];
-                v[1] = l2 * v[3] - l0 * v[5];
-                v[2] = l0 * v[4] - l1 * v[3];
+                if constexpr (SYMM) {
+                    const SymmArgs &sy = symm_of(xx...);
+                    a[kPlaneCount] += 1.0;
+                    if (!symm_normal(n4[idx[i]], sy.ux[i], sy.uy[i], sy.uz[i], Q, v[3], v[4], v[5])) return;
+                    const double l0 = (q0 - c0) + (y.x - c0), l1 = (q1 - c1) + (y.y - c1), l2 = (q2 - c2) + (y.z - c2);
+                    v[0] = l1 * v[5] - l2 * v[4];
+                    v[1] = l2 * v[3] - l0 * v[5];
+                    v[2] = l0 * v[4] - l1 * v[3];
+                } else {
+                    const double4 nn = n4[idx[i]]; // (idx is final here whichever search ran: kpos rides beside it)
+                    const double u0 = q0 - c0, u1 = q1 - c1, u2 = q2 - c2;
+                    v[0] = u1 * nn.z - u2 * nn.y;
+                    v[1] = u2 * nn.x - u0 * nn.z;
+                    v[2] = u0 * nn.y - u1 * nn.x;
+                    v[3] = nn.x;
+                    v[4] = nn.y;
+                    v[5] = nn.z;
+                }
                 const double r = (dx * v[3] + dy * v[4]) + dz * v[5];
                 double w = 1.0; // (unweighted: not multiplied)
-                if constexpr (kRobust) w = robust_weight<KIND>(r * r, kk...);
+                if constexpr (kRobust) w = plane_weight<KIND>(r * r, xx...);
                 const auto add = [&](double &sum, double t) __attribute__((always_inline)) {
                     if constexpr (kRobust) sum += w * t;
                     else sum += t;
@@ -198,6 +179,7 @@ __global__ __launch_bounds__(kBlock) void symm_moments_kernel(
                     for (int col = row; col < 6; ++col) add(a[6 * row - row * (row - 1) / 2 + (col - row)], v[row] * v[col]);
 #pragma unroll
                 for (int row = 0; row < 6; ++row) add(a[kPlaneB + row], v[row] * r);
+                if constexpr (!SYMM) a[kPlaneCount] += 1.0;
                 if constexpr (kRobust) {
                     a[kRobustPlaneW] += w;
                     a[kRobustPlaneKpos] += w > 0.0 ? 1.0 : 0.0;
@@ -385,60 +367,46 @@ __device__ __forceinline__ void plane_solve_body(
 
 // (The step is an inlined function under the kernel, not the kernel's own body: written straight
 // into the kernel the same text compiles to another instruction stream.)
-template <bool ROBUST>
+template <bool ROBUST, bool SYMM>
 __global__ __launch_bounds__(kBlock) void plane_solve_kernel(
     const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
     int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
     IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
 {
-    plane_solve_body<ROBUST>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace, h_ptrace, trim_few);
+    plane_solve_body<ROBUST, SYMM>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace, h_ptrace,
+                                   trim_few);
 }
 
 // Every point moves, and the squared residual along the normal, gathered again through idx, is
-// summed over the kept points (kept_transform).
+// summed over the kept points (kept_transform).  S, the symmetric form's SymmArgs or nothing: with it
+// the pair's normal is formed again from Q', the total's rotation with the step just composed (the
+// step kernel ran before this one; a frozen run returns before Q' is used).
+template <class... S>
 __global__ __launch_bounds__(kBlock) void plane_transform_kernel(
     double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, const double *__restrict__ yx,
     const double *__restrict__ yy, const double *__restrict__ yz, int n, const Xform *__restrict__ xfd,
     const int *__restrict__ done, float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
-    const int *__restrict__ idx, const double4 *__restrict__ n4, double *__restrict__ partials)
+    const int *__restrict__ idx, const double4 *__restrict__ n4, double *__restrict__ partials, S... sy)
 {
-    kept_transform(px, py, pz, n, xfd, done, p32, mask, partials,
-                   [&](long long i, double q0, double q1, double q2) __attribute__((always_inline)) {
-                       const double4 nn = n4[idx[i]];
-                       const double e0 = q0 - yx[i], e1 = q1 - yy[i], e2 = q2 - yz[i];
-                       const double rn = (e0 * nn.x + e1 * nn.y) + e2 * nn.z;
-                       return rn * rn;
-                   });
-}
-
-template <bool ROBUST>
-__global__ __launch_bounds__(kBlock) void symm_solve_kernel(
-    const double *__restrict__ partials, int nblocks, double *__restrict__ sums, int step, double c0, double c1, double c2,
-    int *__restrict__ cnt, IterState *__restrict__ s, GateState *__restrict__ g, GateState *__restrict__ h_g,
-    IterState *__restrict__ h_state, double *__restrict__ h_wtrace, long long *__restrict__ h_ptrace, int trim_few)
-{
-    plane_solve_body<ROBUST, true>(partials, nblocks, sums, step, c0, c1, c2, cnt, s, g, h_g, h_state, h_wtrace, h_ptrace,
-                                   trim_few);
-}
-
-// plane_transform_kernel with the pair's normal formed again from Q', the total's rotation with the
-// step just composed (the step kernel ran before this one; a frozen run returns before Q' is used).
-__global__ __launch_bounds__(kBlock) void symm_transform_kernel(
-    double *__restrict__ px, double *__restrict__ py, double *__restrict__ pz, const double *__restrict__ yx,
-    const double *__restrict__ yy, const double *__restrict__ yz, int n, const Xform *__restrict__ xfd,
-    const int *__restrict__ done, float4 *__restrict__ p32, const unsigned long long *__restrict__ mask,
-    const int *__restrict__ idx, const double4 *__restrict__ n4, double *__restrict__ partials, SymmArgs sy)
-{
-    __shared__ double sq[9];
-    if (threadIdx.x == 0) symm_total_rotation(sy.st, sy, sq);
-    __syncthreads();
-    double Q[9]; // (the same in every lane: kept in scalar registers)
+    constexpr bool SYMM = sizeof...(S) != 0;
+    [[maybe_unused]] double Q[SYMM ? 9 : 1]; // (the same in every lane: kept in scalar registers)
+    if constexpr (SYMM) {
+        __shared__ double sq[9];
+        if (threadIdx.x == 0) symm_total_rotation(symm_of(sy...).st, symm_of(sy...), sq);
+        __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Q[k] = wave_uniform(sq[k]);
+        for (int k = 0; k < 9; ++k) Q[k] = wave_uniform(sq[k]);
+    }
     kept_transform(px, py, pz, n, xfd, done, p32, mask, partials,
                    [&](long long i, double q0, double q1, double q2) __attribute__((always_inline)) {
                        double n0, n1, n2;
-                       symm_normal(n4[idx[i]], sy.ux[i], sy.uy[i], sy.uz[i], Q, n0, n1, n2);
+                       if constexpr (SYMM) {
+                           const SymmArgs &u = symm_of(sy...);
+                           symm_normal(n4[idx[i]], u.ux[i], u.uy[i], u.uz[i], Q, n0, n1, n2);
+                       } else {
+                           const double4 nn = n4[idx[i]];
+                           n0 = nn.x, n1 = nn.y, n2 = nn.z;
+                       }
                        const double e0 = q0 - yx[i], e1 = q1 - yy[i], e2 = q2 - yz[i];
                        const double rn = (e0 * n0 + e1 * n1) + e2 * n2;
                        return rn * rn;
@@ -473,48 +441,42 @@ void launch_plane_normals4(const double *aos, int nm, double4 *n4, hipStream_t s
 
 void plane_moments(const KeptPass &a, bool y_ready)
 {
-    if (a.symm) {
-        kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
-            const auto go = [&](auto... kk) {
-                symm_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
-                    a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
-                    a.partials, a.kpos, a.m4kd, *a.symm, kk..., a.cut);
-            };
-            if constexpr (kind() == kRobustNone) go();
-            else go(a.k, a.k2);
-        });
-        return;
-    }
     kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
-        const auto go = [&](auto... kk) {
-            plane_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
+        // the kernel of (yin, kind, the form) with what these add to its arguments: [SymmArgs,] [k, k2]
+        const auto go = [&](auto symm, auto... xx) {
+            plane_moments_kernel<yin(), kind(), symm(), decltype(xx)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
                 a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
-                a.partials, a.kpos, a.m4kd, kk..., a.cut);
+                a.partials, a.kpos, a.m4kd, xx..., a.cut);
         };
-        if constexpr (kind() == kRobustNone) go();
-        else go(a.k, a.k2);
+        const auto of_form = [&](auto... kk) {
+            if (a.symm) go(std::true_type(), *a.symm, kk...);
+            else go(std::false_type(), kk...);
+        };
+        if constexpr (kind() == kRobustNone) of_form();
+        else of_form(a.k, a.k2);
     });
 }
 
 void plane_step(const KeptStep &a, const double *partials, int nblocks, bool step)
 {
-    const auto kernel = a.symm ? (a.robust ? symm_solve_kernel<true> : symm_solve_kernel<false>)
-                               : (a.robust ? plane_solve_kernel<true> : plane_solve_kernel<false>);
-    kernel<<<1, kBlock, 0, a.st>>>(partials, nblocks, a.sums, step ? 1 : 0, a.c[0], a.c[1], a.c[2], a.amb_count, a.st_dev,
-                                   a.gate, a.h_gate, a.h_state, a.h_wtrace, a.h_ptrace, a.trim_few ? 1 : 0);
+    static constexpr decltype(&plane_solve_kernel<false, false>) kernels[2][2] = {
+        {plane_solve_kernel<false, false>, plane_solve_kernel<false, true>},
+        {plane_solve_kernel<true, false>, plane_solve_kernel<true, true>}};
+    kernels[a.robust][a.symm]<<<1, kBlock, 0, a.st>>>(partials, nblocks, a.sums, step ? 1 : 0, a.c[0], a.c[1], a.c[2],
+                                                      a.amb_count, a.st_dev, a.gate, a.h_gate, a.h_state, a.h_wtrace,
+                                                      a.h_ptrace, a.trim_few ? 1 : 0);
 }
 
 void plane_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,
                      const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask, const int *idx,
                      const double4 *n4, double *partials, hipStream_t st, const SymmArgs *symm)
 {
-    if (symm) {
-        symm_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4,
-                                                                partials, *symm);
-        return;
-    }
-    plane_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4,
-                                                             partials);
+    const auto go = [&](auto... sy) {
+        plane_transform_kernel<<<red_blocks(n), kBlock, 0, st>>>(px, py, pz, yx, yy, yz, n, xf, done, p32, mask, idx, n4,
+                                                                 partials, sy...);
+    };
+    if (symm) go(*symm);
+    else go();
 }
 
 } // namespace icp

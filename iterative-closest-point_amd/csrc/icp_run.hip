@@ -693,8 +693,8 @@ template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int m
 // moments pass then runs in its streamed form with the cut's address.  With ranks each pass's bins are all-reduced before its pick (kSelectPasses more all-reduces an
 // iteration).  T below the metric's least count stops the run as K below it does.  A trimmed run
 // counts as a gated one for icp_get_inliers, and leaves icp_get_trim_trace its C trace.
-// With icp_set_plane_symmetric the plane metric's three launches are their symmetric kernels
-// (icp_plane.hip: symm_*), which also read the scene's normals u0 in the scene's current order and the
+// With icp_set_plane_symmetric the plane metric's three launches are their symmetric instantiations
+// (icp_plane.hip: SYMM), which also read the scene's normals u0 in the scene's current order and the
 // total since icp_set_scene* (SymmArgs: the context's at the run's start, the run's own from the loop
 // state); everything else of the loop, the sums' width and the all-reduces included, is the plane metric's.
 int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Everything the kept-pairs loop (icp_run under icp_set_max_distance, icp_set_metric, icp_set_robust
-and / or icp_set_trim) computes on the cases of tests/test_gpu_gated.py and tests/test_gpu_plane.py
-and on every combination of its options at one small size (matrix()), dumped for a
+"""Everything the kept-pairs loop (icp_run under icp_set_max_distance, icp_set_metric, icp_set_robust,
+icp_set_trim and / or icp_set_plane_symmetric) computes on the cases of tests/test_gpu_gated.py,
+tests/test_gpu_plane.py and tests/test_gpu_symm.py and on every combination of its options at one
+small size (matrix()), and what the normals' estimators and icp_model_knn return (normals()), dumped for a
 bit-for-bit comparison of two libraries (ICP_AMD_LIB picks the library; tools/build_ab.sh builds
 another revision's):
 
@@ -11,7 +12,8 @@ another revision's):
 
 One process.  Per run: the return code and message, errs, the scene, s / R / t, the iterations, with
 a gate the K trace, the mask and k, with weights the W and K+ traces, with a trim the C trace, and
-the integer counters of stats() (run_path_bits, the searches' queue counts).
+the integer counters of stats() (run_path_bits, the searches' queue counts), and the scene's current
+normals where the context has them.
 """
 import argparse
 import os
@@ -26,7 +28,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import icp_amd as amd  # noqa: E402
 import datasets  # noqa: E402
 import gated_ref as G  # noqa: E402
+import normals_ref as NR  # noqa: E402
 import plane_ref as P  # noqa: E402
+import symm_ref as S  # noqa: E402
 from test_gpu_gated import HostAllReduce  # noqa: E402
 
 OUT = {}
@@ -43,6 +47,10 @@ def record(tag, ctx, iters, threshold=-1.0):
     OUT[tag + "/rc"] = np.array(rc)
     OUT[tag + "/msg"] = np.array(msg)
     OUT[tag + "/scene"] = ctx.get_scene()
+    try:
+        OUT[tag + "/scene_normals"] = ctx.scene_normals()
+    except amd.ICPError:  # (the context has none)
+        pass
     if res is not None:
         OUT[tag + "/errs"] = errs
         OUT[tag + "/srt"] = np.array([res.s] + list(res.R) + list(res.t))
@@ -75,7 +83,20 @@ def options(ctx, dmax, robust, trim):
         ctx.set_trim(trim)
 
 
-def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, robust=None, trim=None, **ctx_args):
+def symmetric(ctx, snrm):
+    """snrm: the scene's normals, or None: the one-sided form"""
+    if snrm is not None:
+        ctx.set_scene_normals(snrm)
+        ctx.set_plane_symmetric(True)
+
+
+def unit_rows(n, seed):
+    v = np.random.default_rng(seed).standard_normal((n, 3))
+    return v / np.linalg.norm(v, axis=1)[:, None]
+
+
+def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, robust=None, trim=None, snrm=None,
+          **ctx_args):
     with amd.Context(0, mode, **ctx_args) as ctx:
         if variant is not None:
             ctx.set_nn_variant(variant)
@@ -84,11 +105,12 @@ def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None
             ctx.set_model_normals(nrm)
             ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
         ctx.set_scene(p)
+        symmetric(ctx, snrm)
         options(ctx, dmax, robust, trim)
         record(tag, ctx, iters, threshold)
 
 
-def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None, trim=None):
+def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None, trim=None, snrm=None):
     red = HostAllReduce(world)
     errors = []
 
@@ -101,6 +123,7 @@ def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None
                     ctx.set_model_normals(nrm)
                     ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
                 ctx.set_scene(p[b:b + c], np_total=p.shape[0])
+                symmetric(ctx, None if snrm is None else snrm[b:b + c])
                 options(ctx, dmax, robust, trim)
                 record(f"{tag}/rank{r}", ctx, iters, threshold)
         except Exception as e:
@@ -132,16 +155,19 @@ KINDS = (("none", amd.ROBUST_NONE), ("huber", amd.ROBUST_HUBER), ("tukey", amd.R
 
 def matrix(clump):
     """Every cell of metric x weights x trim x gate at n = 193 (three full waves and a partial fourth: the
-    last mask word and the last ballot are partial) on one rank, and without and with Tukey weights on
+    last mask word and the last ballot are partial; "symm": the plane metric's symmetric form on seeded
+    unit normals for the scene) on one rank, and without and with Tukey weights on
     two (the fold-only pass, the all-reduce at each row width, the step on all-reduced sums); the cow
     clump with Tukey weights and a trim to convergence; the stops through the weighted and trimmed paths."""
     m, nrm, p = P.gate_case(MATRIX_N)
-    for metric in ("point", "plane"):
+    snrm = unit_rows(MATRIX_N, 7)
+    for metric in ("point", "plane", "symm"):
         for kname, kind in KINDS:
             for trim in (None, MATRIX_F):
                 for dmax in (0.0, MATRIX_DMAX):
                     cell = f"{metric}_{kname}_trim{trim or 'off'}_gate{dmax or 'off'}"
-                    args = dict(nrm=nrm if metric == "plane" else None, robust=(kind, MATRIX_K) if kind else None, trim=trim)
+                    args = dict(nrm=None if metric == "point" else nrm, robust=(kind, MATRIX_K) if kind else None, trim=trim,
+                                snrm=snrm if metric == "symm" else None)
                     fresh(f"matrix/{cell}", m, p, dmax, MATRIX_ITERS, **args)
                     if kname in ("none", "tukey"):
                         sharded(f"matrix/world2/{cell}", m, p, dmax, 2, MATRIX_ITERS, **args)
@@ -202,16 +228,25 @@ def dump():
     fresh("plane/too_few", m, p, 0.0, 5, nrm=nrm)
     m, nrm, p = P.planar()
     fresh("plane/degenerate", m, p, 0.0, 5, nrm=nrm)
+    # the symmetric form's stops (the normals after a frozen iteration are in the dump: unmoved)
+    m, nrm, p, snrm = S.five()
+    fresh("symm/too_few", m, p, 0.0, 5, nrm=nrm, snrm=snrm)
+    m, nrm, p, snrm = S.planar()
+    fresh("symm/degenerate", m, p, 0.0, 5, nrm=nrm, snrm=snrm)
     # a scene in slot order, each metric
     m, p, nrm = slot_scene()
-    for name in ("gated", "plane"):
+    for name in ("gated", "plane", "symm"):
         with amd.Context() as ctx:
             ctx.set_model(m)
             ctx.set_model_normals(nrm)
             ctx.set_scene(p)
+            if name == "symm":
+                ctx.set_scene_normals(unit_rows(p.shape[0], 6))
             record(f"{name}/slot/before", ctx, 2)
-            if name == "plane":
+            if name != "gated":
                 ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+            if name == "symm":
+                ctx.set_plane_symmetric(True)
             ctx.set_max_distance(0.05)
             record(f"{name}/slot/run", ctx, 3)
     # one context: gated point-to-point, ungated plane, gated plane, a new scene
@@ -230,6 +265,19 @@ def dump():
         ctx.set_max_distance(0.0)
         ctx.set_metric(amd.METRIC_POINT_TO_POINT)
         record("sequence/4_new_scene_point", ctx, 3)
+    # symmetric iterations, a pose from outside, more of them: the run's total composed onto the context's
+    with amd.Context() as ctx:
+        ctx.set_model(gm)
+        ctx.set_model_normals(gn)
+        ctx.set_scene(gp)
+        ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
+        symmetric(ctx, unit_rows(gp.shape[0], 8))
+        ctx.set_max_distance(0.08)
+        record("symm_sequence/1_run", ctx, 2)
+        ctx.transform_scene(1.0, P.rot((3, -1, 2), 2.0).reshape(-1), [0.01, -0.02, 0.005])
+        OUT["symm_sequence/posed/scene"] = ctx.get_scene()
+        OUT["symm_sequence/posed/scene_normals"] = ctx.scene_normals()
+        record("symm_sequence/2_run", ctx, 2)
     # a point-to-point run after a plane run
     with amd.Context() as ctx:
         ctx.set_model(cow[0])
@@ -240,6 +288,23 @@ def dump():
         record("after_plane/plane", ctx, 3)
         ctx.set_metric(amd.METRIC_POINT_TO_POINT)
         record("after_plane/point", ctx, 5)
+
+
+def normals():
+    """What the estimators and the k-NN return at 257 points and on tests/test_gpu_normals.py's duplicates
+    (k = 16): the model's normals, the same cloud's as a scene, the neighbours and their distances, and
+    the counts of undetermined points."""
+    for name, cloud in (("257", P.ellipsoid(257, 357)[0]), ("duplicates", NR.duplicates())):
+        with amd.Context() as ctx:
+            ctx.set_model(cloud)
+            OUT[f"normals/{name}/model_degenerate"] = np.array(ctx.estimate_model_normals(16))
+            OUT[f"normals/{name}/model_normals"] = ctx.model_normals()
+            ctx.set_scene(cloud)
+            OUT[f"normals/{name}/scene_degenerate"] = np.array(ctx.estimate_scene_normals(16))
+            OUT[f"normals/{name}/scene_normals"] = ctx.scene_normals()
+            idx, d2 = ctx.model_knn(16, distances=True)
+            OUT[f"normals/{name}/knn_idx"] = idx
+            OUT[f"normals/{name}/knn_d2"] = d2
 
 
 def compare(a_path, b_path):
@@ -271,6 +336,7 @@ def main():
     if not a.out:
         ap.error("--out FILE.npz or --compare A.npz B.npz")
     dump()
+    normals()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez(a.out, **OUT)
     print(f"{len(OUT)} arrays of {len({k.rsplit('/', 1)[0] for k in OUT})} runs -> {a.out} ({amd.LIB_PATH})")

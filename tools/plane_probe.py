@@ -24,8 +24,8 @@ import icp_amd as amd  # noqa: E402
 BYTES = {
     "gated_moments_kernel": 24 + 4 + 32 + 24,             # p, idx, y gather, y store
     "gated_transform_kernel": 24 + 24 + 24,               # p, y, p store
-    "plane_moments_kernel": 24 + 4 + 32 + 24 + 32,        # ... + the normal's gather
-    "plane_transform_kernel": 24 + 24 + 4 + 32 + 24,      # p, y, idx, normal gather, p store
+    "plane_moments_kernel<*, *, false>": 24 + 4 + 32 + 24 + 32,  # ... + the normal's gather
+    "plane_transform_kernel<>": 24 + 24 + 4 + 32 + 24,    # p, y, idx, normal gather, p store
 }
 
 

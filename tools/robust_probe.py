@@ -9,7 +9,7 @@ nothing reaches (dmax = 1e6), so every loop runs the same searches' cascade and 
 The clouds are icp_synthetic_pair's, the normals seeded unit vectors (the metric's arithmetic does
 not care that they are not a surface's).  Under `rocprofv3 --kernel-trace --stats` the kernels' own
 times are in the trace: a weighted instantiation of a moments kernel (gated_moments_kernel<YIN, KIND>,
-plane_moments_kernel<YIN, KIND>) reads and writes the bytes of the unweighted one (KIND = 0), whose
+plane_moments_kernel<YIN, KIND, false>) reads and writes the bytes of the unweighted one (KIND = 0), whose
 time in the same trace is its yardstick; the stated algorithmic bytes per point are printed here.
 """
 import argparse
@@ -25,8 +25,8 @@ import icp_amd as amd  # noqa: E402
 
 # bytes a point of one launch, from what each kernel reads and writes (y gathered through idx / kpos)
 BYTES = {
-    "gated_moments_kernel<false, KIND>": 24 + 4 + 32 + 24,       # p, idx, y gather, y store
-    "plane_moments_kernel<false, KIND>": 24 + 4 + 32 + 24 + 32,  # ... + the normal's gather
+    "gated_moments_kernel<false, KIND>": 24 + 4 + 32 + 24,              # p, idx, y gather, y store
+    "plane_moments_kernel<false, KIND, false>": 24 + 4 + 32 + 24 + 32,  # ... + the normal's gather
 }
 KINDS = {"huber": amd.ROBUST_HUBER, "tukey": amd.ROBUST_TUKEY, "cauchy": amd.ROBUST_CAUCHY}
 LOOPS = [("gated", False, False), ("gated+w", False, True), ("plane", True, False), ("plane+w", True, True)]

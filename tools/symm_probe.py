@@ -24,10 +24,10 @@ import icp_amd as amd  # noqa: E402
 
 # bytes a point of one launch, from what each kernel reads and writes (y gathered through idx / kpos)
 BYTES = {
-    "plane_moments_kernel": 24 + 4 + 32 + 24 + 32,        # p, idx, y gather, y store, the normal's gather
-    "plane_transform_kernel": 24 + 24 + 4 + 32 + 24,      # p, y, idx, normal gather, p store
-    "symm_moments_kernel": 24 + 4 + 32 + 24 + 32 + 24,    # ... + u0
-    "symm_transform_kernel": 24 + 24 + 4 + 32 + 24 + 24,  # ... + u0
+    "plane_moments_kernel<*, *, false>": 24 + 4 + 32 + 24 + 32,                # p, idx, y gather, y store, the normal's gather
+    "plane_transform_kernel<>": 24 + 24 + 4 + 32 + 24,                         # p, y, idx, normal gather, p store
+    "plane_moments_kernel<*, *, true, SymmArgs>": 24 + 4 + 32 + 24 + 32 + 24,  # ... + u0
+    "plane_transform_kernel<SymmArgs>": 24 + 24 + 4 + 32 + 24 + 24,            # ... + u0
 }
 
 
