@@ -74,7 +74,10 @@ typedef struct icp_result {
     int converged;  /* 1 if err < threshold stopped the loop (src/GPU/gpu.cc:79-80)   */
     double err;     /* last err = (e_align + e_apply) / np, as printed (gpu.cc:76);
                        with icp_set_plane_symmetric the residual is along a sum of two
-                       normals: up to four times the one-sided metric's           */
+                       normals: up to four times the one-sided metric's; with
+                       icp_set_plane_to_plane it is the mean squared Mahalanobis residual,
+                       which carries the tangential distance with weight 1/2 and does
+                       not fall to zero between two samplings of a surface           */
     double s;       /* last increment's scale       (GPU::ICP::s, gpu.hh:91); 1 with
                        ICP_METRIC_POINT_TO_PLANE                                      */
     double R[9];    /* last increment's rotation, row-major (GPU::ICP::r, gpu.hh:93)  */
@@ -289,7 +292,9 @@ int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t n
  * multiplied by a weight w_j of its residual at the current pose (PCL / Open3D robust kernels).
  * With d = p_j - y_j the residual is r2_j = (dx*dx + dy*dy) + dz*dz, the gate's own d2, under
  * ICP_METRIC_POINT_TO_POINT, and r2_j = r_j * r_j with r_j = (dx*nx + dy*ny) + dz*nz under
- * ICP_METRIC_POINT_TO_PLANE.  With k in the clouds' units and k2 = k * k (fp64, once, on the host):
+ * ICP_METRIC_POINT_TO_PLANE (with icp_set_plane_to_plane: the squared Mahalanobis residual d^T M d
+ * of that iteration, so k is in those units: for a residual along both normals, 1 / sqrt(2 epsilon)
+ * times the distance).  With k in the clouds' units and k2 = k * k (fp64, once, on the host):
  *   ICP_ROBUST_HUBER   w = r2 <= k2 ? 1 : k / sqrt(r2)
  *   ICP_ROBUST_TUKEY   w = r2 < k2 ? (1 - r2/k2)^2 : 0
  *   ICP_ROBUST_CAUCHY  w = 1 / (1 + r2/k2)
@@ -434,6 +439,43 @@ int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz);
  * ICP_E_RANGE for a scene with a non-finite coordinate.  It touches nothing a run depends on except
  * the scene normals, and needs no model. */
 int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate);
+
+/* ---- the plane-to-plane iteration (generalised ICP) from both clouds' normals ---- */
+/* icp_set_plane_to_plane(ctx, epsilon) with 0 < epsilon <= 1: with ICP_METRIC_POINT_TO_PLANE every
+ * iteration of icp_run minimises the plane-to-plane objective of generalised ICP (Segal, Haehnel and
+ * Thrun, RSS 2009) in the regularised form of PCL's GeneralizedIterativeClosestPoint and Open3D's
+ * registration_generalized_icp, whose default epsilon is 1e-3: a point's covariance has the eigenvalues
+ * (epsilon, 1, 1), epsilon along its normal, C = I - (1 - epsilon) n n^T.  The covariances are a function
+ * of the normals the context holds, and the scene's turn with the scene because its normals do.  One
+ * iteration, with N the model's normals, u0 the scene's as given, c the model's centroid, Q the rotation
+ * of icp_get_transform at the iteration's start and k1 = 1 - epsilon (fp64, once):
+ * 1. The search, y_j = m[idx_j], d = p_j - y_j, the gate, the trim, the mask and K: unchanged.
+ * 2. N_j = N[idx_j], u_j = Q u0_j (rows summed as ((Q0 u0 + Q1 u1) + Q2 u2)).  S = 2 I - k1 (N_j N_j^T +
+ *    u_j u_j^T), six entries s_ab = [a == b ? 2 : 0] - k1 * (N_a * N_b + u_a * u_b).  A zero normal gives
+ *    that cloud's covariance as I; the sign of a normal changes no bit.  Normals are used as given and are
+ *    expected to be unit or zero: when S is not positive definite (s00 > 0, s00 s11 - s01 s01 > 0 and
+ *    det S > 0, each false for a NaN) the pair counts in K and adds nothing else.  M_j = adj(S) * (1 / det S)
+ *    in fp64; the condition number of S is at most 1 / epsilon.
+ * 3. v = p_j - c, g = M_j d, r2 = d . g (the squared Mahalanobis residual), w = the robust weight of r2 (1
+ *    without).  With J = [-[v]x | I]: A = sum w J^T M_j J, b = -sum w [v x g ; g], the count, and with
+ *    weights W and K+: the plane metric's 28 (30) sums in its columns.  For M = n n^T they are the plane
+ *    metric's own.
+ * 4. The fold, the all-reduce, the least counts (6), the scaled Cholesky with the 1e-12 pivot and the
+ *    step R = exp([omega]x), t = (c + tau) - R c, s = 1 are the one-sided plane metric's: one
+ *    Gauss-Newton step a search, as Open3D does.
+ * 5. Every point moves; err = (e + e) / K with e = sum over the kept pairs of (q_j - y_j)^T M'_j (q_j -
+ *    y_j), M' from Q' u0, Q' the total's rotation with this step composed.  This err -- icp_result.err,
+ *    the trace, what the threshold is compared with -- carries the tangential distance with weight 1/2:
+ *    between different samplings of one surface it does not fall to zero.
+ * The tangential term of weight epsilon also registers a planar model, where both other forms stop with
+ * ICP_E_DEGENERATE.  It works with the gate, the trim, robust weights, ranks (with given scene normals)
+ * and communicators as the plane metric does.  epsilon = 0 (the default) is off: icp_run exactly as
+ * without this call; with the point-to-point metric the switch has no effect.  A NaN, a negative value
+ * or one above 1 is ICP_E_ARG and leaves the earlier setting.  The setting survives icp_set_scene /
+ * icp_set_model.  On together with icp_set_plane_symmetric(1), icp_run returns ICP_E_ARG before it
+ * changes anything; without model normals or scene normals it returns ICP_E_NO_MODEL, and
+ * icp_last_error names the missing setter. */
+int icp_set_plane_to_plane(icp_ctx *ctx, double epsilon);
 
 /* ---- coarse-to-fine: the total transform, a pose for the scene, a voxel downsample -- */
 /* icp_get_transform: the similarity q = s R p + t (R row-major) that maps the scene as icp_set_scene*

@@ -26,6 +26,11 @@
 //                      model normals (--normals | --estimate-normals) and one of scene normals
 //                      (--scene-normals | --estimate-scene-normals); its error is along a sum of two normals,
 //                      up to four times the one-sided metric's (--threshold compares with it)
+//   --gicp             the plane-to-plane iteration of generalised ICP (icp_set_plane_to_plane): the same normals
+//                      options as --symmetric, which it excludes; its error is the mean squared Mahalanobis
+//                      residual (--threshold compares with it); works under --pyramid
+//   --gicp-epsilon E   the covariances' eigenvalue along the normal, 0 < E <= 1 (default 1e-3, PCL's and
+//                      Open3D's); needs --gicp
 //   --scene-normals FILE  the scene's normals, a CSV in the clouds' format with one row per scene point, in
 //                      the frame of the scene file; excludes --estimate-scene-normals and --pyramid
 //   --estimate-scene-normals K  the scene's normals estimated from its own K nearest neighbours (3 <= K <= 64,
@@ -84,7 +89,7 @@ int main(int argc, char **argv)
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
         std::printf("       options: [--max-dist X] [--trim F] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
-                    "[--symmetric] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
+                    "[--symmetric | --gicp [--gicp-epsilon E]] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
         return -1;
@@ -97,7 +102,8 @@ int main(int argc, char **argv)
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
     const char *robust = nullptr, *robust_k = nullptr, *trim = nullptr;
     const char *scene_normals = nullptr, *estimate_scene = nullptr, *write_scene_normals = nullptr;
-    bool symmetric = false;
+    bool symmetric = false, gicp = false;
+    const char *gicp_epsilon = nullptr;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
@@ -114,6 +120,8 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
         else if (!std::strcmp(argv[a], "--symmetric")) symmetric = true;
+        else if (!std::strcmp(argv[a], "--gicp")) gicp = true;
+        else if (!std::strcmp(argv[a], "--gicp-epsilon") && a + 1 < argc) gicp_epsilon = argv[++a];
         else if (!std::strcmp(argv[a], "--scene-normals") && a + 1 < argc) scene_normals = argv[++a];
         else if (!std::strcmp(argv[a], "--estimate-scene-normals") && a + 1 < argc) estimate_scene = argv[++a];
         else if (!std::strcmp(argv[a], "--write-scene-normals") && a + 1 < argc) write_scene_normals = argv[++a];
@@ -155,6 +163,29 @@ int main(int argc, char **argv)
     }
     if (symmetric && (!(normals || estimate) || !(scene_normals || estimate_scene))) {
         std::fprintf(stderr, "[error] --symmetric needs the model's normals (--normals or --estimate-normals) and the "
+                             "scene's (--scene-normals or --estimate-scene-normals)\n");
+        return -1;
+    }
+    // the plane-to-plane switch: the same normals, never with --symmetric
+    double gicp_eps = 1e-3;
+    if (gicp_epsilon) {
+        char *end = nullptr;
+        gicp_eps = std::strtod(gicp_epsilon, &end);
+        if (end == gicp_epsilon || *end || !(gicp_eps > 0.0 && gicp_eps <= 1.0)) {
+            std::fprintf(stderr, "[error] --gicp-epsilon: %s is not a number in (0, 1]\n", gicp_epsilon);
+            return -1;
+        }
+        if (!gicp) {
+            std::fprintf(stderr, "[error] --gicp-epsilon needs --gicp\n");
+            return -1;
+        }
+    }
+    if (gicp && symmetric) {
+        std::fprintf(stderr, "[error] --gicp and --symmetric exclude each other\n");
+        return -1;
+    }
+    if (gicp && (!(normals || estimate) || !(scene_normals || estimate_scene))) {
+        std::fprintf(stderr, "[error] --gicp needs the model's normals (--normals or --estimate-normals) and the "
                              "scene's (--scene-normals or --estimate-scene-normals)\n");
         return -1;
     }
@@ -295,6 +326,7 @@ int main(int argc, char **argv)
         return 3;
     };
     if ((rc = icp_set_plane_symmetric(ctx, symmetric ? 1 : 0)) != ICP_OK) return die("--symmetric");
+    if ((rc = icp_set_plane_to_plane(ctx, gicp ? gicp_eps : 0.0)) != ICP_OK) return die("--gicp");
     // --write-normals / --write-scene-normals: a cloud's current normals, the clouds' format
     const auto write_normals_file = [&](const char *option, int (*get)(icp_ctx *, double *), size_t rows, const char *path) {
         std::vector<double> nout(3 * rows);

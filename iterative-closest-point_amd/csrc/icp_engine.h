@@ -331,6 +331,7 @@ struct icp_ctx {
     // sn_slot_valid falls with every change of the scene's order).  scene_pristine: no icp_run or
     // icp_transform_scene since icp_set_scene* (icp_estimate_scene_normals' condition).
     bool plane_symmetric = false;
+    double plane_to_plane = 0.0; // icp_set_plane_to_plane's epsilon (0: off); reads the same sn / sn_slot
     DevCloud sn, sn_slot;
     bool has_scene_normals = false, sn_slot_valid = false;
     bool scene_pristine = false;

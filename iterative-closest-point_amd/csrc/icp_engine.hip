@@ -1992,6 +1992,13 @@ int icp_set_plane_symmetric(icp_ctx *ctx, int on)
     return ICP_OK;
 }
 
+int icp_set_plane_to_plane(icp_ctx *ctx, double epsilon)
+{
+    if (!ctx || !(epsilon >= 0.0 && epsilon <= 1.0)) return ICP_E_ARG; // (false for a NaN)
+    ctx->plane_to_plane = epsilon;
+    return ICP_OK;
+}
+
 // u0 (the caller's order) from the scene's interleaved normals (host or device memory)
 static int set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t n, bool host)
 {

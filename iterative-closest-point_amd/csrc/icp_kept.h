@@ -1,7 +1,7 @@
 // icp_kept.h — what the kept-pairs iterations share on the device (icp_gated.hip: point-to-point
-// under the max-distance gate; icp_plane.hip: point-to-plane, gated or not).  Private to those two
-// files, which hold each metric's own arithmetic and are compiled with IEEE semantics (`d2 <= D`
-// must stay false for a NaN):
+// under the max-distance gate; icp_plane.hip: point-to-plane, gated or not; icp_gicp.hip: its
+// plane-to-plane form).  Private to those three files, which hold each metric's own arithmetic and
+// are compiled with IEEE semantics (`d2 <= D` must stay false for a NaN):
 //   kept_pairs_pass   the moments kernels' loop: y, the gate, the mask word, a callable per kept pair
 //   kept_cut          a trimmed iteration's gate: the smaller of D and the cut selected on the device
 //   robust_weight     a kept pair's weight from its squared residual (icp_set_robust)

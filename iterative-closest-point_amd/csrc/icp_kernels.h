@@ -786,7 +786,7 @@ void launch_nn_exact_few(const double *q_aos, int nq, const double4 *m4, int nm,
 void launch_reduce_pair(const double *part17, const double *part1, int nblocks, double *out, hipStream_t st);
 void launch_reduce(const double *partials, int nblocks, int K, double *out, hipStream_t st);
 
-// ---- the kept-pairs iterations (icp_gated.hip, icp_plane.hip, icp_kept.h) ------------------------
+// ---- the kept-pairs iterations (icp_gated.hip, icp_plane.hip, icp_gicp.hip, icp_kept.h) ------------------------
 // icp_run over the kept pairs: the max-distance gate (icp_set_max_distance), the point-to-plane
 // metric (icp_set_metric), robust weights (icp_set_robust), a trim (icp_set_trim), or any together.
 // The moments' sums of a point-to-point iteration: the 17 one-pass terms over the kept pairs (sums
@@ -831,10 +831,17 @@ struct SymmArgs {
     double q0[9];
     int have_q0;
 };
+// The plane-to-plane form (icp_set_plane_to_plane; icp_gicp.hip): the same scene normals and total, and
+// k1 = 1 - epsilon (fp64, once on the host).  Passed by value to that file's two kernels.
+struct GicpArgs {
+    SymmArgs sy;
+    double k1;
+};
 // What a moments pass reads and writes (host side: the launcher hands the kernels plain arguments).
 struct KeptPass {
     bool plane;                    // the point-to-plane metric: n4 and c are read
     const SymmArgs *symm;          // ... in its symmetric form (null: one-sided)
+    const GicpArgs *gicp;          // ... in its plane-to-plane form (launch_gicp_moments alone reads it)
     int robust_kind;               // kRobust*; with a weight, k and k2 = k * k
     double k, k2;
     const int *idx;                // the search's correspondences; kpos / m4kd: its kd-ordered form, or null
@@ -890,6 +897,15 @@ void launch_kept_transform(double *px, double *py, double *pz, const double *yx,
                            int n, const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask,
                            const int *idx, const double4 *n4, double *partials, hipStream_t st,
                            const SymmArgs *symm = nullptr);
+// The plane-to-plane form's moments and transform (icp_gicp.hip), in launch_kept_moments' and
+// launch_kept_transform's places: the same rows in the plane metric's columns, each kept pair entering
+// with its 3 x 3 information matrix from n4[idx[i]] and the scene's normal turned by the total
+// (a.gicp, not null); the transform's partial is the kept points' squared Mahalanobis residual.  The
+// fold and the step between them are launch_kept_step's with plane and not symm.
+void launch_gicp_moments(const KeptPass &a, bool y_ready);
+void launch_gicp_transform(double *px, double *py, double *pz, const double *yx, const double *yy, const double *yz, int n,
+                           const Xform *xf, const int *done, float4 *p32, const unsigned long long *mask, const int *idx,
+                           const double4 *n4, double *partials, hipStream_t st, const GicpArgs &gicp);
 // nblocks > 0: sums[kSumErr] = the fold of the partial rows; step: launch_err_step's with N =
 // gate->K, and h_ktrace[iter] = K for a recorded iteration
 void launch_gated_err(const double *partials, int nblocks, double *sums, bool step, double threshold, int max_iter,

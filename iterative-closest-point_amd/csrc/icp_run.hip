@@ -697,6 +697,9 @@ template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int m
 // (icp_plane.hip: SYMM), which also read the scene's normals u0 in the scene's current order and the
 // total since icp_set_scene* (SymmArgs: the context's at the run's start, the run's own from the loop
 // state); everything else of the loop, the sums' width and the all-reduces included, is the plane metric's.
+// With icp_set_plane_to_plane the moments and the transform are icp_gicp.hip's (each kept pair enters
+// with a 3 x 3 information matrix from both clouds' normals; the same SymmArgs and 1 - epsilon), and
+// the fold and step between them are the one-sided plane metric's as they stand.
 int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, icp_result *res, bool need_p32,
              std::chrono::steady_clock::time_point wall0)
 {
@@ -706,6 +709,10 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     const bool symm = plane && ctx->plane_symmetric;
     if (symm && !ctx->has_scene_normals)
         return fail(ctx, ICP_E_NO_MODEL, "icp_run: the symmetric point-to-plane iteration needs the scene's normals "
+                                         "(icp_set_scene_normals, icp_estimate_scene_normals)");
+    const bool gicp = plane && ctx->plane_to_plane > 0.0; // (never with symm: run_setup refused both)
+    if (gicp && !ctx->has_scene_normals)
+        return fail(ctx, ICP_E_NO_MODEL, "icp_run: the plane-to-plane iteration needs the scene's normals "
                                          "(icp_set_scene_normals, icp_estimate_scene_normals)");
     if (max_iter < 1) return finish_run(ctx, threshold, err_trace, res, wall0); // (no gate evaluated: the last one stays)
     const size_t n = ctx->scene.n;
@@ -753,7 +760,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     // order, made once per order), and the context's total at the run's start, which the kernels
     // compose the run's own onto.
     SymmArgs sy = {};
-    if (symm) {
+    if (symm || gicp) {
         const DevCloud *U = nullptr;
         TRY(scene_normals_current(ctx, &U));
         sy.ux = U->x, sy.uy = U->y, sy.uz = U->z;
@@ -761,9 +768,12 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         sy.have_q0 = ctx->tot_n > 0 ? 1 : 0;
         for (int k = 0; k < 9; ++k) sy.q0[k] = sy.have_q0 ? ctx->tot[1 + k] : (k % 4 == 0 ? 1.0 : 0.0);
     }
+    GicpArgs ga = {}; // (the plane-to-plane form: the same u0 and total; read by its two launchers alone)
+    if (gicp) ga = {sy, 1.0 - ctx->plane_to_plane};
     KeptPass pass = {};
     pass.plane = plane;
     pass.symm = symm ? &sy : nullptr;
+    pass.gicp = gicp ? &ga : nullptr;
     pass.robust_kind = robust;
     pass.k = ctx->robust_k, pass.k2 = ctx->robust_k2;
     pass.m4 = ctx->m4, pass.n4 = ctx->n4;
@@ -787,7 +797,8 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         pass.idx = ctx->idx;
         pass.kpos = ctx->kpos_valid ? ctx->kpos : nullptr;
         pass.m4kd = ctx->m4kd;
-        launch_kept_moments(pass, y_ready);
+        if (gicp) launch_gicp_moments(pass, y_ready);
+        else launch_kept_moments(pass, y_ready);
         launch_kept_step(fold, ctx->kept_part, nb, do_step);
     };
     LoopRun r; // (the ring and the after-search bookkeeping only: no timing, no policy)
@@ -845,9 +856,13 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                 LAUNCHCHK(plane ? "plane_solve" : "gated_horn");
             }
             // 5-6. every point moves; the kept points' residual; err = (e + e) / K
-            launch_kept_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
-                                  ctx->kept_mask, ctx->idx, plane ? ctx->n4 : nullptr, ctx->partials, ctx->st,
-                                  symm ? &sy : nullptr);
+            if (gicp)
+                launch_gicp_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                      ctx->kept_mask, ctx->idx, ctx->n4, ctx->partials, ctx->st, ga);
+            else
+                launch_kept_transform(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, need_p32 ? P.f : nullptr,
+                                      ctx->kept_mask, ctx->idx, plane ? ctx->n4 : nullptr, ctx->partials, ctx->st,
+                                      symm ? &sy : nullptr);
             if (!need_p32) ctx->p32_stale = true;
             const int sl = r.enqueued % kRing;
             r.slot_ticket[sl] = ++ctx->flag_ticket;
@@ -915,7 +930,8 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         std::snprintf(piv, sizeof(piv), "%.3g", hk.min_pivot);
         return fail(ctx, ICP_E_DEGENERATE,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) +
-                        " has a degenerate point-to-plane system (smallest pivot " + piv + ", K = " +
+                        " has a degenerate " + (gicp ? "plane-to-plane" : "point-to-plane") + " system (smallest pivot " +
+                        piv + ", K = " +
                         std::to_string(hk.K) + ")");
     }
     return ICP_OK;
@@ -1194,6 +1210,10 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     r.ctx = ctx;
     r.max_iter = max_iter;
     r.threshold = threshold;
+    // the two switches on the plane metric exclude each other: refused before anything changes
+    if (ctx && ctx->metric == ICP_METRIC_POINT_TO_PLANE && ctx->plane_symmetric && ctx->plane_to_plane > 0.0)
+        return fail(ctx, ICP_E_ARG, "icp_run: icp_set_plane_symmetric and icp_set_plane_to_plane are both on; the "
+                                    "point-to-plane metric takes one form at a time");
     TRY(run_setup_buffers(r));
     *handed = true;
     // icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim: the kept-pairs loop (never the one-launch kernels or the

@@ -82,7 +82,7 @@ EXPORTED = [
     "icp_voxel_downsample", "icp_voxel_downsample_device", "icp_get_transform", "icp_transform_scene",
     "icp_set_trim", "icp_get_trim_trace", "icp_select_kth",
     "icp_set_plane_symmetric", "icp_set_scene_normals", "icp_set_scene_normals_device", "icp_get_scene_normals",
-    "icp_estimate_scene_normals",
+    "icp_estimate_scene_normals", "icp_set_plane_to_plane",
 ]
 
 
@@ -221,6 +221,8 @@ def lib() -> C.CDLL:
         L.icp_set_scene_normals_device.argtypes = [vp, vp, sz]
         L.icp_get_scene_normals.argtypes = [vp, dp]
         L.icp_estimate_scene_normals.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong)]
+    if hasattr(L, "icp_set_plane_to_plane"):
+        L.icp_set_plane_to_plane.argtypes = [vp, C.c_double]
     _lib = L
     return L
 
@@ -557,6 +559,13 @@ class Context:
         (needs set_model_normals and set_scene_normals; its err is up to four times the one-sided one)."""
         self._check(lib().icp_set_plane_symmetric(self._h, int(on)))
 
+    def set_plane_to_plane(self, eps):
+        """icp_set_plane_to_plane: with METRIC_POINT_TO_PLANE, run() minimises generalised ICP's plane-to-plane
+        objective, each cloud's covariance (eps, 1, 1) about its normal (0 < eps <= 1; PCL's and Open3D's
+        default is 1e-3; 0: off).  Needs set_model_normals and set_scene_normals, excludes
+        set_plane_symmetric; its err is the mean squared Mahalanobis residual."""
+        self._check(lib().icp_set_plane_to_plane(self._h, float(eps)))
+
     def set_scene_normals(self, n):
         """icp_set_scene_normals: one normal per point of the resident scene as set_scene received it,
         kept as given; the current normals follow the scene (scene_normals)."""
@@ -846,6 +855,8 @@ class ICP:
     robust: tuple | None = None  # (kind, k): icp_set_robust (None: every kept pair with weight 1)
     trim: float | None = None  # icp_set_trim: the fraction of the pairs each iteration keeps (None: all)
     scene_normals: np.ndarray | None = None  # the scene's normals too: the symmetric iteration (needs model normals)
+    plane_to_plane: float | None = None  # epsilon: the plane-to-plane iteration (generalised ICP) instead of the
+    # symmetric one, from the same two sets of normals (the two forms exclude each other; needs scene_normals)
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -855,6 +866,8 @@ class ICP:
     def __post_init__(self):
         if self.normals is not None and self.estimate_normals is not None:
             raise ValueError("ICP: give either normals or estimate_normals, not both")
+        if self.plane_to_plane is not None and self.scene_normals is None:
+            raise ValueError("ICP: plane_to_plane needs scene_normals (and normals or estimate_normals)")
         self.m = _cloud(self.m); self.p = _cloud(self.p)
         self.new_p = self.p.copy()
         self.r = np.eye(3); self.t = np.zeros(3)
@@ -879,7 +892,10 @@ class ICP:
             if self.normals is None and self.estimate_normals is None:
                 raise ValueError("ICP: scene_normals need the model's normals (normals or estimate_normals)")
             self._ctx.set_scene_normals(self.scene_normals)
-            self._ctx.set_plane_symmetric(True)
+            if self.plane_to_plane is not None:  # (one form at a time: icp_run refuses both switches)
+                self._ctx.set_plane_to_plane(self.plane_to_plane)
+            else:
+                self._ctx.set_plane_symmetric(True)
 
     def find_corresponding_opti(self):
         res, errs = self._ctx.run(self.max_iter, self.threshold)
