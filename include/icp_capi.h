@@ -348,6 +348,33 @@ int icp_set_trim(icp_ctx *ctx, double fraction);
  * ICP_E_NO_MODEL if no trimmed run has happened since icp_set_scene. */
 int icp_get_trim_trace(icp_ctx *ctx, double *cut_d2_out, size_t cap);
 
+/* ---- partial overlap without a parameter: one-to-one correspondences -------- */
+/* on == 1: of all the scene points that chose model point j, only the closest is a pair (PCL's
+ * CorrespondenceRejectorOneToOne, libpointmatcher's unique-match filter).  With
+ * d2_i = (dx*dx + dy*dy) + dz*dz between scene point i and its correspondence idx_i (the gate's own
+ * value, under either metric) and B_j = min{ d2_i : idx_i = j }, found on the device, pair i is kept
+ * when d2_i == B_{idx_i} and d2_i <= min(D, C), D and C the gate's and the trim's exactly as without
+ * this call: C is still selected over all pairs and T is unchanged.  The gate and the trim cannot
+ * change the winner: a model point's winner has its smallest d2, so if the winner fails the gate or
+ * the cut every other pair of that point fails too; "the winner among all pairs" and "the winner
+ * among the kept" are the same set, and the three rejectors are independent predicates.  Ties are
+ * kept whole, as at the trim's cut: two scene points at the same smallest d2 of a model point (two
+ * identical points, say) are both pairs, no index breaks a tie, and the mask and K do not depend on
+ * the points' order or on the schedule.  A NaN d2 never wins and is never kept.  Everything after
+ * the mask is the gated loop's: N = K (W with robust weights, which apply to the kept pairs), every
+ * point moves, err = (e + e) / K, and K below the metric's least count (4 / 6) stops the run before
+ * it changes anything with ICP_E_TOO_FEW_POINTS; icp_last_error names the iteration and K and says
+ * that one-to-one is on.  A one-to-one run counts as a gated one for icp_get_inliers /
+ * icp_get_inlier_trace, and always takes the launch loop (ICP_RUN_LAUNCHES), whatever
+ * icp_set_run_mode says.  It combines with the gate, the trim, robust weights, every metric
+ * (point-to-point, point-to-plane and its symmetric and plane-to-plane forms), icp_run_pyramid and
+ * icp_set_allow_unequal.  Ranks are not supported: B_j over ranks is a min-reduction, which the
+ * engine's sum all-reduce cannot express, and with world_size > 1 icp_run returns ICP_E_ARG before
+ * it enqueues anything.
+ * on == 0 switches it off (the default: icp_run exactly as without this call); any other value is
+ * ICP_E_ARG and leaves the earlier setting.  The setting survives icp_set_scene / icp_set_model. */
+int icp_set_one_to_one(icp_ctx *ctx, int on);
+
 /* ---- normals estimated from the model itself: grid k-NN and PCA ------------ */
 /* The k nearest model points of every point of the resident model, searched over the model's grid.
  * 1. Neighbour set.  With d = m_j - m_i and d2 = (dx*dx + dy*dy) + dz*dz in fp64 exactly as written,

@@ -17,6 +17,9 @@
 //   --trim F           trimmed ICP (icp_set_trim): each iteration keeps the fraction F (0 < F <= 1) of the
 //                      pairs with the smallest distances, the expected overlap; combines with --max-dist,
 //                      --normals, --robust and --pyramid (each level trimmed by the same fraction)
+//   --one-to-one       one-to-one correspondences (icp_set_one_to_one): of the scene points that chose one model
+//                      point only the closest is a pair (ties whole); no parameter; combines with --max-dist,
+//                      --trim, --robust, every metric and --pyramid
 //   --normals FILE     the model's normals, a CSV in the clouds' format with one row per model point:
 //                      selects the point-to-plane metric (combines with --max-dist; no scale)
 //   --estimate-normals K  the model's normals estimated from its own K nearest neighbours (3 <= K <= 64,
@@ -88,7 +91,7 @@ int main(int argc, char **argv)
     const char *prog = std::strrchr(argv[0], '/') ? std::strrchr(argv[0], '/') + 1 : argv[0];
     if (argc < 4) { // main.cc:5-8
         std::printf("Usage: ./%s [path_to_ref_cloud] [path_to_transform_cloud] [nb_iter]\n", prog);
-        std::printf("       options: [--max-dist X] [--trim F] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
+        std::printf("       options: [--max-dist X] [--trim F] [--one-to-one] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
                     "[--symmetric | --gicp [--gicp-epsilon E]] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
@@ -102,7 +105,7 @@ int main(int argc, char **argv)
     const char *out = "output.txt", *normals = nullptr, *estimate = nullptr, *write_normals = nullptr;
     const char *robust = nullptr, *robust_k = nullptr, *trim = nullptr;
     const char *scene_normals = nullptr, *estimate_scene = nullptr, *write_scene_normals = nullptr;
-    bool symmetric = false, gicp = false;
+    bool symmetric = false, gicp = false, one_to_one = false;
     const char *gicp_epsilon = nullptr;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     for (int a = 4; a < argc; ++a) {
@@ -116,6 +119,7 @@ int main(int argc, char **argv)
         } else if (!std::strcmp(argv[a], "--threshold") && a + 1 < argc) threshold = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--max-dist") && a + 1 < argc) max_dist = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--trim") && a + 1 < argc) trim = argv[++a];
+        else if (!std::strcmp(argv[a], "--one-to-one")) one_to_one = true;
         else if (!std::strcmp(argv[a], "--normals") && a + 1 < argc) normals = argv[++a];
         else if (!std::strcmp(argv[a], "--estimate-normals") && a + 1 < argc) estimate = argv[++a];
         else if (!std::strcmp(argv[a], "--write-normals") && a + 1 < argc) write_normals = argv[++a];
@@ -315,6 +319,10 @@ int main(int argc, char **argv)
     }
     if ((rc = icp_set_trim(ctx, trim_fraction)) != ICP_OK) {
         std::fprintf(stderr, "[error] --trim: %s (a fraction in (0, 1])\n", icp_strerror(rc));
+        return 3;
+    }
+    if ((rc = icp_set_one_to_one(ctx, one_to_one ? 1 : 0)) != ICP_OK) {
+        std::fprintf(stderr, "[error] --one-to-one: %s\n", icp_strerror(rc));
         return 3;
     }
     if ((rc = icp_set_robust(ctx, robust_kind, robust_scale)) != ICP_OK) {

@@ -119,6 +119,18 @@ __device__ __forceinline__ double residual2(double y0, double y1, double y2, dou
     return (e0 * e0 + e1 * e1) + e2 * e2;
 }
 
+// The 64-bit key of a double whose unsigned order is the doubles' own (icp_select.hip's radix select,
+// icp_unique.hip's minimum and its test in kept_pairs_pass): the sign bit flipped for non-negatives,
+// every bit flipped for negatives, every NaN mapped to all ones:
+//   -inf < ... < -0 < +0 < ... < +inf < NaN.
+constexpr unsigned long long kSignBit = 0x8000000000000000ull;
+__device__ __forceinline__ unsigned long long select_key(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    if ((u & ~kSignBit) > 0x7ff0000000000000ull) return ~0ull; // (every NaN: equal, last)
+    return (u & kSignBit) ? ~u : (u | kSignBit);
+}
+
 // f16 MFMA filter: queries whose scaled |coordinate| exceeds this are clamped and never certified
 constexpr double kF16QueryClamp = 32000.0;
 // every scaled model point b_s has |b_s| below this: the f16 image's scale puts each centred

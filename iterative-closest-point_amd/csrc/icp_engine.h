@@ -307,6 +307,11 @@ struct icp_ctx {
     size_t ctrace_cap = 0;
     bool trim_have = false;
     std::vector<double> trim_ctrace;
+    // One-to-one rejection (icp_set_one_to_one): the switch, and per run the table of each model
+    // point's smallest d2 key (icp_unique.hip; nm words, all ones at every iteration's start).
+    bool one_to_one = false;
+    unsigned long long *uniq_best = nullptr;
+    size_t uniq_best_cap = 0;
     // Robust weights (icp_set_robust): the kind (ICP_ROBUST_*; 0: off), k and k2 = k * k (fp64, once),
     // the mapped W / K+ traces beside the K trace (grown with it), and what icp_get_robust_trace
     // reports, saved at the end of the last robust run (dropped with the scene).

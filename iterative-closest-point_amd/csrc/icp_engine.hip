@@ -1301,7 +1301,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
                     (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
                     (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->trim_keys,
-                    (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state})
+                    (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state,
+                    (void *)ctx->uniq_best})
         if (p) (void)hipFree(p);
     if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
     if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
@@ -1399,6 +1400,13 @@ int icp_set_trim(icp_ctx *ctx, double fraction)
 {
     if (!ctx || !(fraction > 0.0) || !(fraction <= 1.0)) return ICP_E_ARG; // (a NaN fails both)
     ctx->trim_fraction = fraction;
+    return ICP_OK;
+}
+
+int icp_set_one_to_one(icp_ctx *ctx, int on)
+{
+    if (!ctx || (on != 0 && on != 1)) return ICP_E_ARG;
+    ctx->one_to_one = on == 1;
     return ICP_OK;
 }
 

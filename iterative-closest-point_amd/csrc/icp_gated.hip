@@ -36,13 +36,13 @@ namespace {
 // gate's own, and W = sum w and K+ = #{w > 0} are the 19th and 20th sums (doubles: K+ exact below
 // 2^53).  A weight of exactly 1.0 adds the unweighted kind's bits.
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN, int KIND, class... K>
+template <bool YIN, int KIND, class CUT, class... K>
 __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double *__restrict__ px,
     const double *__restrict__ py, const double *__restrict__ pz, int n, double *__restrict__ yx,
     double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     unsigned long long *__restrict__ mask, double *__restrict__ partials, const int *__restrict__ kpos,
-    const double4 *__restrict__ m4kd, K... kk, const double *__restrict__ cut)
+    const double4 *__restrict__ m4kd, K... kk, CUT cut)
 {
     constexpr bool kRobust = KIND != kRobustNone;
     constexpr int WIDTH = kept_width(false, kRobust);
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kBlock) void gated_moments_kernel(
 #pragma unroll
     for (double &v : a) v = 0.0;
     double kept = 0.0;
-    kept_pairs_pass<YIN>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
+    kept_pairs_pass<YIN, kKeptUnique<CUT>>(idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut_of(cut)), mask, kpos, m4kd, best_of(cut),
                          [&](long long, double q0, double q1, double q2, const double4 &m, double dx, double dy, double dz)
                              __attribute__((always_inline)) {
                                  if constexpr (kRobust) {
@@ -203,9 +203,11 @@ void launch_kept_moments(const KeptPass &a, bool y_ready)
     if (a.plane) return plane_moments(a, y_ready);
     kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
         const auto go = [&](auto... kk) {
-            gated_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
-                a.idx, a.m4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.mask, a.partials, a.kpos, a.m4kd, kk...,
-                a.cut);
+            kept_tail(yin, a, [&](auto cut) {
+                gated_moments_kernel<yin(), kind(), decltype(cut), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
+                    a.idx, a.m4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.mask, a.partials, a.kpos, a.m4kd,
+                    kk..., cut);
+            });
         };
         if constexpr (kind() == kRobustNone) go();
         else go(a.k, a.k2);

@@ -110,13 +110,13 @@ __device__ __forceinline__ bool gicp_information(const double4 &N, double a0, do
 // weight of the squared Mahalanobis residual (X = k, k2): M and g are scaled by w, and W and K+ are the
 // 29th and 30th sums.  Q goes through LDS into scalar registers as in the symmetric kernels.
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN, int KIND, class... X>
+template <bool YIN, int KIND, class CUT, class... X>
 __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, GicpArgs ga, X... kk, const double *__restrict__ cut)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, GicpArgs ga, X... kk, CUT cut)
 {
     constexpr bool kRobust = KIND != kRobustNone;
     constexpr int WIDTH = kept_width(true, kRobust);
@@ -127,8 +127,8 @@ __global__ __launch_bounds__(kBlock) void gicp_moments_kernel(
     double a[WIDTH];
 #pragma unroll
     for (int j = 0; j < WIDTH; ++j) a[j] = 0.0;
-    kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
+    kept_pairs_pass<YIN, kKeptUnique<CUT>>(
+        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut_of(cut)), mask, kpos, m4kd, best_of(cut),
         [&](long long i, double q0, double q1, double q2, const double4 &, double dx, double dy, double dz)
             __attribute__((always_inline)) {
                 a[kPlaneCount] += 1.0;
@@ -223,9 +223,11 @@ void launch_gicp_moments(const KeptPass &a, bool y_ready)
 {
     kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
         const auto go = [&](auto... kk) {
-            gicp_moments_kernel<yin(), kind(), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
-                a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
-                a.partials, a.kpos, a.m4kd, *a.gicp, kk..., a.cut);
+            kept_tail(yin, a, [&](auto cut) {
+                gicp_moments_kernel<yin(), kind(), decltype(cut), decltype(kk)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
+                    a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
+                    a.partials, a.kpos, a.m4kd, *a.gicp, kk..., cut);
+            });
         };
         if constexpr (kind() == kRobustNone) go();
         else go(a.k, a.k2);

@@ -35,13 +35,18 @@ namespace {
 // d2 = (dx*dx + dy*dy) + dz*dz as written, and kept(i, p, y, d) for a kept pair.
 // The loop runs whole waves (its bound is the wave's first point), so that every lane takes part
 // in the ballot; word w of the mask holds points 64 w .. 64 w + 63 and is stored by lane 0.
-template <bool YIN, class Kept>
+// UNIQ (icp_set_one_to_one; a template flag: the other instantiations carry no argument, register
+// or branch for it): best is the min pass's table (icp_unique.hip), and a pair within D is kept only
+// when key(d2) == best[idx_i], d2 being the bits that pass scattered (the same p, the stored y, the
+// same expression).
+template <bool YIN, bool UNIQ, class Kept>
 __device__ __forceinline__ void kept_pairs_pass(const int *__restrict__ idx, const double4 *__restrict__ m4,
                                                 const double *__restrict__ px, const double *__restrict__ py,
                                                 const double *__restrict__ pz, int n, double *__restrict__ yx,
                                                 double *__restrict__ yy, double *__restrict__ yz, double D,
                                                 unsigned long long *__restrict__ mask, const int *__restrict__ kpos,
-                                                const double4 *__restrict__ m4kd, Kept &&kept)
+                                                const double4 *__restrict__ m4kd,
+                                                const unsigned long long *__restrict__ best, Kept &&kept)
 {
     const int lane = threadIdx.x & 63;
     const long long G = (long long)gridDim.x * kBlock;
@@ -61,12 +66,27 @@ __device__ __forceinline__ void kept_pairs_pass(const int *__restrict__ idx, con
             const double dx = q0 - m.x, dy = q1 - m.y, dz = q2 - m.z;
             const double d2 = (dx * dx + dy * dy) + dz * dz;
             keep = d2 <= D;
+            if constexpr (UNIQ) {
+                if (keep) keep = select_key(d2) == best[idx[i]];
+            }
             if (keep) kept(i, q0, q1, q2, m, dx, dy, dz);
         }
         const unsigned long long word = __ballot(keep);
         if (lane == 0) mask[i >> 6] = word;
     }
 }
+
+// A moments kernel's last argument, CUT: the trim's nullable cut alone (const double *: the kernel
+// as it is without one-to-one), or with one-to-one on (KeptCutBest) the cut and the table.
+struct KeptCutBest {
+    const double *cut;
+    const unsigned long long *best;
+};
+template <class CUT> constexpr bool kKeptUnique = std::is_same<CUT, KeptCutBest>::value;
+__device__ __forceinline__ const double *cut_of(const double *c) { return c; }
+__device__ __forceinline__ const double *cut_of(const KeptCutBest &c) { return c.cut; }
+__device__ __forceinline__ const unsigned long long *best_of(const double *) { return nullptr; }
+__device__ __forceinline__ const unsigned long long *best_of(const KeptCutBest &c) { return c.best; }
 
 // D of an iteration: the gate's, or with a trim (icp_set_trim; cut not null) the smaller of it and
 // the cut the selection left in device memory (icp_select.hip).  A NaN cut leaves D.
@@ -92,6 +112,16 @@ __device__ __forceinline__ double robust_weight(double r2, double k, double k2)
         static_assert(KIND == kRobustCauchy, "robust_weight: unknown kind");
         return r2 == r2 ? 1.0 / (1.0 + r2 / k2) : 0.0;
     }
+}
+
+// g(a.cut) or, with one-to-one on, g(KeptCutBest): a moments kernel's last argument and its type.
+// The one-to-one kernels exist in the streamed form alone (yin: the min pass has stored y).
+template <class YIN, class Pass, class G> void kept_tail(YIN, const Pass &a, G &&g)
+{
+    if constexpr (YIN::value) {
+        if (a.best) return g(KeptCutBest{a.cut, a.best});
+    }
+    g(a.cut);
 }
 
 // f(YIN, KIND) with the pass's (y_ready, robust kind) as integral constants: a moments kernel's

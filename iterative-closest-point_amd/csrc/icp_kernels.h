@@ -854,6 +854,9 @@ struct KeptPass {
     double D;                      // the gate, squared (+inf: none)
     const double *cut;             // a trimmed run: the device address of the iteration's selected C
                                    // (icp_select.hip), and the pass keeps d2 <= min(D, *cut); null: D alone, no read
+    const unsigned long long *best; // a one-to-one run (icp_set_one_to_one): the min pass's table (icp_unique.hip), and
+                                   // the pass keeps a pair within the gate when key(d2) == best[idx]; null: off.  Read by
+                                   // the streamed passes alone (y_ready: the min pass has stored y), their own kernels
     double c[3];                   // the model's centre
     unsigned long long *mask;
     double *partials;
@@ -954,6 +957,17 @@ void launch_select_pick(unsigned *bins, const double *bins_reduced, int pass, un
 // inside it; more: kSelectPasses x (launch_select_count, launch_select_pick).  bins as above.
 void launch_select_kth(const unsigned long long *keys, int n, unsigned long long rank, SelectState *state, const int *done,
                        unsigned *bins, double *cut, const IterState *s, double *h_trace, hipStream_t st);
+
+// ---- the one-to-one rejector's min pass (icp_unique.hip; icp_set_one_to_one) ---------------------
+// best[j] = min(best[j], key of d2_i) over the points i with idx_i = j, j < nm (an unsigned 64-bit
+// atomic minimum; best is all ones before the pass); y = m[idx] stored unless y_ready and d2_i as
+// launch_select_keys has them; a no-op once *done
+void launch_unique_min(const int *idx, const double4 *m4, const double *px, const double *py, const double *pz, int n,
+                       double *yx, double *yy, double *yz, const int *done, unsigned long long *best, int nm, hipStream_t st,
+                       const int *kpos, const double4 *m4kd, bool y_ready);
+// the same table from the keys launch_select_keys wrote (a one-to-one run with a trim)
+void launch_unique_min_keys(const int *idx, const unsigned long long *keys, int n, const int *done, unsigned long long *best,
+                            int nm, hipStream_t st);
 
 // ---- the model's k nearest neighbours and estimated normals (icp_normals.hip) -------------------
 constexpr int kKnnMinK = 3, kKnnMaxK = 64;

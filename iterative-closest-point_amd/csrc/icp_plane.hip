@@ -121,13 +121,13 @@ template <int KIND> __device__ __forceinline__ double plane_weight(double r2, co
 // X, what the form and the kind add to the arguments: [SymmArgs,] [k, k2] (an unused one costs the
 // pairs' loop instructions).
 // A frozen iteration (st->done) returns at once: neither its sums nor the mask are written.
-template <bool YIN, int KIND, bool SYMM, class... X>
+template <bool YIN, int KIND, bool SYMM, class CUT, class... X>
 __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     const int *__restrict__ idx, const double4 *__restrict__ m4, const double4 *__restrict__ n4,
     const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz, int n,
     double *__restrict__ yx, double *__restrict__ yy, double *__restrict__ yz, const IterState *__restrict__ st, double D,
     double c0, double c1, double c2, unsigned long long *__restrict__ mask, double *__restrict__ partials,
-    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, X... xx, const double *__restrict__ cut)
+    const int *__restrict__ kpos, const double4 *__restrict__ m4kd, X... xx, CUT cut)
 {
     constexpr bool kRobust = KIND != kRobustNone;
     constexpr int WIDTH = kept_width(true, kRobust);
@@ -143,8 +143,8 @@ __global__ __launch_bounds__(kBlock) void plane_moments_kernel(
     double a[WIDTH];
 #pragma unroll
     for (int j = 0; j < WIDTH; ++j) a[j] = 0.0;
-    kept_pairs_pass<YIN>(
-        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut), mask, kpos, m4kd,
+    kept_pairs_pass<YIN, kKeptUnique<CUT>>(
+        idx, m4, px, py, pz, n, yx, yy, yz, kept_cut(D, cut_of(cut)), mask, kpos, m4kd, best_of(cut),
         [&](long long i, double q0, double q1, double q2, const double4 &y, double dx, double dy, double dz)
             __attribute__((always_inline)) {
                 double v[6];
@@ -444,9 +444,12 @@ void plane_moments(const KeptPass &a, bool y_ready)
     kept_dispatch(y_ready, a.robust_kind, [&](auto yin, auto kind) {
         // the kernel of (yin, kind, the form) with what these add to its arguments: [SymmArgs,] [k, k2]
         const auto go = [&](auto symm, auto... xx) {
-            plane_moments_kernel<yin(), kind(), symm(), decltype(xx)...><<<red_blocks(a.n), kBlock, 0, a.st>>>(
-                a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev, a.D, a.c[0], a.c[1], a.c[2], a.mask,
-                a.partials, a.kpos, a.m4kd, xx..., a.cut);
+            kept_tail(yin, a, [&](auto cut) {
+                plane_moments_kernel<yin(), kind(), symm(), decltype(cut), decltype(xx)...>
+                    <<<red_blocks(a.n), kBlock, 0, a.st>>>(a.idx, a.m4, a.n4, a.px, a.py, a.pz, a.n, a.yx, a.yy, a.yz, a.st_dev,
+                                                           a.D, a.c[0], a.c[1], a.c[2], a.mask, a.partials, a.kpos, a.m4kd,
+                                                           xx..., cut);
+            });
         };
         const auto of_form = [&](auto... kk) {
             if (a.symm) go(std::true_type(), *a.symm, kk...);

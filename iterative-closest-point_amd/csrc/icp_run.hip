@@ -4,7 +4,8 @@
 //   icp_run -> run_loop: run_setup, then per iteration enqueue_canon (a scene in slot order: the
 //              canonical schedule) or enqueue_launches (every other scene: the launch loop),
 //              wait_one for the ring's oldest iteration, the drain and finish_run
-//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim)
+//   run_setup hands over to run_kept (icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim,
+//   icp_set_one_to_one)
 //              or run_persistent (the one-launch loops of small clouds) where they apply
 //   run_knobs / run_test_knobs: every environment switch of the run path (the table in icp_engine.h)
 #include <algorithm>
@@ -693,6 +694,14 @@ template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int m
 // moments pass then runs in its streamed form with the cut's address.  With ranks each pass's bins are all-reduced before its pick (kSelectPasses more all-reduces an
 // iteration).  T below the metric's least count stops the run as K below it does.  A trimmed run
 // counts as a gated one for icp_get_inliers, and leaves icp_get_trim_trace its C trace.
+// With icp_set_one_to_one a pair is kept only when it is its model point's closest: between the search
+// (and the trim's selection) and the moments, the table best (one 64-bit key a model point, all ones
+// from a memset on the run's stream at every iteration's start) takes the unsigned minimum of the d2
+// keys that chose each model point (icp_unique.hip: unique_min_kernel gathers and stores y like the
+// keys pass; with a trim it scatters the keys that pass wrote), and every moments pass then runs in
+// its streamed form with the table's address and keeps d2 <= min(D, C) && key(d2) == best[idx].  The
+// minimum is over this rank's points, so more than one rank is refused (run_setup).  A one-to-one run
+// counts as a gated one for icp_get_inliers.
 // With icp_set_plane_symmetric the plane metric's three launches are their symmetric instantiations
 // (icp_plane.hip: SYMM), which also read the scene's normals u0 in the scene's current order and the
 // total since icp_set_scene* (SymmArgs: the context's at the run's start, the run's own from the loop
@@ -718,7 +727,8 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     const size_t n = ctx->scene.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
     const bool trim = ctx->trim_fraction < 1.0;
-    const bool gated = ctx->gate_dmax > 0.0 || trim; // (what icp_get_inliers reports)
+    const bool uniq = ctx->one_to_one;
+    const bool gated = ctx->gate_dmax > 0.0 || trim || uniq; // (what icp_get_inliers reports)
     const double D = ctx->gate_dmax > 0.0 ? ctx->gate_dmax * ctx->gate_dmax : HUGE_VAL; // (fp64, once)
     // the trim's count, PCL's rule: the product in fp64 as written, truncated, once
     const long long T = trim ? std::max(1LL, (long long)(ctx->trim_fraction * (double)ctx->np_total)) : 0;
@@ -746,6 +756,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         if (!ctx->trim_cut) HIPCHK(hipMalloc((void **)&ctx->trim_cut, sizeof(double)));
         HIPCHK(hipMemsetAsync(ctx->trim_bins, 0, sizeof(unsigned) * kSelectBins, ctx->st)); // (each pick leaves them zero)
     }
+    if (uniq) TRY(grow(ctx, &ctx->uniq_best, &ctx->uniq_best_cap, ctx->nm));
     std::memset(ctx->h_kept, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -782,6 +793,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     pass.st_dev = sd;
     pass.D = D;
     pass.cut = trim ? ctx->trim_cut : nullptr;
+    pass.best = uniq ? ctx->uniq_best : nullptr;
     pass.mask = ctx->kept_mask, pass.partials = ctx->kept_part;
     pass.st = ctx->st;
     KeptStep fold = {};
@@ -839,8 +851,20 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                     LAUNCHCHK("select_pick");
                 }
             }
+            // One-to-one: each model point's smallest d2 key into best (all ones before); with a trim
+            // the keys pass above has stored y and the keys, else this pass stores y.
+            if (uniq) {
+                HIPCHK(hipMemsetAsync(ctx->uniq_best, 0xff, sizeof(unsigned long long) * ctx->nm, ctx->st));
+                if (trim)
+                    launch_unique_min_keys(ctx->idx, ctx->trim_keys, (int)n, &sd->done, ctx->uniq_best, (int)ctx->nm, ctx->st);
+                else
+                    launch_unique_min(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)n, Y.x, Y.y, Y.z, &sd->done, ctx->uniq_best,
+                                      (int)ctx->nm, ctx->st, ctx->kpos_valid ? ctx->kpos : nullptr, ctx->m4kd, ctx->y_ready);
+                LAUNCHCHK("unique_min");
+            }
+            const bool y_stored = ctx->y_ready || trim || uniq;
             if (pre_pass) {
-                moments(ctx->y_ready || trim, false); // (the fold alone)
+                moments(y_stored, false); // (the fold alone)
                 LAUNCHCHK("gated_moments (first shifts)");
                 if (ranks) TRY(allreduce(ctx, ctx->sums, width));
                 launch_kept_first_shift(sd, ctx->sums, robust ? kRobustGateW : kGateCount, ctx->st);
@@ -848,7 +872,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             }
             // 2-4. the gate, the kept pairs' sums and count, the metric's step
             // (after the pre-pass y = m[idx] is stored: the pass streams it)
-            moments(ctx->y_ready || pre_pass || trim, !ranks);
+            moments(y_stored || pre_pass, !ranks);
             LAUNCHCHK(plane ? "plane_moments" : "gated_moments");
             if (ranks) {
                 TRY(allreduce(ctx, ctx->sums, width));
@@ -910,9 +934,10 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         ctx->robust_ptrace.assign(ctx->h_ptrace, ctx->h_ptrace + ctx->h_iter->iter);
     }
     TRY(finish_run(ctx, threshold, err_trace, res, wall0));
-    const std::string trimmed = trim ? " (the trim keeps T = " + std::to_string(T) + " of " + std::to_string(ctx->np_total) +
-                                           " pairs, ties at the cut included)"
-                                     : std::string();
+    const std::string trimmed = (trim ? " (the trim keeps T = " + std::to_string(T) + " of " + std::to_string(ctx->np_total) +
+                                            " pairs, ties at the cut included)"
+                                      : std::string()) +
+                                (uniq ? " (one-to-one is on: a model point keeps its closest pair alone)" : "");
     if (hk.status == kGateTooFew && robust)
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
@@ -922,7 +947,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
         return fail(ctx, ICP_E_TOO_FEW_POINTS,
                     "icp_run: iteration " + std::to_string(hk.fail_iter) + " kept K = " + std::to_string(hk.K) +
                         (plane ? " pairs; the point-to-plane metric needs at least 6"
-                               : trim ? " pairs; need at least 4"
+                               : trim || (uniq && D == HUGE_VAL) ? " pairs; need at least 4"
                                       : " pairs within the max correspondence distance; need at least 4") +
                         trimmed);
     if (hk.status == kPlaneDegenerate) {
@@ -1214,11 +1239,17 @@ int run_setup(LoopRun &r, icp_ctx *ctx, int max_iter, double threshold, double *
     if (ctx && ctx->metric == ICP_METRIC_POINT_TO_PLANE && ctx->plane_symmetric && ctx->plane_to_plane > 0.0)
         return fail(ctx, ICP_E_ARG, "icp_run: icp_set_plane_symmetric and icp_set_plane_to_plane are both on; the "
                                     "point-to-plane metric takes one form at a time");
+    // one-to-one: the table's minimum is over one rank's points (a min-reduction over ranks is not
+    // the engine's sum all-reduce): refused before anything is enqueued
+    if (ctx && ctx->one_to_one && ctx->world > 1)
+        return fail(ctx, ICP_E_ARG, "icp_run: icp_set_one_to_one is on with world_size > 1; the closest pair of a model "
+                                    "point is chosen on one rank (ranks are not supported)");
     TRY(run_setup_buffers(r));
     *handed = true;
-    // icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim: the kept-pairs loop (never the one-launch kernels or the
-    // fused iterations)
-    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0 || ctx->robust_kind != 0 || ctx->trim_fraction < 1.0)
+    // icp_set_metric, icp_set_max_distance, icp_set_robust, icp_set_trim, icp_set_one_to_one: the kept-pairs loop (never
+    // the one-launch kernels or the fused iterations)
+    if (ctx->metric == ICP_METRIC_POINT_TO_PLANE || ctx->gate_dmax > 0.0 || ctx->robust_kind != 0 || ctx->trim_fraction < 1.0 ||
+        ctx->one_to_one)
         return run_kept(ctx, max_iter, threshold, err_trace, res, r.need_p32, r.wall0);
     {
         size_t lds = 0;

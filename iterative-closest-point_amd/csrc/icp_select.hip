@@ -31,15 +31,7 @@
 namespace icp {
 namespace {
 
-constexpr unsigned long long kSignBit = 0x8000000000000000ull;
-
-__device__ __forceinline__ unsigned long long select_key(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    if ((u & ~kSignBit) > 0x7ff0000000000000ull) return ~0ull; // (every NaN: equal, last)
-    return (u & kSignBit) ? ~u : (u | kSignBit);
-}
-
+// (select_key, the map itself: icp_device.h, shared with the one-to-one rejector)
 __device__ __forceinline__ double select_value(unsigned long long key)
 {
     if (key == ~0ull) return __longlong_as_double(0x7ff8000000000000ll); // (a quiet NaN)

@@ -83,6 +83,7 @@ EXPORTED = [
     "icp_set_trim", "icp_get_trim_trace", "icp_select_kth",
     "icp_set_plane_symmetric", "icp_set_scene_normals", "icp_set_scene_normals_device", "icp_get_scene_normals",
     "icp_estimate_scene_normals", "icp_set_plane_to_plane",
+    "icp_set_one_to_one",
 ]
 
 
@@ -223,6 +224,8 @@ def lib() -> C.CDLL:
         L.icp_estimate_scene_normals.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong)]
     if hasattr(L, "icp_set_plane_to_plane"):
         L.icp_set_plane_to_plane.argtypes = [vp, C.c_double]
+    if hasattr(L, "icp_set_one_to_one"):
+        L.icp_set_one_to_one.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -616,6 +619,11 @@ class Context:
         distances (ties at the cut included); 1: off."""
         self._check(lib().icp_set_trim(self._h, float(fraction)))
 
+    def set_one_to_one(self, on):
+        """icp_set_one_to_one: run() keeps, of all the pairs that chose one model point, only the closest
+        (ties whole); False: off.  Combines with the gate, the trim, robust weights and every metric."""
+        self._check(lib().icp_set_one_to_one(self._h, int(on)))
+
     def trim_trace(self) -> np.ndarray:
         """C, the selected squared distance, of each recorded iteration of the last trimmed run() (float64)."""
         n = lib().icp_get_trim_trace(self._h, None, 0)
@@ -857,6 +865,7 @@ class ICP:
     scene_normals: np.ndarray | None = None  # the scene's normals too: the symmetric iteration (needs model normals)
     plane_to_plane: float | None = None  # epsilon: the plane-to-plane iteration (generalised ICP) instead of the
     # symmetric one, from the same two sets of normals (the two forms exclude each other; needs scene_normals)
+    one_to_one: bool = False  # icp_set_one_to_one: a model point keeps its closest pair alone
     new_p: np.ndarray = field(init=False)
     s: float = field(init=False, default=1.0)
     r: np.ndarray = field(init=False)
@@ -878,6 +887,8 @@ class ICP:
             self._ctx.set_max_distance(self.max_distance)
         if self.trim is not None:
             self._ctx.set_trim(self.trim)
+        if self.one_to_one:
+            self._ctx.set_one_to_one(True)
         if self.robust is not None:
             self._ctx.set_robust(*self.robust)
         self._ctx.set_model(self.m)
