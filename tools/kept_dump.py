@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Everything the kept-pairs loop (icp_run under icp_set_max_distance, icp_set_metric, icp_set_robust,
-icp_set_trim and / or icp_set_plane_symmetric) computes on the cases of tests/test_gpu_gated.py,
-tests/test_gpu_plane.py and tests/test_gpu_symm.py and on every combination of its options at one
+icp_set_trim, icp_set_one_to_one and / or icp_set_plane_symmetric, icp_set_plane_to_plane) computes on the
+cases of tests/test_gpu_gated.py, tests/test_gpu_plane.py and tests/test_gpu_symm.py and on every combination of its options at one
 small size (matrix()), and what the normals' estimators and icp_model_knn return (normals()), dumped for a
 bit-for-bit comparison of two libraries (ICP_AMD_LIB picks the library; tools/build_ab.sh builds
 another revision's):
@@ -28,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import icp_amd as amd  # noqa: E402
 import datasets  # noqa: E402
 import gated_ref as G  # noqa: E402
+import gicp_ref as GI  # noqa: E402
 import normals_ref as NR  # noqa: E402
 import plane_ref as P  # noqa: E402
 import symm_ref as S  # noqa: E402
@@ -73,21 +74,26 @@ def record(tag, ctx, iters, threshold=-1.0):
     OUT[tag + "/stats"] = np.array([int(v) & (2**64 - 1) for k, v in sorted(st.items()) if not isinstance(v, float)], dtype=np.uint64)
 
 
-def options(ctx, dmax, robust, trim):
-    """robust: (kind, k) or None; trim: the fraction or None"""
+def options(ctx, dmax, robust, trim, uniq=False):
+    """robust: (kind, k) or None; trim: the fraction or None; uniq: one-to-one"""
     if dmax:
         ctx.set_max_distance(dmax)
     if robust:
         ctx.set_robust(*robust)
     if trim:
         ctx.set_trim(trim)
+    if uniq:
+        ctx.set_one_to_one(True)
 
 
-def symmetric(ctx, snrm):
-    """snrm: the scene's normals, or None: the one-sided form"""
+def symmetric(ctx, snrm, gicp=False):
+    """snrm: the scene's normals, or None: the one-sided form; gicp: plane-to-plane, not the symmetric form"""
     if snrm is not None:
         ctx.set_scene_normals(snrm)
-        ctx.set_plane_symmetric(True)
+        if gicp:
+            ctx.set_plane_to_plane(GI.EPS)
+        else:
+            ctx.set_plane_symmetric(True)
 
 
 def unit_rows(n, seed):
@@ -96,7 +102,7 @@ def unit_rows(n, seed):
 
 
 def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None, robust=None, trim=None, snrm=None,
-          **ctx_args):
+          gicp=False, uniq=False, **ctx_args):
     with amd.Context(0, mode, **ctx_args) as ctx:
         if variant is not None:
             ctx.set_nn_variant(variant)
@@ -105,12 +111,12 @@ def fresh(tag, m, p, dmax, iters, nrm=None, threshold=-1.0, mode=0, variant=None
             ctx.set_model_normals(nrm)
             ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
         ctx.set_scene(p)
-        symmetric(ctx, snrm)
-        options(ctx, dmax, robust, trim)
+        symmetric(ctx, snrm, gicp)
+        options(ctx, dmax, robust, trim, uniq)
         record(tag, ctx, iters, threshold)
 
 
-def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None, trim=None, snrm=None):
+def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None, trim=None, snrm=None, gicp=False):
     red = HostAllReduce(world)
     errors = []
 
@@ -123,7 +129,7 @@ def sharded(tag, m, p, dmax, world, iters, nrm=None, threshold=-1.0, robust=None
                     ctx.set_model_normals(nrm)
                     ctx.set_metric(amd.METRIC_POINT_TO_PLANE)
                 ctx.set_scene(p[b:b + c], np_total=p.shape[0])
-                symmetric(ctx, None if snrm is None else snrm[b:b + c])
+                symmetric(ctx, None if snrm is None else snrm[b:b + c], gicp)
                 options(ctx, dmax, robust, trim)
                 record(f"{tag}/rank{r}", ctx, iters, threshold)
         except Exception as e:
@@ -149,30 +155,36 @@ def slot_scene(n=65536):
     return m, p, nrm
 
 
-MATRIX_N, MATRIX_ITERS, MATRIX_K, MATRIX_F, MATRIX_DMAX = 193, 3, 0.1, 0.75, 0.08
+# MATRIX_F: T = 77 of 193.  Under MATRIX_DMAX the gate keeps 72 pairs at first and 77 to 86 afterwards for the
+# point, symmetric and (weighted) plane-to-plane cells, so in a gate-and-trim cell the gate binds first and
+# the trim after it; the one-sided plane metric stays at 68 to 75 under the gate, where the gate alone binds.
+# (0.75, T = 144, never bound under this gate: C stayed above 4 D.)
+MATRIX_N, MATRIX_ITERS, MATRIX_K, MATRIX_F, MATRIX_DMAX = 193, 3, 0.1, 0.4, 0.08
 KINDS = (("none", amd.ROBUST_NONE), ("huber", amd.ROBUST_HUBER), ("tukey", amd.ROBUST_TUKEY), ("cauchy", amd.ROBUST_CAUCHY))
 
 
 def matrix(clump):
-    """Every cell of metric x weights x trim x gate at n = 193 (three full waves and a partial fourth: the
-    last mask word and the last ballot are partial; "symm": the plane metric's symmetric form on seeded
-    unit normals for the scene) on one rank, and without and with Tukey weights on
-    two (the fold-only pass, the all-reduce at each row width, the step on all-reduced sums); the cow
-    clump with Tukey weights and a trim to convergence; the stops through the weighted and trimmed paths."""
+    """Every cell of metric x weights x trim x gate x one-to-one at n = 193 (three full waves and a partial
+    fourth: the last mask word and the last ballot are partial; "symm" and "gicp": the plane metric's symmetric
+    and plane-to-plane forms on seeded unit normals for the scene) on one rank, and without one-to-one and
+    without and with Tukey weights on two (the fold-only pass, the all-reduce at each row width, the step on
+    all-reduced sums); the cow clump with Tukey weights and a trim to convergence; the stops through the weighted and trimmed paths."""
     m, nrm, p = P.gate_case(MATRIX_N)
     snrm = unit_rows(MATRIX_N, 7)
-    for metric in ("point", "plane", "symm"):
+    for metric in ("point", "plane", "symm", "gicp"):
         for kname, kind in KINDS:
             for trim in (None, MATRIX_F):
                 for dmax in (0.0, MATRIX_DMAX):
                     cell = f"{metric}_{kname}_trim{trim or 'off'}_gate{dmax or 'off'}"
                     args = dict(nrm=None if metric == "point" else nrm, robust=(kind, MATRIX_K) if kind else None, trim=trim,
-                                snrm=snrm if metric == "symm" else None)
+                                snrm=snrm if metric in ("symm", "gicp") else None, gicp=metric == "gicp")
                     fresh(f"matrix/{cell}", m, p, dmax, MATRIX_ITERS, **args)
+                    fresh(f"matrix/{cell}_one_to_one", m, p, dmax, MATRIX_ITERS, uniq=True, **args)
                     if kname in ("none", "tukey"):
                         sharded(f"matrix/world2/{cell}", m, p, dmax, 2, MATRIX_ITERS, **args)
     tukey = (amd.ROBUST_TUKEY, 0.25 * G.cow_ext(clump[0]))
-    fresh("matrix/clump_tukey_trim", clump[0], clump[1], 0.0, 60, threshold=1e-5, robust=tukey, trim=MATRIX_F)
+    # (the clump is a quarter of the scene: its own fraction, not the matrix's)
+    fresh("matrix/clump_tukey_trim", clump[0], clump[1], 0.0, 60, threshold=1e-5, robust=tukey, trim=0.75)
     # K+ below the least count with K above it
     sm, sn, sp, _src = P.synth(MATRIX_N, 100 + MATRIX_N, 0.01)
     for metric in ("point", "plane"):
