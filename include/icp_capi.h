@@ -36,7 +36,8 @@ extern "C" {
 #define ICP_E_NO_DEVICE (-7)      /* no HIP device / bad device ordinal             */
 #define ICP_E_IO (-8)             /* file could not be opened (src/load.cc:11-14)   */
 #define ICP_E_RANGE (-9)          /* coordinates outside the engine's domain        */
-#define ICP_E_DEGENERATE (-10)    /* point-to-plane: an iteration's 6 x 6 system is singular */
+#define ICP_E_DEGENERATE (-10)    /* point-to-plane: an iteration's 6 x 6 system is singular;
+                                     icp_ransac_pose: no hypothesis passed the edge check */
 
 /* ---- nearest-neighbour arithmetic -------------------------------------- */
 /* Both modes return the SAME indices: the first (lowest-index) minimum of the fp64
@@ -549,6 +550,109 @@ int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel
                          double *xyz_out, int32_t *count_out, size_t *n_out);
 int icp_voxel_downsample_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double voxel, const double *origin,
                                 double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out);
+
+/* ---- global registration: FPFH descriptors, feature matches, a RANSAC pose ---- */
+/* What a scene that does NOT start near its answer needs before icp_run: a pose from local shape
+ * descriptors (Rusu, Blodow and Beetz, "Fast Point Feature Histograms (FPFH) for 3D Registration", ICRA
+ * 2009; PCL's FPFHEstimation, Open3D's compute_fpfh_feature / registration_ransac_based_on_correspondence).
+ * The four calls take host arrays, are synchronous, work on any context (a sharded one too: nothing is
+ * communicated), need no resident cloud and touch neither the resident clouds nor anything a run
+ * depends on: an icp_run after any of them is bit-identical to that run on a fresh context.
+ *
+ * icp_fpfh: the descriptors of the n points xyz (3 x n column-major like a cloud): fpfh_out is n x 33
+ * row-major, spfh_out (nullable) the simplified histograms of rule 3, normals_out (nullable, 3 x n)
+ * the normals used.
+ * 1. Grid, normals, neighbours.  A temporary grid of the cloud is built as icp_estimate_scene_normals
+ *    builds the scene's and freed before the call returns.  normals == NULL: they are estimated on that
+ *    grid by the estimator's own kernels, bit for bit what icp_estimate_model_normals(k_normals,
+ *    viewpoint) gives on a fresh context whose model is these points; else normals (3 x n) are used as
+ *    given and k_normals and viewpoint are ignored.  N_i is icp_model_knn's list of point i for k: the
+ *    same kernel, ascending (d2, index), the point itself a candidate.
+ * 2. Pair feature of point i and list entry j (PCL's computePairFeatures); every dot product and 3-term
+ *    sum is ((a + b) + c), a cross product a x b is (ay bz - az by, az bx - ax bz, ax by - ay bx).  With
+ *    d = x_j - x_i and L2 = (dx dx + dy dy) + dz dz the pair is SKIPPED when j == i, L2 == 0 or either
+ *    normal is all zero.  L = sqrt(L2), a1 = (N_i . d) / L, a2 = (N_j . d) / L.  If |a1| < |a2|:
+ *    (n1, n2, e, f3) = (N_j, N_i, -d, -a2), else (N_i, N_j, d, a1) -- the frame on the point whose normal
+ *    is closer to the line, as a comparison (no acos).  v = e x n1, vl2 = (vx vx + vy vy) + vz vz; vl2 == 0
+ *    skips the pair, else each component of v is divided by sqrt(vl2).  w = n1 x v, f2 = v . n2,
+ *    f1 = atan2(w . n2, n1 . n2).  Bins: b1 = clamp(floor(11 * ((f1 + pi) / (2 pi))), 0, 10), b2 the same
+ *    of (f2 + 1) / 2, b3 of (f3 + 1) / 2; pi is M_PI, 2 pi is 2.0 * M_PI, a NaN goes to bin 0.
+ * 3. SPFH_i[b] = (double)cnt_b * (100.0 / (double)c_i) with c_i the counted pairs of point i and cnt_b
+ *    those in bin b (b1 in 0-10, 11 + b2, 22 + b3); all 0 when c_i = 0.  Integer counts: no order.
+ * 4. FPFH (Open3D's form).  A[b] from +0; for the entries j of N_i in list order with j != i and
+ *    d2_ij > 0 (the list's d2): A[b] += (1.0 / d2_ij) * SPFH_j[b].  Per third (bins 0-10, 11-21, 22-32): T
+ *    = the sum of its A in ascending bin order from +0, A[b] = T > 0 ? A[b] * (100.0 / T) : 0.
+ *    FPFH_i[b] = A[b] + SPFH_i[b].
+ * Everything but atan2 is IEEE arithmetic as written; two calls give the same bits.
+ * Errors: ICP_E_ARG for a null required pointer, n == 0, n > INT_MAX, k < 3, k > 64, k > n (and the
+ * same for k_normals when normals == NULL), a non-finite viewpoint or given normal; ICP_E_RANGE for a
+ * non-finite coordinate.  Nothing is written to the outputs on an error. */
+#define ICP_FPFH_DIM 33
+int icp_fpfh(icp_ctx *ctx, const double *xyz, size_t n, const double *normals, int k_normals,
+             const double *viewpoint, int k, double *fpfh_out, double *spfh_out, double *normals_out);
+/* For every row a of fa (na x 33) the nearest row of fb (nb x 33): D(a, b) = sum over c = 0..32 of
+ * (fa[a][c] - fb[b][c])^2, summed from +0 in ascending c, the difference taken before the product;
+ * idx_out[a] = the LOWEST b among the minimisers of D (the first-minimum rule in 33 dimensions),
+ * dist_out[a] (nullable) its D.  A NaN D never wins: idx_out[a] = -1 (and dist_out[a] a NaN) when every
+ * D is a NaN.  Brute force: na * nb * 33 subtract-multiply-adds in fp64 -- meant for downsampled clouds.
+ * The mutual filter is two calls: keep a when idx_ba[idx_ab[a]] == a (icp_global_pose does that).
+ * ICP_E_ARG for a null required pointer, na == 0, nb == 0 or either above INT_MAX.
+ * icp_match_features_plan: how the search cuts fb for these sizes -- rows staged at a time (tile), rows a
+ * workgroup's range (chunk, a multiple of tile) and the number of ranges (splits); for tests and tools. */
+int icp_match_features(icp_ctx *ctx, const double *fa, size_t na, const double *fb, size_t nb,
+                       int32_t *idx_out, double *dist_out);
+int icp_match_features_plan(size_t na, size_t nb, int *tile, int *chunk, int *splits);
+/* A rigid pose q = R p + t from C putative pairs p_c -> q_c (both 3 x C column-major) by RANSAC over 3-pair
+ * samples.  Hypothesis h = 0 .. hypotheses - 1:
+ * 1. Draw.  z_r = splitmix64(seed + (3 h + r + 1) * 0x9E3779B97F4A7C15) for r = 0, 1, 2, where
+ *    splitmix64(x) is x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB;
+ *    x ^= x >> 31, all mod 2^64.  i0 = z_0 % C; i1 = z_1 % (C - 1), then + 1 if >= i0; i2 = z_2 % (C - 2),
+ *    then + 1 if >= min(i0, i1), then + 1 if >= max(i0, i1): three distinct pairs, a pure function of
+ *    (seed, h, C).
+ * 2. Edge check over the sample's index pairs (0, 1), (1, 2), (2, 0): with lp and lq the squared lengths
+ *    ((dx dx + dy dy) + dz dz) in p and in q, the hypothesis is kept when min(lp, lq) >= e2 * max(lp, lq)
+ *    for all three, e2 = edge_ratio * edge_ratio formed once.  A rejected hypothesis has count -1.
+ * 3. Pose.  Centroids ((x0 + x1) + x2) / 3 per axis; p' = p - mu_p, q' = q - mu_q; S = sum p' q'^T (nine
+ *    entries), d_caps = sum ((q'x q'x + q'y q'y) + q'z q'z) and sp likewise of p', each from +0 in the
+ *    order r = 0, 1, 2; R = the rotation of icp_horn_solve(S, mu_p, mu_q, d_caps, sp) -- the same code, on
+ *    the device; the scale is discarded: t = mu_q - R mu_p, rows as ((R0 m0 + R1 m1) + R2 m2).
+ * 4. Count: the pairs with (dx dx + dy dy) + dz dz <= max_dist * max_dist (formed once), d = (((R0 p0 +
+ *    R1 p1) + R2 p2) + t) - q per row: the iterations' arithmetic.
+ * 5. Winner: the largest count, ties to the lowest h, decided on the device by an unsigned 64-bit atomic
+ *    maximum over (count << 32) | (0xFFFFFFFF - h): an integer key, so no schedule changes the result.
+ * Outputs: R (row-major), t, *inliers (the winner's count), *best_h, *evaluated (nullable: how many
+ * passed the edge check), counts_out (nullable, one per hypothesis), mask_out (nullable, C: the
+ * winner's inliers).  Hypotheses run in batches of 65,536, so device memory does not grow with them.
+ * ICP_E_ARG: a null required pointer, C < 3, C > INT_MAX, hypotheses < 1 or >= 2^32, max_dist not finite
+ * or not > 0, edge_ratio outside [0, 1], a non-finite point.  ICP_E_DEGENERATE: no hypothesis passed the
+ * edge check (icp_last_error names H and the seed).  Nothing is written on an error. */
+int icp_ransac_pose(icp_ctx *ctx, const double *p_xyz, const double *q_xyz, size_t C, long long hypotheses,
+                    uint64_t seed, double max_dist, double edge_ratio, double R[9], double t[3],
+                    long long *inliers, long long *best_h, long long *evaluated, int32_t *counts_out,
+                    uint8_t *mask_out);
+/* The chain, bit for bit what the public calls give when chained by hand: both clouds through
+ * icp_voxel_downsample(voxel), each from its own origin; icp_fpfh of each with estimated normals
+ * (k_normals, no viewpoint) and k_fpfh; icp_match_features scene -> model, and with mutual != 0 model ->
+ * scene and the mutual filter; the surviving pairs in ascending (downsampled) scene index through
+ * icp_ransac_pose.  q = R p + t maps the scene onto the model: ready for icp_transform_scene(1, R, t).
+ * Zero fields of prm take defaults: k_normals 16, k_fpfh 32, hypotheses 100000 (Open3D's), max_dist
+ * 1.5 * voxel, edge_ratio 0.9; seed 0 is used as it is and mutual as given.  ICP_E_ARG, before anything
+ * runs: a null required pointer, nm or np outside [1, INT_MAX], voxel not finite or not > 0, and with the
+ * defaults filled in a k outside [3, 64], hypotheses outside [1, 2^32), max_dist not finite or not > 0,
+ * edge_ratio outside [0, 1].  ICP_E_TOO_FEW_POINTS: a downsampled cloud has fewer than max(k_normals, k_fpfh) points
+ * (before any descriptor kernel runs), or fewer than 3 matches survive.  rep is nullable. */
+typedef struct icp_global_params {
+    double voxel;
+    int k_normals, k_fpfh, mutual;
+    long long hypotheses;
+    uint64_t seed;
+    double max_dist, edge_ratio;
+} icp_global_params;
+typedef struct icp_global_report {
+    long long model_points, scene_points, matches, evaluated, inliers, best_h;
+} icp_global_report;
+int icp_global_pose(icp_ctx *ctx, const double *m_xyz, size_t nm, const double *p_xyz, size_t np,
+                    const icp_global_params *prm, double R[9], double t[3], icp_global_report *rep);
 
 /* ---- the ICP loop: GPU::ICP::find_corresponding_opti (src/GPU/gpu.cc:52-83) -- */
 /* Runs up to max_iter iterations on the resident clouds; stops after the iteration

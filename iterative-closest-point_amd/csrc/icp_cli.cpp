@@ -49,6 +49,16 @@
 //                      "[pyramid] level ..." line per level and a "[pyramid] total ..." line go to stderr.
 //                      With --estimate-normals the normals are estimated per level; excludes --normals
 //   --pyramid-iters K  iterations per level (default nb_iter)
+//   --global H         global registration first (icp_global_pose): both clouds downsampled to voxel H, FPFH
+//                      descriptors, mutual feature matches and a RANSAC pose, applied to the scene with
+//                      icp_transform_scene before the first run (so it is part of --write-transform's total);
+//                      for a scene that does not start near its answer.  One "[global] model ... scene ...
+//                      matches ... evaluated ... inliers ... hypothesis ..." line goes to stderr.  Combines
+//                      with every other option; under --pyramid it is the pyramid's initial pose
+//   --global-k K       neighbours of a descriptor (default 32), --global-normals-k K of a normal (default 16):
+//                      integers in [3, 64]
+//   --global-hyp N     RANSAC hypotheses (default 100000), --global-seed S their seed (default 0)
+//   --global-dist X    a pair counts as an inlier within X (default 1.5 H)
 //   --write-transform FILE  the total transform q = s R p + t (icp_get_transform) as a 4 x 4 matrix
 //                      [sR t; 0 0 0 1], four comma-separated rows of 6 significant digits
 //   --out PATH         output file (default output.txt, src/load.cc:71)
@@ -94,7 +104,8 @@ int main(int argc, char **argv)
         std::printf("       options: [--max-dist X] [--trim F] [--one-to-one] [--normals FILE | --estimate-normals K] [--write-normals FILE] "
                     "[--symmetric | --gicp [--gicp-epsilon E]] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
-                    "[--pyramid-iters K] [--write-transform FILE] [--out PATH]\n");
+                    "[--pyramid-iters K] [--global H [--global-k K] [--global-normals-k K] [--global-hyp N] [--global-seed S] "
+                    "[--global-dist X]] [--write-transform FILE] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -108,6 +119,8 @@ int main(int argc, char **argv)
     bool symmetric = false, gicp = false, one_to_one = false;
     const char *gicp_epsilon = nullptr;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
+    const char *global = nullptr, *global_k = nullptr, *global_nk = nullptr, *global_hyp = nullptr, *global_seed = nullptr;
+    const char *global_dist = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -133,6 +146,12 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--robust-k") && a + 1 < argc) robust_k = argv[++a];
         else if (!std::strcmp(argv[a], "--pyramid") && a + 1 < argc) pyramid = argv[++a];
         else if (!std::strcmp(argv[a], "--pyramid-iters") && a + 1 < argc) pyramid_iters = argv[++a];
+        else if (!std::strcmp(argv[a], "--global") && a + 1 < argc) global = argv[++a];
+        else if (!std::strcmp(argv[a], "--global-k") && a + 1 < argc) global_k = argv[++a];
+        else if (!std::strcmp(argv[a], "--global-normals-k") && a + 1 < argc) global_nk = argv[++a];
+        else if (!std::strcmp(argv[a], "--global-hyp") && a + 1 < argc) global_hyp = argv[++a];
+        else if (!std::strcmp(argv[a], "--global-seed") && a + 1 < argc) global_seed = argv[++a];
+        else if (!std::strcmp(argv[a], "--global-dist") && a + 1 < argc) global_dist = argv[++a];
         else if (!std::strcmp(argv[a], "--write-transform") && a + 1 < argc) write_transform = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -268,6 +287,45 @@ int main(int argc, char **argv)
         level_iter = (int)v;
     }
 
+    // the global registration's options: the voxel and what goes with it
+    icp_global_params gprm{};
+    gprm.mutual = 1;
+    if (!global && (global_k || global_nk || global_hyp || global_seed || global_dist)) {
+        std::fprintf(stderr, "[error] --global-k, --global-normals-k, --global-hyp, --global-seed and --global-dist need --global\n");
+        return -1;
+    }
+    if (global) {
+        char *end = nullptr;
+        gprm.voxel = std::strtod(global, &end);
+        if (end == global || *end || !(gprm.voxel > 0.0) || gprm.voxel > 1.7e308) {
+            std::fprintf(stderr, "[error] --global: %s is not a voxel size > 0\n", global);
+            return -1;
+        }
+        if (global_k && !parse_k("--global-k", global_k, &gprm.k_fpfh)) return -1;
+        if (global_nk && !parse_k("--global-normals-k", global_nk, &gprm.k_normals)) return -1;
+        if (global_hyp) {
+            gprm.hypotheses = std::strtoll(global_hyp, &end, 10);
+            if (end == global_hyp || *end || gprm.hypotheses < 1 || gprm.hypotheses >= (1LL << 32)) {
+                std::fprintf(stderr, "[error] --global-hyp: %s is not an integer in [1, 2^32)\n", global_hyp);
+                return -1;
+            }
+        }
+        if (global_seed) {
+            gprm.seed = std::strtoull(global_seed, &end, 10);
+            if (end == global_seed || *end || global_seed[0] == '-') {
+                std::fprintf(stderr, "[error] --global-seed: %s is not an unsigned integer\n", global_seed);
+                return -1;
+            }
+        }
+        if (global_dist) {
+            gprm.max_dist = std::strtod(global_dist, &end);
+            if (end == global_dist || *end || !(gprm.max_dist > 0.0) || gprm.max_dist > 1.7e308) {
+                std::fprintf(stderr, "[error] --global-dist: %s is not a distance > 0\n", global_dist);
+                return -1;
+            }
+        }
+    }
+
     size_t nm = 0, np = 0;
     double *m = load_or_exit(argv[1], &nm);
     double *p = load_or_exit(argv[2], &np);
@@ -385,6 +443,14 @@ int main(int argc, char **argv)
         icp_free(snrm);
         return 0;
     };
+    // --global: the pose of the full clouds' global registration, before anything is resident
+    double g_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, g_t[3] = {0, 0, 0};
+    if (global) {
+        icp_global_report rep{};
+        if ((rc = icp_global_pose(ctx, m, nm, p, np, &gprm, g_R, g_t, &rep)) != ICP_OK) return die("--global");
+        std::fprintf(stderr, "[global] model %lld scene %lld points, matches %lld, evaluated %lld, inliers %lld, hypothesis %lld\n",
+                     rep.model_points, rep.scene_points, rep.matches, rep.evaluated, rep.inliers, rep.best_h);
+    }
     if (pyramid) {
         // The calls of icp_amd.register_pyramid, in its order: every level's clouds first, then per
         // level (and for the full clouds) set_allow_unequal, set_model, [estimate], set_scene,
@@ -419,7 +485,9 @@ int main(int argc, char **argv)
         if (estimate && !k_fits("--estimate-normals", est_k, "model", &Level::m)) return -1;
         if (estimate_scene && !k_fits("--estimate-scene-normals", est_scene_k, "scene", &Level::p)) return -1;
         if (estimate && (rc = icp_set_metric(ctx, ICP_METRIC_POINT_TO_PLANE)) != ICP_OK) return die("--estimate-normals");
-        double s = 1.0, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
+        double s = 1.0, R[9], t[3]; // (the identity, or --global's pose)
+        std::memcpy(R, g_R, sizeof(R));
+        std::memcpy(t, g_t, sizeof(t));
         double *errs = (double *)std::calloc((size_t)(max_iter > level_iter ? max_iter : level_iter) + 1, sizeof(double));
         icp_result res{};
         for (size_t l = 0; l <= levels.size(); ++l) {
@@ -484,6 +552,8 @@ int main(int argc, char **argv)
         const int w = write_normals_file("--write-normals", icp_get_model_normals, nm, write_normals);
         if (w) return w;
     }
+    // (after the estimates: icp_estimate_scene_normals needs the scene as icp_set_scene received it)
+    if (global && (rc = icp_transform_scene(ctx, 1.0, g_R, g_t)) != ICP_OK) return die("--global");
     double *errs = (double *)std::calloc(max_iter > 0 ? (size_t)max_iter : 1, sizeof(double));
     icp_result res{};
     // each iteration's line as it ends (gpu.cc:65,77), from the engine's progress callback

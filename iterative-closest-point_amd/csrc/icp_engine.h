@@ -1,7 +1,8 @@
-// icp_engine.h — private to the engine's two translation units: icp_engine.hip (the context, the
-// model and scene set-up, the searches, the per-operation surface) and icp_run.hip (icp_run's
-// loops).  The context, the few types the two share, the error macros, the run path's knob table
-// and the declarations of the helpers one file calls in the other.  The helpers are icp::engine
+// icp_engine.h — private to the engine's translation units: icp_engine.hip (the context, the
+// model and scene set-up, the searches, the per-operation surface), icp_run.hip (icp_run's
+// loops) and icp_global.hip (global registration's four calls).  The context, the few types they
+// share, the error macros, the run path's knob table and the declarations of the helpers one file
+// calls in another.  The helpers are icp::engine
 // and hidden: the shared library exports the C ABI (include/icp_capi.h) and nothing of this.
 #pragma once
 
@@ -26,7 +27,7 @@ struct DevCloud {
 } // namespace engine
 } // namespace icp
 
-// (a private header: both files that include it work in these namespaces)
+// (a private header: the files that include it work in these namespaces)
 using namespace icp;
 using namespace icp::engine;
 
@@ -523,6 +524,13 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
                     bool slot_order = false, bool grid_seeded = false, const double *seedd = nullptr);
 int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop);
 int moments_phase(icp_ctx *ctx, size_t n);
+// icp_fpfh's grid half (icp_global.hip): a temporary grid of the n points in aos (device memory, 3 x n
+// col-major), built as icp_estimate_scene_normals builds the scene's and freed before the call
+// returns; rows = the points' double4 rows; with k_normals > 0 nrm = their normals by the estimator's
+// own kernels; row j of idx / d2 = launch_model_knn's k lists.  All four are the caller's device
+// arrays of n (rows, nrm) and n x k entries.  ICP_E_RANGE for a non-finite coordinate.  Synchronous.
+int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
+              int k, double4 *rows, double4 *nrm, int *idx, double *d2);
 
 // ---- icp_run.hip -----------------------------------------------------------------------
 int wait_flag(icp_ctx *ctx, const int *flag, int ticket);

@@ -1558,7 +1558,7 @@ static int estimate_normals(icp_ctx *ctx, const GridView &gv, const double4 *row
     if (degenerate) *degenerate = (long long)c[0];
     if (debug)
         std::fprintf(stderr, "[normals] %s=%zu k=%d degenerate=%llu second_scans=%llu full_scans=%llu candidates=%llu\n",
-                     label == "model" ? "nm" : "scene n", n, k, c[0], c[1], c[2], c[3]);
+                     label == "model" ? "nm" : (label == "scene" ? "scene n" : "cloud n"), n, k, c[0], c[1], c[2], c[3]);
     return ICP_OK;
 }
 
@@ -2052,6 +2052,55 @@ int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
     return ICP_OK;
 }
 
+// A temporary grid over n points that are not the model (icp_estimate_scene_normals, icp_fpfh): the
+// one place where it is built, so that both get what icp_set_model makes of a model's upload.  The
+// cloud comes as its SoA streams (x, y, z) and its interleaved copy (aos), both in device memory: the
+// box and the finiteness check from aos (ICP_E_RANGE names `word`), the grid's size from the box, the
+// double4 rows, the build.  Everything is freed with the object; extra: one more allocation of the
+// caller's that goes with it.
+struct TempGrid {
+    void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // rows, offsets, points, fp32 image, sort scratch
+    void *extra = nullptr;
+    double4 *rows = nullptr;
+    GridView gv{};
+    TempGrid() = default;
+    TempGrid(const TempGrid &) = delete;
+    TempGrid &operator=(const TempGrid &) = delete;
+    ~TempGrid()
+    {
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+        if (extra) (void)hipFree(extra);
+    }
+};
+
+static int temp_grid_build(icp_ctx *ctx, const std::string &who, const std::string &word, const double *x, const double *y,
+                           const double *z, const double *aos, size_t n, TempGrid &tg)
+{
+    TRY(ensure_model_stats(ctx));
+    launch_model_stats(aos, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
+    LAUNCHCHK(word + "_stats");
+    HIPCHK(hipMemcpyAsync(ctx->h_mstat, ctx->mstat_out, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, who + ": the " + word + " has non-finite coordinates");
+    const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
+    const long long ncell = grid_cells(gp);
+    const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
+    HIPCHK(hipMalloc(&tg.p[0], sizeof(double4) * n));                 // the cloud's rows
+    HIPCHK(hipMalloc(&tg.p[1], sizeof(int) * ((size_t)ncell + 1)));   // the grid's offsets
+    HIPCHK(hipMalloc(&tg.p[2], sizeof(double4) * n));                 // its points
+    HIPCHK(hipMalloc(&tg.p[3], sizeof(float4) * n));                  // their fp32 image
+    HIPCHK(hipMalloc(&tg.p[4], gbytes ? gbytes : 1));                 // the build's sort scratch
+    tg.rows = (double4 *)tg.p[0];
+    launch_make_aos4(x, y, z, (int)n, tg.rows, ctx->st);
+    if (launch_grid_build(x, y, z, tg.rows, (int)n, gp, tg.p[4], gbytes, (int *)tg.p[1], (double4 *)tg.p[2], (float4 *)tg.p[3],
+                          ctx->st) != 0)
+        return fail(ctx, ICP_E_HIP, who + ": grid build: radix sort failed");
+    LAUNCHCHK(word + "_grid_build");
+    tg.gv = grid_view_of(gp, (const int *)tg.p[1], (const double4 *)tg.p[2], (const float4 *)tg.p[3]);
+    return ICP_OK;
+}
+
 int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
 {
     if (!ctx) return ICP_E_ARG;
@@ -2074,40 +2123,13 @@ int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, lon
         LAUNCHCHK("scene_to_file_order");
         P = &ctx->s_tmp;
     }
-    TRY(ensure_model_stats(ctx));
     TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
     launch_soa_to_aos(P->x, P->y, P->z, n, ctx->stage, ctx->st);
-    launch_model_stats(ctx->stage, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
-    LAUNCHCHK("scene_stats");
-    HIPCHK(hipMemcpyAsync(ctx->h_mstat, ctx->mstat_out, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, who + ": the scene has non-finite coordinates");
-    const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
-    const long long ncell = grid_cells(gp);
-    const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
-    // the temporary grid and rows: freed before the call returns, whatever it returns
-    struct Temp {
-        void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Temp()
-        {
-            for (void *q : p)
-                if (q) (void)hipFree(q);
-        }
-    } tmp;
-    HIPCHK(hipMalloc(&tmp.p[0], sizeof(double4) * n));                 // the scene's rows
-    HIPCHK(hipMalloc(&tmp.p[1], sizeof(int) * ((size_t)ncell + 1)));   // the grid's offsets
-    HIPCHK(hipMalloc(&tmp.p[2], sizeof(double4) * n));                 // its points
-    HIPCHK(hipMalloc(&tmp.p[3], sizeof(float4) * n));                  // their fp32 image
-    HIPCHK(hipMalloc(&tmp.p[4], gbytes ? gbytes : 1));                 // the build's sort scratch
-    HIPCHK(hipMalloc(&tmp.p[5], sizeof(double4) * n));                 // the normals' rows
-    double4 *rows = (double4 *)tmp.p[0], *nrm = (double4 *)tmp.p[5];
-    launch_make_aos4(P->x, P->y, P->z, (int)n, rows, ctx->st);
-    if (launch_grid_build(P->x, P->y, P->z, rows, (int)n, gp, tmp.p[4], gbytes, (int *)tmp.p[1], (double4 *)tmp.p[2],
-                          (float4 *)tmp.p[3], ctx->st) != 0)
-        return fail(ctx, ICP_E_HIP, who + ": grid build: radix sort failed");
-    LAUNCHCHK("scene_grid_build");
-    const GridView gv = grid_view_of(gp, (const int *)tmp.p[1], (const double4 *)tmp.p[2], (const float4 *)tmp.p[3]);
-    TRY(estimate_normals(ctx, gv, rows, n, k, grid_budget_for(n), viewpoint, nrm, "scene", degenerate, [&] {
+    TempGrid tg; // (freed before the call returns, whatever it returns)
+    TRY(temp_grid_build(ctx, who, "scene", P->x, P->y, P->z, ctx->stage, n, tg));
+    HIPCHK(hipMalloc(&tg.extra, sizeof(double4) * n)); // the normals' rows
+    double4 *nrm = (double4 *)tg.extra;
+    TRY(estimate_normals(ctx, tg.gv, tg.rows, n, k, grid_budget_for(n), viewpoint, nrm, "scene", degenerate, [&] {
         ctx->has_scene_normals = false; // (until the new ones are complete)
         ctx->sn_slot_valid = false;
         TRY(grow_cloud(ctx, ctx->sn, n, false));
@@ -2812,3 +2834,28 @@ int icp_reset_stats(icp_ctx *ctx)
 }
 
 } // extern "C"
+
+namespace icp {
+namespace engine {
+
+int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
+              int k, double4 *rows, double4 *nrm, int *idx, double *d2)
+{
+    TempGrid tg; // (freed before the call returns, whatever it returns)
+    HIPCHK(hipMalloc(&tg.extra, sizeof(double) * 3 * n)); // the cloud's SoA streams
+    double *x = (double *)tg.extra, *y = x + n, *z = y + n;
+    launch_aos_to_soa(aos, n, x, y, z, ctx->st);
+    TRY(temp_grid_build(ctx, who, "cloud", x, y, z, aos, n, tg));
+    const int budget = grid_budget_for(n);
+    if (k_normals > 0)
+        TRY(estimate_normals(ctx, tg.gv, tg.rows, n, k_normals, budget, viewpoint, nrm, "cloud", nullptr,
+                             [] { return (int)ICP_OK; }));
+    launch_model_knn(tg.gv, tg.rows, (int)n, k, budget, idx, d2, ctx->st);
+    LAUNCHCHK("cloud_knn");
+    HIPCHK(hipMemcpyAsync(rows, tg.rows, sizeof(double4) * n, hipMemcpyDeviceToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st)); // (the grid is freed on return)
+    return ICP_OK;
+}
+
+} // namespace engine
+} // namespace icp

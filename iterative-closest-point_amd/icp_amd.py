@@ -38,7 +38,7 @@ ICP_E_RCCL = -6
 ICP_E_NO_DEVICE = -7
 ICP_E_IO = -8
 ICP_E_RANGE = -9
-ICP_E_DEGENERATE = -10  # point-to-plane: an iteration's 6 x 6 system is singular
+ICP_E_DEGENERATE = -10  # point-to-plane: an iteration's 6 x 6 system is singular; ransac_pose: no sample kept
 
 NN_CERTIFIED = 0
 NN_FP64 = 1
@@ -84,6 +84,7 @@ EXPORTED = [
     "icp_set_plane_symmetric", "icp_set_scene_normals", "icp_set_scene_normals_device", "icp_get_scene_normals",
     "icp_estimate_scene_normals", "icp_set_plane_to_plane",
     "icp_set_one_to_one",
+    "icp_fpfh", "icp_match_features", "icp_match_features_plan", "icp_ransac_pose", "icp_global_pose",
 ]
 
 
@@ -110,6 +111,21 @@ class Stats(C.Structure):
                 ("bundle_builds_in_run", C.c_longlong), ("run_bundle_searches", C.c_longlong),
                 ("run_grid_searches", C.c_longlong), ("run_certified", C.c_longlong),
                 ("run_walked", C.c_longlong), ("run_path_bits", C.c_ulonglong)]
+
+
+class GlobalParams(C.Structure):
+    """icp_global_params: zero fields take the header's defaults."""
+    _fields_ = [("voxel", C.c_double), ("k_normals", C.c_int), ("k_fpfh", C.c_int), ("mutual", C.c_int),
+                ("hypotheses", C.c_longlong), ("seed", C.c_uint64), ("max_dist", C.c_double),
+                ("edge_ratio", C.c_double)]
+
+
+class GlobalReport(C.Structure):
+    _fields_ = [(k, C.c_longlong) for k in ("model_points", "scene_points", "matches", "evaluated", "inliers",
+                                            "best_h")]
+
+
+FPFH_DIM = 33
 
 
 class BundleAudit(C.Structure):
@@ -226,6 +242,14 @@ def lib() -> C.CDLL:
         L.icp_set_plane_to_plane.argtypes = [vp, C.c_double]
     if hasattr(L, "icp_set_one_to_one"):
         L.icp_set_one_to_one.argtypes = [vp, C.c_int]
+    if hasattr(L, "icp_fpfh"):
+        ip, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.icp_fpfh.argtypes = [vp, dp, sz, dp, C.c_int, dp, C.c_int, dp, dp, dp]
+        L.icp_match_features.argtypes = [vp, dp, sz, dp, sz, ip, dp]
+        L.icp_match_features_plan.argtypes = [sz, sz, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.icp_ransac_pose.argtypes = [vp, dp, dp, sz, C.c_longlong, C.c_uint64, C.c_double, C.c_double, dp, dp,
+                                      llp, llp, llp, ip, C.POINTER(C.c_uint8)]
+        L.icp_global_pose.argtypes = [vp, dp, sz, dp, sz, C.POINTER(GlobalParams), dp, dp, C.POINTER(GlobalReport)]
     _lib = L
     return L
 
@@ -596,6 +620,82 @@ class Context:
         self._check(lib().icp_estimate_scene_normals(self._h, int(k), None if v is None else _dp(v), C.byref(deg)))
         return int(deg.value)
 
+    def fpfh(self, xyz, k: int = 32, normals=None, k_normals: int = 16, viewpoint=None, spfh: bool = False,
+             return_normals: bool = False):
+        """icp_fpfh: the 33-bin FPFH descriptors of a cloud from its k-neighbourhoods; the normals are
+        the given ones or estimated from k_normals neighbours -> fpfh (n, 33), or a tuple with the SPFH
+        rows (spfh) and the normals used (return_normals) behind it."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        nr = None if normals is None else _cloud(normals)
+        if nr is not None and nr.shape[0] != n:
+            raise ValueError("one normal per point")
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        out = np.empty((max(n, 1), FPFH_DIM))
+        sp = np.empty((max(n, 1), FPFH_DIM)) if spfh else None
+        no = np.empty((max(n, 1), 3)) if return_normals else None
+        self._check(lib().icp_fpfh(self._h, _dp(xyz), n, None if nr is None else _dp(nr), int(k_normals),
+                                   None if v is None else _dp(v), int(k), _dp(out), None if sp is None else _dp(sp),
+                                   None if no is None else _dp(no)))
+        res = (out[:n],) + ((sp[:n],) if spfh else ()) + ((no[:n],) if return_normals else ())
+        return res[0] if len(res) == 1 else res
+
+    def match_features(self, fa, fb, distances: bool = False):
+        """icp_match_features: for every row of fa the nearest row of fb (the lowest index among the
+        minimisers; -1 when every distance is a NaN) -> idx (na,) int32, or (idx, D) with distances."""
+        fa = np.ascontiguousarray(fa, dtype=np.float64)
+        fb = np.ascontiguousarray(fb, dtype=np.float64)
+        if fa.ndim != 2 or fb.ndim != 2 or fa.shape[1] != FPFH_DIM or fb.shape[1] != FPFH_DIM:
+            raise ValueError("descriptors are (n, 33) float64 arrays")
+        idx = np.empty(max(fa.shape[0], 1), dtype=np.int32)
+        d = np.empty(max(fa.shape[0], 1)) if distances else None
+        self._check(lib().icp_match_features(self._h, _dp(fa), fa.shape[0], _dp(fb), fb.shape[0],
+                                             idx.ctypes.data_as(C.POINTER(C.c_int32)), _dp(d) if distances else None))
+        idx = idx[:fa.shape[0]]
+        return (idx, d[:fa.shape[0]]) if distances else idx
+
+    def ransac_pose(self, p, q, hypotheses: int = 100000, seed: int = 0, max_dist: float = 1.0,
+                    edge_ratio: float = 0.9, counts: bool = False, mask: bool = False) -> dict:
+        """icp_ransac_pose: the rigid pose q = R p + t with the most pairs p_c -> q_c within max_dist among
+        `hypotheses` 3-pair samples of `seed` -> dict(R (3, 3), t, inliers, best_h, evaluated, and with
+        counts / mask: counts (hypotheses,) int32 with -1 for a rejected sample, mask (C,) bool)."""
+        p = _cloud(p)
+        q = _cloud(q)
+        if p.shape[0] != q.shape[0]:
+            raise ValueError("one q per p")
+        H = int(hypotheses)
+        R = np.empty(9)
+        t = np.empty(3)
+        inl, bh, ev = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        cn = np.empty(max(H, 1), dtype=np.int32) if counts and 0 < H < 2 ** 32 else None
+        mk = np.empty(max(p.shape[0], 1), dtype=np.uint8) if mask else None
+        self._check(lib().icp_ransac_pose(self._h, _dp(p), _dp(q), p.shape[0], H, int(seed), float(max_dist),
+                                          float(edge_ratio), _dp(R), _dp(t), C.byref(inl), C.byref(bh), C.byref(ev),
+                                          None if cn is None else cn.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8))))
+        out = {"R": R.reshape(3, 3), "t": t, "inliers": int(inl.value), "best_h": int(bh.value),
+               "evaluated": int(ev.value)}
+        if cn is not None:
+            out["counts"] = cn[:H]
+        if mk is not None:
+            out["mask"] = mk[:p.shape[0]].astype(bool)
+        return out
+
+    def global_pose(self, m, p, voxel: float, k_normals: int = 0, k_fpfh: int = 0, mutual: bool = True,
+                    hypotheses: int = 0, seed: int = 0, max_dist: float = 0.0, edge_ratio: float = 0.0):
+        """icp_global_pose: downsample both clouds, FPFH, (mutual) feature matches, RANSAC; zeros take the
+        header's defaults -> (R (3, 3), t, report dict) with q = R p + t mapping the scene onto the model."""
+        m = _cloud(m)
+        p = _cloud(p)
+        prm = GlobalParams(float(voxel), int(k_normals), int(k_fpfh), 1 if mutual else 0, int(hypotheses), int(seed),
+                           float(max_dist), float(edge_ratio))
+        rep = GlobalReport()
+        R = np.empty(9)
+        t = np.empty(3)
+        self._check(lib().icp_global_pose(self._h, _dp(m), m.shape[0], _dp(p), p.shape[0], C.byref(prm), _dp(R), _dp(t),
+                                          C.byref(rep)))
+        return R.reshape(3, 3), t, {k: int(getattr(rep, k)) for k, _ in GlobalReport._fields_}
+
     def inliers(self):
         """The last gate of the last gated run() -> (mask: bool (np_local,), caller's order; K over all ranks)."""
         mask = np.zeros(self._np_local, dtype=np.uint8)
@@ -845,6 +945,38 @@ def register_pyramid(ctx: Context, m, p, voxels, max_iter: int, level_iter: int 
     finally:
         ctx.set_allow_unequal(allow)
     return res, pose, records
+
+
+def match_plan(na: int, nb: int):
+    """icp_match_features_plan -> (tile, chunk, splits): the rows of fb staged at a time, the rows of a
+    workgroup's range and the number of ranges for these sizes."""
+    tile, chunk, splits = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib().icp_match_features_plan(int(na), int(nb), C.byref(tile), C.byref(chunk), C.byref(splits))
+    if rc != ICP_OK:
+        raise ICPError(rc, strerror(rc))
+    return tile.value, chunk.value, splits.value
+
+
+def register_global(ctx: Context, m, p, voxel: float, max_iter: int, threshold: float = 1e-5,
+                    estimate_normals: int | None = None, estimate_scene_normals: int | None = None, **global_opts):
+    """Registration of a scene p that need not start near the model m (the icp-gpu CLI's --global makes
+    the same calls in the same order): global_pose(m, p, voxel, **global_opts), set_model / set_scene of
+    the full clouds, the requested normal estimates (before the scene moves: estimate_scene_normals needs
+    the scene as given), transform_scene by the global pose, run(max_iter, threshold) with the context's
+    own settings, transform().
+    -> (the run's Result, its error trace, the total (s, R, t), the global pose (R, t), its report)."""
+    m = _cloud(m)
+    p = _cloud(p)
+    R0, t0, report = ctx.global_pose(m, p, voxel, **global_opts)
+    ctx.set_model(m)
+    if estimate_normals is not None:
+        ctx.estimate_model_normals(estimate_normals)
+    ctx.set_scene(p)
+    if estimate_scene_normals is not None:
+        ctx.estimate_scene_normals(estimate_scene_normals)
+    ctx.transform_scene(1.0, R0, t0)
+    res, errs = ctx.run(max_iter, threshold)
+    return res, errs, ctx.transform(), (R0, t0), report
 
 
 @dataclass
