@@ -551,6 +551,62 @@ int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel
 int icp_voxel_downsample_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double voxel, const double *origin,
                                 double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out);
 
+/* ---- outlier removal: the statistical and the radius filter ------------------ */
+/* What a raw scan needs before normals, descriptors, a downsample or icp_run: its isolated returns
+ * (flying pixels, dust, multipath) removed.  PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval and
+ * Open3D's remove_statistical_outlier / remove_radius_outlier, over a temporary grid of the cloud built
+ * as icp_estimate_scene_normals builds the scene's (its device memory and the filters' own are scratch
+ * of the context, kept for the next filter call and freed with the context).  xyz: n points,
+ * 3 x n column-major like a cloud.  d2 between two points is (dx*dx + dy*dy) + dz*dz in fp64 exactly
+ * as written.
+ *
+ * icp_filter_statistical(k, std_ratio):
+ * 1. Neighbour list.  L_j is the first k + 1 indices i in ascending (d2, i) order of point j's distances
+ *    to every point of the cloud: icp_model_knn's rule 1 with k + 1, the same search; the point itself is
+ *    a candidate like any other.
+ * 2. Mean distance.  dbar_j = (sum over the k + 1 entries of L_j, in list order from +0, of sqrt(d2)) / k:
+ *    PCL's mean over the k other points, the self entry adding 0.  With k + 2 or more equal points every
+ *    entry is 0 and dbar_j = 0.  mean_dist_out (nullable, n) = dbar.
+ * 3. Moments, two passes: mu = S(dbar) / n, then sigma = sqrt(S((dbar_j - mu) * (dbar_j - mu)) / (n - 1)).
+ *    S sums a sequence of L terms in an order that depends on L alone: the sequence is cut into chunks of
+ *    1,024; in a chunk 64 partial sums start from +0 and take the terms l, l + 64, l + 128, ... in order
+ *    and are combined by the butterfly a_l += a_(l xor 32), 16, 8, 4, 2, 1; a single chunk's sum is S;
+ *    otherwise the chunk sums in chunk order are a sequence of ceil(L / 1024) terms and S is that
+ *    sequence's S.  No floating-point atomics: two calls, and the host and the device form, give the
+ *    same bits.
+ * 4. T = mu + std_ratio * sigma (the product rounded, then the sum).  Point j is kept iff dbar_j <= T.
+ * 5. stats_out (nullable) = (mu, sigma, T).
+ *
+ * icp_filter_radius(radius, min_neighbors):
+ * 1. c_j = #{ i : d2(j, i) <= radius * radius }, the product taken once on the host.  The point itself is
+ *    counted, so c_j >= 1.
+ * 2. Point j is kept iff c_j > min_neighbors: at least min_neighbors OTHER points within the radius
+ *    (PCL's and Open3D's rule).
+ * 3. count_out (nullable, n) = c_j, the full counts.  Without it the scan of a point may stop at
+ *    min_neighbors + 1; the mask is the same either way.
+ *
+ * Both: the kept points go to out_xyz (nullable, room for n points) in their input order, mask_out
+ * (nullable, n) holds 1 for a kept point and 0 for a removed one, *n_out (required) the number kept; 0
+ * is a valid result and ICP_OK.  The calls are synchronous, write their outputs only once everything
+ * has run, and touch neither the resident clouds, the normals nor any setting: an icp_run after one is
+ * bit-identical to that run on a fresh context.  The device forms take xyz, out_xyz, mask_out and the
+ * per-point mean_dist_out / count_out in device memory, read like icp_set_model_device's array (after
+ * the work of any stream; valid until the call returns); n_out and stats_out stay host pointers.
+ * Errors (icp_last_error names the value; nothing has run and nothing is written): ICP_E_ARG for a null
+ * xyz or n_out, n == 0 or n > INT_MAX, k outside [2, 63] (the list of k + 1 entries must fit
+ * icp_model_knn's 3 to 64), k + 1 > n, std_ratio negative or not finite, radius not finite or <= 0,
+ * min_neighbors < 0; ICP_E_RANGE for a non-finite coordinate. */
+int icp_filter_statistical(icp_ctx *ctx, const double *xyz, size_t n, int k, double std_ratio,
+                           double *out_xyz, uint8_t *mask_out, size_t *n_out, double *mean_dist_out,
+                           double stats_out[3]);
+int icp_filter_statistical_device(icp_ctx *ctx, const double *xyz_dev, size_t n, int k, double std_ratio,
+                                  double *out_xyz_dev, uint8_t *mask_out_dev, size_t *n_out,
+                                  double *mean_dist_out_dev, double stats_out[3]);
+int icp_filter_radius(icp_ctx *ctx, const double *xyz, size_t n, double radius, int min_neighbors,
+                      double *out_xyz, uint8_t *mask_out, size_t *n_out, int32_t *count_out);
+int icp_filter_radius_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double radius, int min_neighbors,
+                             double *out_xyz_dev, uint8_t *mask_out_dev, size_t *n_out, int32_t *count_out_dev);
+
 /* ---- global registration: FPFH descriptors, feature matches, a RANSAC pose ---- */
 /* What a scene that does NOT start near its answer needs before icp_run: a pose from local shape
  * descriptors (Rusu, Blodow and Beetz, "Fast Point Feature Histograms (FPFH) for 3D Registration", ICRA

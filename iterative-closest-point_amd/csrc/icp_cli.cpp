@@ -59,10 +59,22 @@
 //                      integers in [3, 64]
 //   --global-hyp N     RANSAC hypotheses (default 100000), --global-seed S their seed (default 0)
 //   --global-dist X    a pair counts as an inlier within X (default 1.5 H)
+//   --sor K,RATIO      statistical outlier removal (icp_filter_statistical) of the model and of the scene right
+//                      after loading, before --global, --pyramid and any normal estimation: a point stays when
+//                      its mean distance to its K nearest neighbours (2 <= K <= 63) is at most mu + RATIO sigma
+//                      of those means (RATIO >= 0).  The clouds' sizes will differ afterwards, so it needs
+//                      --allow-unequal.  Rows of --normals / --scene-normals files follow their clouds: the rows
+//                      of removed points are dropped.  One "[sor] model|scene N points, kept M, mu .. sigma .. T .."
+//                      line per cloud goes to stderr.  The output file holds the kept scene points as
+//                      registered; --write-transform is unchanged, so the pose can be applied to the full scan
+//   --ror RADIUS,MIN   radius outlier removal (icp_filter_radius), likewise and after --sor when both are given:
+//                      a point stays when at least MIN other points lie within RADIUS (RADIUS > 0, MIN >= 0);
+//                      one "[ror] model|scene N points, kept M" line per cloud
 //   --write-transform FILE  the total transform q = s R p + t (icp_get_transform) as a 4 x 4 matrix
 //                      [sR t; 0 0 0 1], four comma-separated rows of 6 significant digits
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -105,7 +117,7 @@ int main(int argc, char **argv)
                     "[--symmetric | --gicp [--gicp-epsilon E]] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--global H [--global-k K] [--global-normals-k K] [--global-hyp N] [--global-seed S] "
-                    "[--global-dist X]] [--write-transform FILE] [--out PATH]\n");
+                    "[--global-dist X]] [--sor K,RATIO] [--ror RADIUS,MIN] [--write-transform FILE] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -120,7 +132,7 @@ int main(int argc, char **argv)
     const char *gicp_epsilon = nullptr;
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     const char *global = nullptr, *global_k = nullptr, *global_nk = nullptr, *global_hyp = nullptr, *global_seed = nullptr;
-    const char *global_dist = nullptr;
+    const char *global_dist = nullptr, *sor = nullptr, *ror = nullptr;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -152,6 +164,8 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--global-hyp") && a + 1 < argc) global_hyp = argv[++a];
         else if (!std::strcmp(argv[a], "--global-seed") && a + 1 < argc) global_seed = argv[++a];
         else if (!std::strcmp(argv[a], "--global-dist") && a + 1 < argc) global_dist = argv[++a];
+        else if (!std::strcmp(argv[a], "--sor") && a + 1 < argc) sor = argv[++a];
+        else if (!std::strcmp(argv[a], "--ror") && a + 1 < argc) ror = argv[++a];
         else if (!std::strcmp(argv[a], "--write-transform") && a + 1 < argc) write_transform = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -326,6 +340,38 @@ int main(int argc, char **argv)
         }
     }
 
+    // the outlier filters' options: two values each, and the clouds' sizes will differ afterwards
+    int sor_k = 0, ror_min = 0;
+    double sor_ratio = 0.0, ror_radius = 0.0;
+    if (sor) {
+        char *end = nullptr, *end2 = nullptr;
+        const long v = std::strtol(sor, &end, 10);
+        if (end != sor && *end == ',') sor_ratio = std::strtod(end + 1, &end2);
+        if (end == sor || *end != ',' || end2 == end + 1 || *end2 || v < 2 || v > 63 || !(sor_ratio >= 0.0) ||
+            sor_ratio > 1.7e308) {
+            std::fprintf(stderr, "[error] --sor: %s is not K,RATIO with an integer K in [2, 63] and a RATIO >= 0\n", sor);
+            return -1;
+        }
+        sor_k = (int)v;
+    }
+    if (ror) {
+        char *end = nullptr, *end2 = nullptr;
+        ror_radius = std::strtod(ror, &end);
+        long v = -1;
+        if (end != ror && *end == ',') v = std::strtol(end + 1, &end2, 10);
+        if (end == ror || *end != ',' || end2 == end + 1 || *end2 || !(ror_radius > 0.0) || ror_radius > 1.7e308 || v < 0 ||
+            v > 2147483647L) {
+            std::fprintf(stderr, "[error] --ror: %s is not RADIUS,MIN with a RADIUS > 0 and an integer MIN >= 0\n", ror);
+            return -1;
+        }
+        ror_min = (int)v;
+    }
+    if ((sor || ror) && !allow_unequal) {
+        std::fprintf(stderr, "[error] --sor and --ror remove points from each cloud on its own, so the clouds' sizes will "
+                             "differ: they need --allow-unequal\n");
+        return -1;
+    }
+
     size_t nm = 0, np = 0;
     double *m = load_or_exit(argv[1], &nm);
     double *p = load_or_exit(argv[2], &np);
@@ -443,6 +489,48 @@ int main(int argc, char **argv)
         icp_free(snrm);
         return 0;
     };
+    // --sor, then --ror: each cloud on its own, right after loading; a normals file's rows follow the mask
+    if (sor || ror) {
+        const auto filter_cloud = [&](const char *word, double *xyz, size_t *n, double *rows) {
+            for (int pass = 0; pass < 2; ++pass) {
+                if (!(pass == 0 ? sor : ror)) continue;
+                std::vector<double> kept_xyz(3 * *n);
+                std::vector<uint8_t> mask(*n);
+                size_t kept = 0;
+                double st[3] = {0.0, 0.0, 0.0};
+                rc = pass == 0 ? icp_filter_statistical(ctx, xyz, *n, sor_k, sor_ratio, kept_xyz.data(), mask.data(), &kept,
+                                                        nullptr, st)
+                               : icp_filter_radius(ctx, xyz, *n, ror_radius, ror_min, kept_xyz.data(), mask.data(), &kept,
+                                                   nullptr);
+                if (rc != ICP_OK) return false;
+                if (pass == 0)
+                    std::fprintf(stderr, "[sor] %s %zu points, kept %zu, mu %g sigma %g T %g\n", word, *n, kept, st[0], st[1],
+                                 st[2]);
+                else std::fprintf(stderr, "[ror] %s %zu points, kept %zu\n", word, *n, kept);
+                std::memcpy(xyz, kept_xyz.data(), sizeof(double) * 3 * kept);
+                if (rows) {
+                    size_t w = 0;
+                    for (size_t j = 0; j < *n; ++j)
+                        if (mask[j]) {
+                            for (int a = 0; a < 3; ++a) rows[3 * w + a] = rows[3 * j + a];
+                            ++w;
+                        }
+                }
+                *n = kept;
+                if (kept == 0) break; // (the size check below answers)
+            }
+            return true;
+        };
+        if (!filter_cloud("model", m, &nm, nrm)) return die("--sor / --ror (model)");
+        if (!filter_cloud("scene", p, &np, snrm)) return die("--sor / --ror (scene)");
+        if (normals) nn = nm;
+        if (scene_normals) nsn = np;
+        if (np < 4 || nm < 1) {
+            std::fprintf(stderr, "[error] --sor / --ror left %zu model and %zu scene points: need at least 4 point pairs\n", nm,
+                         np);
+            return -1;
+        }
+    }
     // --global: the pose of the full clouds' global registration, before anything is resident
     double g_R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, g_t[3] = {0, 0, 0};
     if (global) {

@@ -355,6 +355,11 @@ struct icp_ctx {
     double *vox_io = nullptr;
     int *vox_cnt = nullptr;
     size_t vox_buf_cap = 0, vox_io_cap = 0, vox_cnt_cap = 0;
+    // icp_filter_* (icp_filter.hip): scratch of those calls alone, kept between calls (a call's dozen
+    // allocations cost as much as its kernels) -- the temporary grid's arrays (filt_grid) and the
+    // filters' own arrays and staged clouds (filt_buf)
+    char *filt_grid = nullptr, *filt_buf = nullptr;
+    size_t filt_grid_cap = 0, filt_buf_cap = 0;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
@@ -531,6 +536,32 @@ int moments_phase(icp_ctx *ctx, size_t n);
 // arrays of n (rows, nrm) and n x k entries.  ICP_E_RANGE for a non-finite coordinate.  Synchronous.
 int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
               int k, double4 *rows, double4 *nrm, int *idx, double *d2);
+
+// A temporary grid over a cloud that is not the model, freed with the object; extra: one more allocation
+// of the builder's that goes with it.  (A grid built into the context's filt_grid owns nothing.)
+struct TempGrid {
+    void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // rows, offsets, points, fp32 image, sort scratch
+    void *extra = nullptr;
+    double4 *rows = nullptr;
+    GridView gv{};
+    TempGrid() = default;
+    TempGrid(const TempGrid &) = delete;
+    TempGrid &operator=(const TempGrid &) = delete;
+    ~TempGrid()
+    {
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+        if (extra) (void)hipFree(extra);
+    }
+};
+
+// The grid alone: tg = cloud_knn's temporary grid of the n points in aos, *budget = its cell budget.  soa
+// null: its memory is tg's own; else (the outlier filters, icp_filter.hip) soa = 3 n doubles of the
+// caller's for the SoA streams and the grid's arrays live in the context's filt_grid, kept for the next
+// call.  Asynchronous on the context's stream but for the box's read-back; the caller synchronises
+// before tg goes.  ICP_E_RANGE for a non-finite coordinate.
+int cloud_grid(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, TempGrid &tg, int *budget,
+               double *soa = nullptr);
 
 // ---- icp_run.hip -----------------------------------------------------------------------
 int wait_flag(icp_ctx *ctx, const int *flag, int ticket);

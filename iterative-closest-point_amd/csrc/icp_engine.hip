@@ -1300,7 +1300,8 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
                     (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
-                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->trim_keys,
+                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->filt_grid, (void *)ctx->filt_buf,
+                    (void *)ctx->trim_keys,
                     (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state,
                     (void *)ctx->uniq_best})
         if (p) (void)hipFree(p);
@@ -2056,26 +2057,10 @@ int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
 // one place where it is built, so that both get what icp_set_model makes of a model's upload.  The
 // cloud comes as its SoA streams (x, y, z) and its interleaved copy (aos), both in device memory: the
 // box and the finiteness check from aos (ICP_E_RANGE names `word`), the grid's size from the box, the
-// double4 rows, the build.  Everything is freed with the object; extra: one more allocation of the
-// caller's that goes with it.
-struct TempGrid {
-    void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // rows, offsets, points, fp32 image, sort scratch
-    void *extra = nullptr;
-    double4 *rows = nullptr;
-    GridView gv{};
-    TempGrid() = default;
-    TempGrid(const TempGrid &) = delete;
-    TempGrid &operator=(const TempGrid &) = delete;
-    ~TempGrid()
-    {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-        if (extra) (void)hipFree(extra);
-    }
-};
-
+// double4 rows, the build.  Everything is freed with the object (TempGrid, icp_engine.h); with `kept` the
+// five arrays are parts of the context's filt_grid instead, which stays for the next call.
 static int temp_grid_build(icp_ctx *ctx, const std::string &who, const std::string &word, const double *x, const double *y,
-                           const double *z, const double *aos, size_t n, TempGrid &tg)
+                           const double *z, const double *aos, size_t n, TempGrid &tg, bool kept = false)
 {
     TRY(ensure_model_stats(ctx));
     launch_model_stats(aos, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
@@ -2086,18 +2071,30 @@ static int temp_grid_build(icp_ctx *ctx, const std::string &who, const std::stri
     const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
     const long long ncell = grid_cells(gp);
     const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
-    HIPCHK(hipMalloc(&tg.p[0], sizeof(double4) * n));                 // the cloud's rows
-    HIPCHK(hipMalloc(&tg.p[1], sizeof(int) * ((size_t)ncell + 1)));   // the grid's offsets
-    HIPCHK(hipMalloc(&tg.p[2], sizeof(double4) * n));                 // its points
-    HIPCHK(hipMalloc(&tg.p[3], sizeof(float4) * n));                  // their fp32 image
-    HIPCHK(hipMalloc(&tg.p[4], gbytes ? gbytes : 1));                 // the build's sort scratch
-    tg.rows = (double4 *)tg.p[0];
+    // the cloud's rows, the grid's offsets, its points, their fp32 image, the build's sort scratch
+    const size_t bytes[5] = {sizeof(double4) * n, sizeof(int) * ((size_t)ncell + 1), sizeof(double4) * n, sizeof(float4) * n,
+                             gbytes ? gbytes : 1};
+    void *q[5];
+    if (kept) {
+        size_t off[5], total = 0;
+        for (int i = 0; i < 5; ++i) {
+            off[i] = total;
+            total += (bytes[i] + 255) & ~(size_t)255;
+        }
+        TRY(grow(ctx, &ctx->filt_grid, &ctx->filt_grid_cap, total));
+        for (int i = 0; i < 5; ++i) q[i] = ctx->filt_grid + off[i];
+    } else {
+        for (int i = 0; i < 5; ++i) {
+            HIPCHK(hipMalloc(&tg.p[i], bytes[i]));
+            q[i] = tg.p[i];
+        }
+    }
+    tg.rows = (double4 *)q[0];
     launch_make_aos4(x, y, z, (int)n, tg.rows, ctx->st);
-    if (launch_grid_build(x, y, z, tg.rows, (int)n, gp, tg.p[4], gbytes, (int *)tg.p[1], (double4 *)tg.p[2], (float4 *)tg.p[3],
-                          ctx->st) != 0)
+    if (launch_grid_build(x, y, z, tg.rows, (int)n, gp, q[4], gbytes, (int *)q[1], (double4 *)q[2], (float4 *)q[3], ctx->st) != 0)
         return fail(ctx, ICP_E_HIP, who + ": grid build: radix sort failed");
     LAUNCHCHK(word + "_grid_build");
-    tg.gv = grid_view_of(gp, (const int *)tg.p[1], (const double4 *)tg.p[2], (const float4 *)tg.p[3]);
+    tg.gv = grid_view_of(gp, (const int *)q[1], (const double4 *)q[2], (const float4 *)q[3]);
     return ICP_OK;
 }
 
@@ -2838,15 +2835,22 @@ int icp_reset_stats(icp_ctx *ctx)
 namespace icp {
 namespace engine {
 
+int cloud_grid(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, TempGrid &tg, int *budget, double *soa)
+{
+    if (!soa) HIPCHK(hipMalloc(&tg.extra, sizeof(double) * 3 * n)); // the cloud's SoA streams
+    double *x = soa ? soa : (double *)tg.extra, *y = x + n, *z = y + n;
+    launch_aos_to_soa(aos, n, x, y, z, ctx->st);
+    TRY(temp_grid_build(ctx, who, "cloud", x, y, z, aos, n, tg, soa != nullptr));
+    *budget = grid_budget_for(n);
+    return ICP_OK;
+}
+
 int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
               int k, double4 *rows, double4 *nrm, int *idx, double *d2)
 {
     TempGrid tg; // (freed before the call returns, whatever it returns)
-    HIPCHK(hipMalloc(&tg.extra, sizeof(double) * 3 * n)); // the cloud's SoA streams
-    double *x = (double *)tg.extra, *y = x + n, *z = y + n;
-    launch_aos_to_soa(aos, n, x, y, z, ctx->st);
-    TRY(temp_grid_build(ctx, who, "cloud", x, y, z, aos, n, tg));
-    const int budget = grid_budget_for(n);
+    int budget = 0;
+    TRY(cloud_grid(ctx, who, aos, n, tg, &budget));
     if (k_normals > 0)
         TRY(estimate_normals(ctx, tg.gv, tg.rows, n, k_normals, budget, viewpoint, nrm, "cloud", nullptr,
                              [] { return (int)ICP_OK; }));

@@ -85,6 +85,7 @@ EXPORTED = [
     "icp_estimate_scene_normals", "icp_set_plane_to_plane",
     "icp_set_one_to_one",
     "icp_fpfh", "icp_match_features", "icp_match_features_plan", "icp_ransac_pose", "icp_global_pose",
+    "icp_filter_statistical", "icp_filter_statistical_device", "icp_filter_radius", "icp_filter_radius_device",
 ]
 
 
@@ -250,6 +251,12 @@ def lib() -> C.CDLL:
         L.icp_ransac_pose.argtypes = [vp, dp, dp, sz, C.c_longlong, C.c_uint64, C.c_double, C.c_double, dp, dp,
                                       llp, llp, llp, ip, C.POINTER(C.c_uint8)]
         L.icp_global_pose.argtypes = [vp, dp, sz, dp, sz, C.POINTER(GlobalParams), dp, dp, C.POINTER(GlobalReport)]
+    if hasattr(L, "icp_filter_statistical"):
+        u8p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        L.icp_filter_statistical.argtypes = [vp, dp, sz, C.c_int, C.c_double, dp, u8p, C.POINTER(sz), dp, dp]
+        L.icp_filter_statistical_device.argtypes = [vp, vp, sz, C.c_int, C.c_double, vp, vp, C.POINTER(sz), vp, dp]
+        L.icp_filter_radius.argtypes = [vp, dp, sz, C.c_double, C.c_int, dp, u8p, C.POINTER(sz), i32p]
+        L.icp_filter_radius_device.argtypes = [vp, vp, sz, C.c_double, C.c_int, vp, vp, C.POINTER(sz), vp]
     _lib = L
     return L
 
@@ -517,6 +524,65 @@ class Context:
         self._check(lib().icp_voxel_downsample_device(self._h, C.c_void_p(ptr), n, float(voxel),
                                                       None if o is None else _dp(o), C.c_void_p(out_ptr),
                                                       C.c_void_p(count_ptr) if count_ptr else None, C.byref(n_out)))
+        return int(n_out.value)
+
+    def filter_statistical(self, xyz, k: int = 16, std_ratio: float = 2.0, mask: bool = False, mean_dist: bool = False,
+                           stats: bool = False):
+        """icp_filter_statistical: the points whose mean distance to their k nearest neighbours is at most
+        mu + std_ratio * sigma of those means, in input order -> (n_out, 3), or a tuple of the points and, as
+        asked for, the mask (n, uint8), the mean distances (n) and (mu, sigma, T)."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        out = np.empty((max(n, 1), 3))
+        mk = np.empty(max(n, 1), dtype=np.uint8) if mask else None
+        md = np.empty(max(n, 1)) if mean_dist else None
+        st = np.empty(3) if stats else None
+        n_out = C.c_size_t(0)
+        self._check(lib().icp_filter_statistical(self._h, _dp(xyz), n, int(k), float(std_ratio), _dp(out),
+                                                 mk.ctypes.data_as(C.POINTER(C.c_uint8)) if mask else None,
+                                                 C.byref(n_out), _dp(md) if mean_dist else None,
+                                                 _dp(st) if stats else None))
+        res = (out[:int(n_out.value)].copy(),) + tuple(a[:n] for a in (mk, md) if a is not None)
+        if stats:
+            res += (st,)
+        return res if len(res) > 1 else res[0]
+
+    def filter_radius(self, xyz, radius: float, min_neighbors: int, mask: bool = False, counts: bool = False):
+        """icp_filter_radius: the points with at least min_neighbors other points within `radius`, in input
+        order -> (n_out, 3), or a tuple of the points and, as asked for, the mask (n, uint8) and the counts
+        (n, int32: the points within the radius, the point itself included)."""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        out = np.empty((max(n, 1), 3))
+        mk = np.empty(max(n, 1), dtype=np.uint8) if mask else None
+        cn = np.empty(max(n, 1), dtype=np.int32) if counts else None
+        n_out = C.c_size_t(0)
+        self._check(lib().icp_filter_radius(self._h, _dp(xyz), n, float(radius), int(min_neighbors), _dp(out),
+                                            mk.ctypes.data_as(C.POINTER(C.c_uint8)) if mask else None, C.byref(n_out),
+                                            cn.ctypes.data_as(C.POINTER(C.c_int32)) if counts else None))
+        res = (out[:int(n_out.value)].copy(),) + tuple(a[:n] for a in (mk, cn) if a is not None)
+        return res if len(res) > 1 else res[0]
+
+    def filter_statistical_device(self, ptr: int, n: int, k: int, std_ratio: float, out_ptr: int | None,
+                                  mask_ptr: int | None = None, mean_dist_ptr: int | None = None):
+        """icp_filter_statistical_device: the cloud (AoS fp64), the output cloud (room for n points), the mask
+        (uint8, n) and the mean distances (fp64, n) are device pointers (None: not wanted)
+        -> (n_out, (mu, sigma, T))."""
+        n_out = C.c_size_t(0)
+        st = np.empty(3)
+        opt = lambda q: C.c_void_p(q) if q else None
+        self._check(lib().icp_filter_statistical_device(self._h, C.c_void_p(ptr), n, int(k), float(std_ratio),
+                                                        opt(out_ptr), opt(mask_ptr), C.byref(n_out),
+                                                        opt(mean_dist_ptr), _dp(st)))
+        return int(n_out.value), st
+
+    def filter_radius_device(self, ptr: int, n: int, radius: float, min_neighbors: int, out_ptr: int | None,
+                             mask_ptr: int | None = None, count_ptr: int | None = None) -> int:
+        """icp_filter_radius_device: as filter_statistical_device; the counts are int32 -> n_out."""
+        n_out = C.c_size_t(0)
+        opt = lambda q: C.c_void_p(q) if q else None
+        self._check(lib().icp_filter_radius_device(self._h, C.c_void_p(ptr), n, float(radius), int(min_neighbors),
+                                                   opt(out_ptr), opt(mask_ptr), C.byref(n_out), opt(count_ptr)))
         return int(n_out.value)
 
     def transform(self):
