@@ -1,14 +1,16 @@
 // icp_engine.h — private to the engine's translation units: icp_engine.hip (the context, the
 // model and scene set-up, the searches, the per-operation surface), icp_run.hip (icp_run's
-// loops) and icp_global.hip (global registration's four calls).  The context, the few types they
-// share, the error macros, the run path's knob table and the declarations of the helpers one file
-// calls in another.  The helpers are icp::engine
+// loops), icp_cloud.hip (the normals, the k-NN lists and the temporary grid of a cloud),
+// icp_global.hip (global registration's four calls) and icp_filter.hip (the outlier filters).  The
+// context, the few types they share, the error macros, the run path's knob table and the
+// declarations of the helpers one file calls in another.  The helpers are icp::engine
 // and hidden: the shared library exports the C ABI (include/icp_capi.h) and nothing of this.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -22,6 +24,12 @@ struct DevCloud {
     double *x = nullptr, *y = nullptr, *z = nullptr;
     float4 *f = nullptr;
     size_t n = 0, cap = 0;
+};
+
+// device memory the context keeps for the Scratch objects over it: want = the last call's total
+struct KeptBlock {
+    char *base = nullptr;
+    size_t cap = 0, want = 0;
 };
 
 } // namespace engine
@@ -355,11 +363,10 @@ struct icp_ctx {
     double *vox_io = nullptr;
     int *vox_cnt = nullptr;
     size_t vox_buf_cap = 0, vox_io_cap = 0, vox_cnt_cap = 0;
-    // icp_filter_* (icp_filter.hip): scratch of those calls alone, kept between calls (a call's dozen
-    // allocations cost as much as its kernels) -- the temporary grid's arrays (filt_grid) and the
-    // filters' own arrays and staged clouds (filt_buf)
-    char *filt_grid = nullptr, *filt_buf = nullptr;
-    size_t filt_grid_cap = 0, filt_buf_cap = 0;
+    // icp_filter_* (icp_filter.hip): every device array of a call -- the temporary grid's, the filter's
+    // own, the staged clouds -- is a part of this one block (Scratch's kept mode), kept between calls: a
+    // call's dozen allocations cost as much as its kernels
+    KeptBlock filt_block;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
@@ -529,39 +536,69 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
                     bool slot_order = false, bool grid_seeded = false, const double *seedd = nullptr);
 int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop);
 int moments_phase(icp_ctx *ctx, size_t n);
-// icp_fpfh's grid half (icp_global.hip): a temporary grid of the n points in aos (device memory, 3 x n
-// col-major), built as icp_estimate_scene_normals builds the scene's and freed before the call
-// returns; rows = the points' double4 rows; with k_normals > 0 nrm = their normals by the estimator's
-// own kernels; row j of idx / d2 = launch_model_knn's k lists.  All four are the caller's device
-// arrays of n (rows, nrm) and n x k entries.  ICP_E_RANGE for a non-finite coordinate.  Synchronous.
+int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32);
+int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz);
+int ensure_model_stats(icp_ctx *ctx);
+GridView grid_view_of(const GridParams &p, const int *start, const double4 *pts, const float4 *pts32);
+int grid_budget_for(size_t n);
+
+// ---- icp_cloud.hip ---------------------------------------------------------------------
+// The device arrays of one call on a cloud that is not the resident model; they go, or may be handed out
+// again, with the object.  Owning (kept null): every get is a hipMalloc, freed with the object.  Kept,
+// over a block of the context's: a get is a 256-byte-aligned part of the block while it fits and an
+// allocation of the object's own when it does not; the object leaves the call's total in the block, and
+// the next object over it grows the block to that, once, before it hands anything out -- so a call at the
+// size of the one before it allocates nothing.  A count of 0 yields a valid pointer.
+class Scratch {
+public:
+    explicit Scratch(icp_ctx *ctx, KeptBlock *kept = nullptr) : ctx(ctx), kept(kept) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch();
+    template <class T> int get(T **out, size_t count) { return get_bytes((void **)out, sizeof(T) * (count ? count : 1)); }
+
+private:
+    int get_bytes(void **out, size_t bytes);
+    icp_ctx *ctx;
+    KeptBlock *kept;
+    size_t off = 0, total = 0;
+    bool begun = false;
+    std::vector<void *> own;
+};
+
+// A temporary grid over a cloud that is not the model: the cloud's double4 rows, the grid as the kernels
+// take it, its cell budget.  The arrays are the Scratch's that it was built from.
+struct TempGrid {
+    double4 *rows = nullptr;
+    GridView gv{};
+    int budget = 0;
+};
+
+// tg = the grid of the n points in aos (device memory, 3 x n col-major), built as the scene estimator's,
+// its arrays and the cloud's SoA streams taken from mem.  Asynchronous on the context's stream but for the
+// box's read-back; the caller synchronises before mem goes.  ICP_E_RANGE for a non-finite coordinate.
+int cloud_grid(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, Scratch &mem, TempGrid &tg);
+// icp_fpfh's grid half: cloud_grid in memory of its own, freed before the call returns; rows = the points'
+// double4 rows; with k_normals > 0 nrm = their normals by the estimator's kernels; row j of idx / d2 =
+// launch_model_knn's k lists: the caller's device arrays of n (rows, nrm) and n x k entries.  Synchronous.
 int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
               int k, double4 *rows, double4 *nrm, int *idx, double *d2);
 
-// A temporary grid over a cloud that is not the model, freed with the object; extra: one more allocation
-// of the builder's that goes with it.  (A grid built into the context's filt_grid owns nothing.)
-struct TempGrid {
-    void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // rows, offsets, points, fp32 image, sort scratch
-    void *extra = nullptr;
-    double4 *rows = nullptr;
-    GridView gv{};
-    TempGrid() = default;
-    TempGrid(const TempGrid &) = delete;
-    TempGrid &operator=(const TempGrid &) = delete;
-    ~TempGrid()
-    {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-        if (extra) (void)hipFree(extra);
-    }
-};
-
-// The grid alone: tg = cloud_knn's temporary grid of the n points in aos, *budget = its cell budget.  soa
-// null: its memory is tg's own; else (the outlier filters, icp_filter.hip) soa = 3 n doubles of the
-// caller's for the SoA streams and the grid's arrays live in the context's filt_grid, kept for the next
-// call.  Asynchronous on the context's stream but for the box's read-back; the caller synchronises
-// before tg goes.  ICP_E_RANGE for a non-finite coordinate.
-int cloud_grid(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, TempGrid &tg, int *budget,
-               double *soa = nullptr);
+// the checks and the unpack loop these calls share; each caller words its own refusal
+constexpr size_t kAllFinite = ~(size_t)0;
+inline size_t first_nonfinite(const double *v, size_t count) // the first non-finite entry's index, or kAllFinite
+{
+    for (size_t k = 0; k < count; ++k)
+        if (!std::isfinite(v[k])) return k;
+    return kAllFinite;
+}
+// name = k within [kKnnMinK, kKnnMaxK] and at most the `word`'s n points (ICP_E_ARG)
+int knn_k_check(icp_ctx *ctx, const std::string &who, const char *name, int k, const std::string &word, size_t n);
+inline void rows4_to_xyz(const double *rows4, size_t n, double *xyz) // n (x, y, z, -) rows -> 3 x n col-major
+{
+    for (size_t j = 0; j < n; ++j)
+        for (int a = 0; a < 3; ++a) xyz[3 * j + a] = rows4[4 * j + a];
+}
 
 // ---- icp_run.hip -----------------------------------------------------------------------
 int wait_flag(icp_ctx *ctx, const int *flag, int ticket);

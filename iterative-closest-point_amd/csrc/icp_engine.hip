@@ -10,13 +10,13 @@
 //  * per iteration only 18 fp64 sums cross PCIe (the reference round-trips whole clouds
 //    ~30 times per iteration);
 //  * multi-GPU: the scene is sharded across ranks, the sums are all-reduced with RCCL.
-// icp_run's loops are icp_run.hip; what the two files share is icp_engine.h.
+// icp_run's loops are icp_run.hip, the normals, the k-NN lists and a cloud's temporary grid icp_cloud.hip;
+// what the files share is icp_engine.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <climits>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -141,7 +141,7 @@ int fail(icp_ctx *ctx, int code, const std::string &msg)
             return fail(ctx, ICP_E_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
-static int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
+int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
 {
     if (c.cap < n || !c.x || (with_f32 && !c.f)) {
         for (void *p : {(void *)c.x, (void *)c.y, (void *)c.z, (void *)c.f})
@@ -219,7 +219,7 @@ static int upload_cloud(icp_ctx *ctx, DevCloud &c, const double *xyz, size_t n, 
     return ICP_OK;
 }
 
-static int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
+int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
 {
     if (!n) return ICP_OK;
     if (3 * n <= kMappedIo) { // small: the conversion kernel writes the host copy directly
@@ -311,8 +311,18 @@ int level1_kind(const icp_ctx *ctx, size_t n)
     return 0;
 }
 
+// launch_model_stats' scratch, its 16 outputs and their host copy, at the first use
+int ensure_model_stats(icp_ctx *ctx)
+{
+    if (ctx->mstat_part) return ICP_OK;
+    HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
+    HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
+    HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
+    return ICP_OK;
+}
+
 // a built grid as the kernels take it: its geometry, offsets, points and their fp32 image
-static GridView grid_view_of(const GridParams &p, const int *start, const double4 *pts, const float4 *pts32)
+GridView grid_view_of(const GridParams &p, const int *start, const double4 *pts, const float4 *pts32)
 {
     GridView gv{};
     gv.pts = pts;
@@ -340,7 +350,7 @@ GridView grid_view(const icp_ctx *ctx)
 // 6,060 -> 12,000 took the grid variant 3,700 -> 4,277 -> 5,003 it/s and the default 5,560 ->
 // 5,977 -> 6,012, with no gain beyond; bunny likewise.  ICP_GRID_BUDGET overrides.
 // (n: the points the grid holds.)
-static int grid_budget_for(size_t n)
+int grid_budget_for(size_t n)
 {
     if (run_knobs().grid_budget) return run_knobs().grid_budget;
     return (int)std::min<size_t>(std::max<size_t>(kGridBudget, n / 4), (size_t)1 << 16);
@@ -1300,7 +1310,7 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
                     (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
-                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->filt_grid, (void *)ctx->filt_buf,
+                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->filt_block.base,
                     (void *)ctx->trim_keys,
                     (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state,
                     (void *)ctx->uniq_best})
@@ -1454,140 +1464,17 @@ int icp_set_metric(icp_ctx *ctx, int metric)
     return ICP_OK;
 }
 
-// What icp_set_{model,scene}_normals[_device] share: the checks (who: the host function's name, which
-// its _device form reports under too; word: the cloud's; present, count: the cloud's) and, of a host
-// array, the finite check and the upload to the stage.  *aos_dev: the interleaved array in device memory.
-static int normals_upload(icp_ctx *ctx, const std::string &who, const std::string &word, bool present, size_t count,
-                          const double *n_xyz, size_t n, bool host, const double **aos_dev)
+int icp_set_plane_symmetric(icp_ctx *ctx, int on)
 {
-    if (!present) return fail(ctx, ICP_E_NO_MODEL, who + ": no " + word + " (icp_set_" + word + ")");
-    if (n != count)
-        return fail(ctx, ICP_E_SIZE_MISMATCH, who + ": " + std::to_string(n) + " normals for a " + word + " of " +
-                                                  std::to_string(count) + " points");
-    HIPCHK(hipSetDevice(ctx->device));
-    *aos_dev = n_xyz;
-    if (!host) {
-        HIPCHK(hipDeviceSynchronize()); // (as icp_set_model_device / icp_set_scene_device: after the work of any stream)
-        return ICP_OK;
-    }
-    for (size_t k = 0; k < 3 * n; ++k)
-        if (!std::isfinite(n_xyz[k])) return fail(ctx, ICP_E_ARG, who + ": normal " + std::to_string(k / 3) + " is not finite");
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
-    HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
-    *aos_dev = ctx->stage;
+    if (!ctx || (on != 0 && on != 1)) return ICP_E_ARG;
+    ctx->plane_symmetric = on == 1;
     return ICP_OK;
 }
 
-// the model's normals as double4 rows, from its interleaved array (host or device memory)
-static int set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm, bool host)
+int icp_set_plane_to_plane(icp_ctx *ctx, double epsilon)
 {
-    if (!ctx || !n_xyz) return ICP_E_ARG;
-    const double *aos_dev = nullptr;
-    TRY(normals_upload(ctx, "icp_set_model_normals", "model", ctx->has_model, ctx->nm, n_xyz, nm, host, &aos_dev));
-    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, nm));
-    launch_plane_normals4(aos_dev, (int)nm, ctx->n4, ctx->st);
-    LAUNCHCHK("plane_normals4");
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the caller's array, or the stage, is free again)
-    ctx->has_normals = true;
-    return ICP_OK;
-}
-
-int icp_set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm) { return set_model_normals(ctx, n_xyz, nm, true); }
-
-int icp_set_model_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t nm)
-{
-    return set_model_normals(ctx, n_xyz_dev, nm, false);
-}
-
-// the checks of a k-NN call over a cloud (word, present, count: the model or the scene) and of an
-// estimator's viewpoint (nullable); nothing has run when they fail
-static int knn_args(icp_ctx *ctx, const std::string &who, const std::string &word, bool present, size_t count, int k,
-                    const double *viewpoint)
-{
-    if (!present) return fail(ctx, ICP_E_NO_MODEL, who + ": no " + word + " (icp_set_" + word + ")");
-    if (k < kKnnMinK || k > kKnnMaxK)
-        return fail(ctx, ICP_E_ARG, who + ": k = " + std::to_string(k) + " is outside [" + std::to_string(kKnnMinK) + ", " +
-                                        std::to_string(kKnnMaxK) + "]");
-    if ((size_t)k > count)
-        return fail(ctx, ICP_E_ARG, who + ": k = " + std::to_string(k) + " exceeds the " + word + "'s " +
-                                        std::to_string(count) + " points");
-    if (viewpoint)
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(viewpoint[a]))
-                return fail(ctx, ICP_E_ARG, who + ": viewpoint[" + std::to_string(a) + "] = " + std::to_string(viewpoint[a]) +
-                                                " is not finite");
-    HIPCHK(hipSetDevice(ctx->device));
-    return ICP_OK;
-}
-
-static bool model_gridded(const icp_ctx *ctx) { return ctx->has_model && ctx->g_start && ctx->g_pts && ctx->m4; }
-
-int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2)
-{
-    if (!ctx) return ICP_E_ARG;
-    if (!idx) return fail(ctx, ICP_E_ARG, "icp_model_knn: idx is null");
-    TRY(knn_args(ctx, "icp_model_knn", "model", model_gridded(ctx), ctx->nm, k, nullptr));
-    const size_t cnt = ctx->nm * (size_t)k;
-    TRY(grow(ctx, &ctx->knn_idx, &ctx->knn_idx_cap, cnt));
-    if (d2) TRY(grow(ctx, &ctx->knn_d2, &ctx->knn_d2_cap, cnt));
-    launch_model_knn(grid_view(ctx), ctx->m4, (int)ctx->nm, k, grid_budget(ctx), ctx->knn_idx, d2 ? ctx->knn_d2 : nullptr,
-                     ctx->st);
-    LAUNCHCHK("model_knn");
-    HIPCHK(hipMemcpyAsync(idx, ctx->knn_idx, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, ctx->st));
-    if (d2) HIPCHK(hipMemcpyAsync(d2, ctx->knn_d2, sizeof(double) * cnt, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    return ICP_OK;
-}
-
-// What both estimators run on a grid gv over the n rows: the counters zeroed, the k-NN + PCA kernel
-// (the rows' normals into out), then() (what the caller enqueues behind it), the counters read back:
-// *degenerate and, with ICP_NORMALS_DEBUG set, the search's counts of this call to stderr
-// (tools/normals_probe.py).  label: "model" or "scene".
-static int estimate_normals(icp_ctx *ctx, const GridView &gv, const double4 *rows, size_t n, int k, int budget,
-                            const double *viewpoint, double4 *out, const std::string &label, long long *degenerate,
-                            const std::function<int()> &then)
-{
-    static const bool debug = getenv("ICP_NORMALS_DEBUG") != nullptr;
-    TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
-    HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
-    launch_model_normals(gv, rows, (int)n, k, budget, viewpoint, out, ctx->knn_counters, debug, ctx->st);
-    LAUNCHCHK(label + "_normals");
-    TRY(then());
-    unsigned long long c[kKnnCounters];
-    HIPCHK(hipMemcpyAsync(c, ctx->knn_counters, sizeof(c), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    if (degenerate) *degenerate = (long long)c[0];
-    if (debug)
-        std::fprintf(stderr, "[normals] %s=%zu k=%d degenerate=%llu second_scans=%llu full_scans=%llu candidates=%llu\n",
-                     label == "model" ? "nm" : (label == "scene" ? "scene n" : "cloud n"), n, k, c[0], c[1], c[2], c[3]);
-    return ICP_OK;
-}
-
-int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
-{
-    if (!ctx) return ICP_E_ARG;
-    TRY(knn_args(ctx, "icp_estimate_model_normals", "model", model_gridded(ctx), ctx->nm, k, viewpoint));
-    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, ctx->nm));
-    ctx->has_normals = false; // (until the new ones are complete)
-    TRY(estimate_normals(ctx, grid_view(ctx), ctx->m4, ctx->nm, k, grid_budget(ctx), viewpoint, ctx->n4, "model", degenerate,
-                         [] { return (int)ICP_OK; }));
-    ctx->has_normals = true;
-    return ICP_OK;
-}
-
-int icp_get_model_normals(icp_ctx *ctx, double *n_xyz)
-{
-    if (!ctx) return ICP_E_ARG;
-    if (!n_xyz) return fail(ctx, ICP_E_ARG, "icp_get_model_normals: n_xyz is null");
-    if (!ctx->has_model || !ctx->has_normals || !ctx->n4)
-        return fail(ctx, ICP_E_NO_MODEL, "icp_get_model_normals: the model has no normals (icp_set_model_normals, "
-                                         "icp_estimate_model_normals)");
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    std::vector<double> rows(4 * ctx->nm);
-    HIPCHK(hipMemcpy(rows.data(), ctx->n4, sizeof(double) * 4 * ctx->nm, hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < ctx->nm; ++j)
-        for (int a = 0; a < 3; ++a) n_xyz[3 * j + a] = rows[4 * j + a];
+    if (!ctx || !(epsilon >= 0.0 && epsilon <= 1.0)) return ICP_E_ARG; // (false for a NaN)
+    ctx->plane_to_plane = epsilon;
     return ICP_OK;
 }
 
@@ -1608,16 +1495,6 @@ static bool kd_host()
         return e && atoi(e) == 1;
     }();
     return on;
-}
-
-// launch_model_stats' scratch, its 16 outputs and their host copy, at the first use
-static int ensure_model_stats(icp_ctx *ctx)
-{
-    if (ctx->mstat_part) return ICP_OK;
-    HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
-    HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
-    return ICP_OK;
 }
 
 // icp_set_model from the staged AoS copy: every image of the model is built on the device
@@ -1992,152 +1869,6 @@ int icp_get_scene(icp_ctx *ctx, double *p_xyz_out)
     return download_cloud(ctx, ctx->scene, ctx->scene.n, p_xyz_out);
 }
 
-// ---- the scene's normals (the symmetric point-to-plane iteration) ------------------------
-
-int icp_set_plane_symmetric(icp_ctx *ctx, int on)
-{
-    if (!ctx || (on != 0 && on != 1)) return ICP_E_ARG;
-    ctx->plane_symmetric = on == 1;
-    return ICP_OK;
-}
-
-int icp_set_plane_to_plane(icp_ctx *ctx, double epsilon)
-{
-    if (!ctx || !(epsilon >= 0.0 && epsilon <= 1.0)) return ICP_E_ARG; // (false for a NaN)
-    ctx->plane_to_plane = epsilon;
-    return ICP_OK;
-}
-
-// u0 (the caller's order) from the scene's interleaved normals (host or device memory)
-static int set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t n, bool host)
-{
-    if (!ctx || !n_xyz) return ICP_E_ARG;
-    const double *aos_dev = nullptr;
-    TRY(normals_upload(ctx, "icp_set_scene_normals", "scene", ctx->has_scene, ctx->scene.n, n_xyz, n, host, &aos_dev));
-    ctx->has_scene_normals = false; // (until the new ones are complete)
-    ctx->sn_slot_valid = false;
-    TRY(grow_cloud(ctx, ctx->sn, n, false));
-    if (n) launch_aos_to_soa(aos_dev, n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
-    LAUNCHCHK("scene_normals");
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the caller's array, or the stage, is free again)
-    ctx->has_scene_normals = true;
-    return ICP_OK;
-}
-
-int icp_set_scene_normals(icp_ctx *ctx, const double *n_xyz, size_t np_local)
-{
-    return set_scene_normals(ctx, n_xyz, np_local, true);
-}
-
-int icp_set_scene_normals_device(icp_ctx *ctx, const double *n_xyz_dev, size_t np_local)
-{
-    return set_scene_normals(ctx, n_xyz_dev, np_local, false);
-}
-
-int icp_get_scene_normals(icp_ctx *ctx, double *n_xyz)
-{
-    if (!ctx) return ICP_E_ARG;
-    if (!n_xyz && ctx->scene.n) return fail(ctx, ICP_E_ARG, "icp_get_scene_normals: n_xyz is null");
-    if (!ctx->has_scene || !ctx->has_scene_normals)
-        return fail(ctx, ICP_E_NO_MODEL, "icp_get_scene_normals: the scene has no normals (icp_set_scene_normals, "
-                                         "icp_estimate_scene_normals)");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = ctx->scene.n;
-    TRY(download_cloud(ctx, ctx->sn, n, n_xyz)); // u0, the caller's order
-    if (ctx->tot_n == 0) return ICP_OK;
-    const double *Q = ctx->tot + 1; // u = Q u0, each row ((Q0 u0 + Q1 u1) + Q2 u2) as the kernels sum it
-    for (size_t j = 0; j < n; ++j) {
-        const double a0 = n_xyz[3 * j], a1 = n_xyz[3 * j + 1], a2 = n_xyz[3 * j + 2];
-        for (int r = 0; r < 3; ++r) n_xyz[3 * j + r] = (Q[3 * r] * a0 + Q[3 * r + 1] * a1) + Q[3 * r + 2] * a2;
-    }
-    return ICP_OK;
-}
-
-// A temporary grid over n points that are not the model (icp_estimate_scene_normals, icp_fpfh): the
-// one place where it is built, so that both get what icp_set_model makes of a model's upload.  The
-// cloud comes as its SoA streams (x, y, z) and its interleaved copy (aos), both in device memory: the
-// box and the finiteness check from aos (ICP_E_RANGE names `word`), the grid's size from the box, the
-// double4 rows, the build.  Everything is freed with the object (TempGrid, icp_engine.h); with `kept` the
-// five arrays are parts of the context's filt_grid instead, which stays for the next call.
-static int temp_grid_build(icp_ctx *ctx, const std::string &who, const std::string &word, const double *x, const double *y,
-                           const double *z, const double *aos, size_t n, TempGrid &tg, bool kept = false)
-{
-    TRY(ensure_model_stats(ctx));
-    launch_model_stats(aos, (int)n, ctx->mstat_part, ctx->mstat_out, ctx->st);
-    LAUNCHCHK(word + "_stats");
-    HIPCHK(hipMemcpyAsync(ctx->h_mstat, ctx->mstat_out, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    if (ctx->h_mstat[9] != 0.0) return fail(ctx, ICP_E_RANGE, who + ": the " + word + " has non-finite coordinates");
-    const GridParams gp = grid_params_box(ctx->h_mstat + 3, ctx->h_mstat + 6, n);
-    const long long ncell = grid_cells(gp);
-    const size_t gbytes = grid_build_scratch_bytes((int)n, ncell);
-    // the cloud's rows, the grid's offsets, its points, their fp32 image, the build's sort scratch
-    const size_t bytes[5] = {sizeof(double4) * n, sizeof(int) * ((size_t)ncell + 1), sizeof(double4) * n, sizeof(float4) * n,
-                             gbytes ? gbytes : 1};
-    void *q[5];
-    if (kept) {
-        size_t off[5], total = 0;
-        for (int i = 0; i < 5; ++i) {
-            off[i] = total;
-            total += (bytes[i] + 255) & ~(size_t)255;
-        }
-        TRY(grow(ctx, &ctx->filt_grid, &ctx->filt_grid_cap, total));
-        for (int i = 0; i < 5; ++i) q[i] = ctx->filt_grid + off[i];
-    } else {
-        for (int i = 0; i < 5; ++i) {
-            HIPCHK(hipMalloc(&tg.p[i], bytes[i]));
-            q[i] = tg.p[i];
-        }
-    }
-    tg.rows = (double4 *)q[0];
-    launch_make_aos4(x, y, z, (int)n, tg.rows, ctx->st);
-    if (launch_grid_build(x, y, z, tg.rows, (int)n, gp, q[4], gbytes, (int *)q[1], (double4 *)q[2], (float4 *)q[3], ctx->st) != 0)
-        return fail(ctx, ICP_E_HIP, who + ": grid build: radix sort failed");
-    LAUNCHCHK(word + "_grid_build");
-    tg.gv = grid_view_of(gp, (const int *)q[1], (const double4 *)q[2], (const float4 *)q[3]);
-    return ICP_OK;
-}
-
-int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, long long *degenerate)
-{
-    if (!ctx) return ICP_E_ARG;
-    const std::string who = "icp_estimate_scene_normals";
-    const size_t n = ctx->scene.n;
-    // (these two refusals come before the checks on k; with no scene knn_args' first check answers)
-    if (ctx->has_scene && n != ctx->np_total)
-        return fail(ctx, ICP_E_ARG, who + ": the scene is sharded (" + std::to_string(n) + " of " +
-                                        std::to_string(ctx->np_total) + " points on this rank)");
-    if (ctx->has_scene && !ctx->scene_pristine)
-        return fail(ctx, ICP_E_ARG, who + ": an icp_run or icp_transform_scene has moved the scene since icp_set_scene");
-    TRY(knn_args(ctx, who, "scene", ctx->has_scene, n, k, viewpoint));
-    // the scene in the caller's order (a copy when it is resident in slot order), its interleaved
-    // copy for the box, its double4 rows: what icp_set_model makes of a model's upload
-    const DevCloud *P = &ctx->scene;
-    if (ctx->scene_slot) {
-        TRY(grow_cloud(ctx, ctx->s_tmp, n, true));
-        launch_permute_cloud(ctx->s_order, (int)n, 1, ctx->scene.x, ctx->scene.y, ctx->scene.z, nullptr, nullptr,
-                             ctx->s_tmp.x, ctx->s_tmp.y, ctx->s_tmp.z, nullptr, nullptr, ctx->st);
-        LAUNCHCHK("scene_to_file_order");
-        P = &ctx->s_tmp;
-    }
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
-    launch_soa_to_aos(P->x, P->y, P->z, n, ctx->stage, ctx->st);
-    TempGrid tg; // (freed before the call returns, whatever it returns)
-    TRY(temp_grid_build(ctx, who, "scene", P->x, P->y, P->z, ctx->stage, n, tg));
-    HIPCHK(hipMalloc(&tg.extra, sizeof(double4) * n)); // the normals' rows
-    double4 *nrm = (double4 *)tg.extra;
-    TRY(estimate_normals(ctx, tg.gv, tg.rows, n, k, grid_budget_for(n), viewpoint, nrm, "scene", degenerate, [&] {
-        ctx->has_scene_normals = false; // (until the new ones are complete)
-        ctx->sn_slot_valid = false;
-        TRY(grow_cloud(ctx, ctx->sn, n, false));
-        launch_rows4_to_soa(nrm, (int)n, ctx->sn.x, ctx->sn.y, ctx->sn.z, ctx->st);
-        LAUNCHCHK("scene_normals_rows");
-        return (int)ICP_OK;
-    }));
-    ctx->has_scene_normals = true;
-    return ICP_OK;
-}
-
 // ---- the total transform, a pose for the resident scene, the voxel downsample -----------
 
 int icp_get_transform(icp_ctx *ctx, double *s, double R[9], double t[3])
@@ -2300,9 +2031,8 @@ int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel
                          int32_t *count_out, size_t *n_out)
 {
     TRY(voxel_args(ctx, xyz, n, voxel, origin, xyz_out, n_out));
-    for (size_t k = 0; k < 3 * n; ++k)
-        if (!std::isfinite(xyz[k]))
-            return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: point " + std::to_string(k / 3) + " is not finite");
+    const size_t bad = first_nonfinite(xyz, 3 * n);
+    if (bad != kAllFinite) return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: point " + std::to_string(bad / 3) + " is not finite");
     TRY(grow(ctx, &ctx->vox_io, &ctx->vox_io_cap, 6 * n));
     if (count_out) TRY(grow(ctx, &ctx->vox_cnt, &ctx->vox_cnt_cap, n));
     double *in = ctx->vox_io, *out = ctx->vox_io + 3 * n;
@@ -2831,35 +2561,3 @@ int icp_reset_stats(icp_ctx *ctx)
 }
 
 } // extern "C"
-
-namespace icp {
-namespace engine {
-
-int cloud_grid(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, TempGrid &tg, int *budget, double *soa)
-{
-    if (!soa) HIPCHK(hipMalloc(&tg.extra, sizeof(double) * 3 * n)); // the cloud's SoA streams
-    double *x = soa ? soa : (double *)tg.extra, *y = x + n, *z = y + n;
-    launch_aos_to_soa(aos, n, x, y, z, ctx->st);
-    TRY(temp_grid_build(ctx, who, "cloud", x, y, z, aos, n, tg, soa != nullptr));
-    *budget = grid_budget_for(n);
-    return ICP_OK;
-}
-
-int cloud_knn(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k_normals, const double *viewpoint,
-              int k, double4 *rows, double4 *nrm, int *idx, double *d2)
-{
-    TempGrid tg; // (freed before the call returns, whatever it returns)
-    int budget = 0;
-    TRY(cloud_grid(ctx, who, aos, n, tg, &budget));
-    if (k_normals > 0)
-        TRY(estimate_normals(ctx, tg.gv, tg.rows, n, k_normals, budget, viewpoint, nrm, "cloud", nullptr,
-                             [] { return (int)ICP_OK; }));
-    launch_model_knn(tg.gv, tg.rows, (int)n, k, budget, idx, d2, ctx->st);
-    LAUNCHCHK("cloud_knn");
-    HIPCHK(hipMemcpyAsync(rows, tg.rows, sizeof(double4) * n, hipMemcpyDeviceToDevice, ctx->st));
-    HIPCHK(hipStreamSynchronize(ctx->st)); // (the grid is freed on return)
-    return ICP_OK;
-}
-
-} // namespace engine
-} // namespace icp

@@ -1,8 +1,8 @@
 // icp_filter.hip -- outlier removal on the device: the statistical and the radius filter behind
 // icp_filter_statistical* and icp_filter_radius* (include/icp_capi.h states the rules).
-// Both take an arbitrary cloud, build cloud_knn's temporary grid over it (icp_engine.hip), decide a
-// mask per point and compact the kept points in input order.  Their device memory is the context's
-// (filt_grid, filt_buf: scratch of these calls alone, grown as needed and kept between calls).
+// Both take an arbitrary cloud, build cloud_grid's temporary grid over it (icp_cloud.hip), decide a
+// mask per point and compact the kept points in input order.  Every device array of a call, the grid's
+// included, is a part of the context's filt_block (a kept Scratch, icp_engine.h), which stays for the next call.
 //
 //   knn_mean_dist_kernel   one lane a query in cell-sorted order, the [slot][lane] LDS lists and
 //                          knn_search of icp_knn.h with k + 1 entries (the normals kernel's search); the
@@ -228,32 +228,6 @@ __global__ __launch_bounds__(kBlock) void filter_place_kernel(const double *__re
 
 int blocks_for(size_t n, int per) { return (int)((std::max<size_t>(n, 1) + per - 1) / per); }
 
-// The device arrays of one call: parts (256-byte aligned) of the context's filt_buf, which begin() grows
-// to what a call over n points can take at the most and which stays for the next call
-struct DevTemp {
-    char *base = nullptr;
-    size_t cap = 0, off = 0;
-    int begin(icp_ctx *ctx, size_t n)
-    {
-        // per point: the staged cloud in and out and the SoA streams (3 x 24), dbar and its staged copy (2 x 8),
-        // the counts and theirs (2 x 4), the mask and its (2 x 1); the sums' and the tiles' rows; 16 parts
-        const size_t rows = n / 1024 + 2;
-        TRY(grow(ctx, &ctx->filt_buf, &ctx->filt_buf_cap, n * 98 + rows * 20 + 24 + 16 * 256));
-        base = ctx->filt_buf;
-        cap = ctx->filt_buf_cap;
-        return ICP_OK;
-    }
-    template <class T> hipError_t get(T **out, size_t count)
-    {
-        const size_t bytes = (sizeof(T) * (count ? count : 1) + 255) & ~(size_t)255;
-        *out = nullptr;
-        if (!base || off + bytes > cap) return hipErrorOutOfMemory;
-        *out = (T *)(base + off);
-        off += bytes;
-        return hipSuccess;
-    }
-};
-
 // The sum rule over v (kDev: over (v - *mu)^2): level after level into the two halves of part
 // (blocks_for(n, kFilterChunk) + 1 doubles each); -> the device address of S
 template <bool kDev>
@@ -313,25 +287,24 @@ int radius_args(icp_ctx *ctx, const std::string &who, const void *xyz, size_t n,
 // the host forms' check of the coordinates: ICP_E_RANGE names the first non-finite one
 int finite_cloud(icp_ctx *ctx, const std::string &who, const double *xyz, size_t n)
 {
-    for (size_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(xyz[i]))
-            return fail(ctx, ICP_E_RANGE, who + ": point " + std::to_string(i / 3) + " has the non-finite coordinate " +
-                                              std::to_string(xyz[i]));
-    return ICP_OK;
+    const size_t bad = first_nonfinite(xyz, 3 * n);
+    if (bad == kAllFinite) return ICP_OK;
+    return fail(ctx, ICP_E_RANGE, who + ": point " + std::to_string(bad / 3) + " has the non-finite coordinate " +
+                                      std::to_string(xyz[bad]));
 }
 
 // What follows a filter's per-point values: the mask, the tile counts, the scan, *kept on the host
 // (synchronises: everything before it has run), and then alone the caller's arrays are written --
 // the kept points at their ranks and the mask.
 template <bool kStat>
-int mask_and_place(icp_ctx *ctx, DevTemp &tmp, const double *aos, size_t n, const double *mean, const double *stats,
+int mask_and_place(icp_ctx *ctx, Scratch &tmp, const double *aos, size_t n, const double *mean, const double *stats,
                    const int *cnt, int min_nb, double *out_dev, unsigned char *mask_dev, size_t *kept)
 {
     const int nt = blocks_for(n, kFilterTile);
     unsigned char *mask = nullptr;
     int *bcount = nullptr;
-    HIPCHK(tmp.get(&mask, n));
-    HIPCHK(tmp.get(&bcount, (size_t)nt + 1));
+    TRY(tmp.get(&mask, n));
+    TRY(tmp.get(&bcount, (size_t)nt + 1));
     filter_mask_count_kernel<kStat><<<nt, kBlock, 0, ctx->st>>>(mean, stats, cnt, min_nb, (int)n, mask, bcount);
     filter_scan_kernel<<<1, 1024, 0, ctx->st>>>(bcount, nt, bcount + nt);
     LAUNCHCHK("filter_mask");
@@ -383,21 +356,19 @@ struct PhaseClock {
 // both forms of the statistical filter, every array in device memory (out, mask, mean: nullable)
 int statistical_dev(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, int k, double std_ratio,
                     double *out_dev, unsigned char *mask_dev, size_t *n_out, double *mean_dev, double stats_out[3],
-                    DevTemp &tmp)
+                    Scratch &tmp)
 {
-    double *mean = nullptr, *part = nullptr, *stats = nullptr, *soa = nullptr;
-    HIPCHK(tmp.get(&soa, 3 * n));
-    HIPCHK(tmp.get(&mean, n));
-    HIPCHK(tmp.get(&part, 2 * ((size_t)blocks_for(n, kFilterChunk) + 1)));
-    HIPCHK(tmp.get(&stats, 3));
-    TempGrid tg; // (its arrays are the context's filt_grid: nothing to free)
+    double *mean = nullptr, *part = nullptr, *stats = nullptr;
+    TRY(tmp.get(&mean, n));
+    TRY(tmp.get(&part, 2 * ((size_t)blocks_for(n, kFilterChunk) + 1)));
+    TRY(tmp.get(&stats, 3));
+    TempGrid tg;
     PhaseClock clock;
-    int budget = 0;
     clock.mark(ctx->st);
-    TRY(cloud_grid(ctx, who, aos, n, tg, &budget, soa));
+    TRY(cloud_grid(ctx, who, aos, n, tmp, tg));
     clock.mark(ctx->st);
     knn_mean_dist_kernel<<<blocks_for(n, kKnnBlock), kKnnBlock, knn_lds_bytes(k + 1), ctx->st>>>(tg.gv, (int)n, k + 1,
-                                                                                                   budget, mean);
+                                                                                                   tg.budget, mean);
     LAUNCHCHK("knn_mean_dist");
     clock.mark(ctx->st);
     const double *s0 = sum_levels<false>(mean, (int)n, nullptr, part, ctx->st);
@@ -419,23 +390,20 @@ int statistical_dev(icp_ctx *ctx, const std::string &who, const double *aos, siz
 }
 
 int radius_dev(icp_ctx *ctx, const std::string &who, const double *aos, size_t n, double radius, int min_neighbors,
-               double *out_dev, unsigned char *mask_dev, size_t *n_out, int32_t *count_dev, DevTemp &tmp)
+               double *out_dev, unsigned char *mask_dev, size_t *n_out, int32_t *count_dev, Scratch &tmp)
 {
     int *cnt = nullptr;
-    double *soa = nullptr;
-    HIPCHK(tmp.get(&soa, 3 * n));
-    HIPCHK(tmp.get(&cnt, n));
-    TempGrid tg; // (its arrays are the context's filt_grid: nothing to free)
+    TRY(tmp.get(&cnt, n));
+    TempGrid tg;
     PhaseClock clock;
-    int budget = 0;
     clock.mark(ctx->st);
-    TRY(cloud_grid(ctx, who, aos, n, tg, &budget, soa));
+    TRY(cloud_grid(ctx, who, aos, n, tmp, tg));
     clock.mark(ctx->st);
     const double r2 = radius * radius; // (once, here)
     const double R = std::max(radius, std::sqrt(r2));
     // (min_neighbors + 1 hits decide the mask; the full counts only when they are asked for)
     const int limit = count_dev || min_neighbors >= INT_MAX - 1 ? INT_MAX : min_neighbors + 1;
-    radius_count_kernel<<<blocks_for(n, kBlock), kBlock, 0, ctx->st>>>(tg.gv, (int)n, R, r2, budget, limit, cnt);
+    radius_count_kernel<<<blocks_for(n, kBlock), kBlock, 0, ctx->st>>>(tg.gv, (int)n, R, r2, tg.budget, limit, cnt);
     LAUNCHCHK("radius_count");
     clock.mark(ctx->st);
     size_t kept = 0;
@@ -455,11 +423,11 @@ struct HostStage {
     unsigned char *mask = nullptr;
 };
 
-int stage_in(icp_ctx *ctx, DevTemp &tmp, const double *xyz, size_t n, bool want_out, bool want_mask, HostStage &hs)
+int stage_in(icp_ctx *ctx, Scratch &tmp, const double *xyz, size_t n, bool want_out, bool want_mask, HostStage &hs)
 {
-    HIPCHK(tmp.get(&hs.in, 3 * n));
-    if (want_out) HIPCHK(tmp.get(&hs.out, 3 * n));
-    if (want_mask) HIPCHK(tmp.get(&hs.mask, n));
+    TRY(tmp.get(&hs.in, 3 * n));
+    if (want_out) TRY(tmp.get(&hs.out, 3 * n));
+    if (want_mask) TRY(tmp.get(&hs.mask, n));
     HIPCHK(hipMemcpyAsync(hs.in, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
     return ICP_OK;
 }
@@ -488,8 +456,7 @@ int icp_filter_statistical_device(icp_ctx *ctx, const double *xyz_dev, size_t n,
     TRY(statistical_args(ctx, who, xyz_dev, n, k, std_ratio, n_out));
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize()); // (the array is read after the work of any stream, as icp_set_model_device's)
-    DevTemp tmp;
-    TRY(tmp.begin(ctx, n));
+    Scratch tmp(ctx, &ctx->filt_block); // (kept for the next filter call)
     return statistical_dev(ctx, who, xyz_dev, n, k, std_ratio, out_xyz_dev, mask_out_dev, n_out, mean_dist_out_dev,
                            stats_out, tmp);
 }
@@ -502,12 +469,11 @@ int icp_filter_statistical(icp_ctx *ctx, const double *xyz, size_t n, int k, dou
     TRY(statistical_args(ctx, who, xyz, n, k, std_ratio, n_out));
     TRY(finite_cloud(ctx, who, xyz, n));
     HIPCHK(hipSetDevice(ctx->device));
-    DevTemp tmp;
-    TRY(tmp.begin(ctx, n));
+    Scratch tmp(ctx, &ctx->filt_block); // (kept for the next filter call)
     HostStage hs;
     double *mean = nullptr;
     TRY(stage_in(ctx, tmp, xyz, n, out_xyz != nullptr, mask_out != nullptr, hs));
-    if (mean_dist_out) HIPCHK(tmp.get(&mean, n));
+    if (mean_dist_out) TRY(tmp.get(&mean, n));
     size_t kept = 0;
     double stats[3];
     TRY(statistical_dev(ctx, who, hs.in, n, k, std_ratio, hs.out, hs.mask, &kept, mean, stats, tmp));
@@ -526,8 +492,7 @@ int icp_filter_radius_device(icp_ctx *ctx, const double *xyz_dev, size_t n, doub
     TRY(radius_args(ctx, who, xyz_dev, n, radius, min_neighbors, n_out));
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize()); // (as above)
-    DevTemp tmp;
-    TRY(tmp.begin(ctx, n));
+    Scratch tmp(ctx, &ctx->filt_block); // (kept for the next filter call)
     return radius_dev(ctx, who, xyz_dev, n, radius, min_neighbors, out_xyz_dev, mask_out_dev, n_out, count_out_dev, tmp);
 }
 
@@ -539,12 +504,11 @@ int icp_filter_radius(icp_ctx *ctx, const double *xyz, size_t n, double radius, 
     TRY(radius_args(ctx, who, xyz, n, radius, min_neighbors, n_out));
     TRY(finite_cloud(ctx, who, xyz, n));
     HIPCHK(hipSetDevice(ctx->device));
-    DevTemp tmp;
-    TRY(tmp.begin(ctx, n));
+    Scratch tmp(ctx, &ctx->filt_block); // (kept for the next filter call)
     HostStage hs;
     int32_t *cnt = nullptr;
     TRY(stage_in(ctx, tmp, xyz, n, out_xyz != nullptr, mask_out != nullptr, hs));
-    if (count_out) HIPCHK(tmp.get(&cnt, n));
+    if (count_out) TRY(tmp.get(&cnt, n));
     size_t kept = 0;
     TRY(radius_dev(ctx, who, hs.in, n, radius, min_neighbors, hs.out, hs.mask, &kept, cnt, tmp));
     TRY(stage_out(ctx, hs, n, kept, out_xyz, mask_out));

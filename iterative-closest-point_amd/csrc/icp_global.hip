@@ -2,8 +2,8 @@
 // descriptor of every row of one set in another, a rigid pose from putative pairs by RANSAC, and
 // the chain of the three (icp_fpfh, icp_match_features, icp_ransac_pose, icp_global_pose;
 // include/icp_capi.h states every rule).  The four calls take host arrays, are synchronous, keep
-// their device memory to themselves (allocated and freed inside the call) and touch neither the
-// resident clouds nor anything a run depends on.
+// their device memory to themselves (an owning Scratch, icp_engine.h: allocated and freed inside the call)
+// and touch neither the resident clouds nor anything a run depends on.  icp_fpfh's grid: cloud_knn, icp_cloud.hip.
 //
 // Kernels (all fp64 as written, -ffp-contract=off; no floating-point atomic anywhere):
 //   spfh_kernel          one wave a point, one list entry a lane: the pair feature of (i, N_i[lane]),
@@ -30,7 +30,6 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "icp_engine.h"
@@ -375,39 +374,15 @@ __global__ __launch_bounds__(256) void ransac_mask_kernel(RansacArgs A, const un
     mask[c] = ransac_inlier(A, R, c) ? 1 : 0;
 }
 
-// device memory of one call: freed when the call returns, whatever it returns
-struct DevTemp {
-    std::vector<void *> p;
-    ~DevTemp()
-    {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-    }
-    template <class T> hipError_t get(T **out, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * (count ? count : 1));
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T *)q;
-        return e;
-    }
-};
-
-bool all_finite(const double *v, size_t n)
+// what icp_ransac_pose refuses of its three parameters (icp_global_pose: before anything runs)
+int ransac_args(icp_ctx *ctx, const std::string &who, long long hypotheses, double max_dist, double edge_ratio)
 {
-    for (size_t k = 0; k < n; ++k)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
-int knn_k_check(icp_ctx *ctx, const std::string &who, const char *name, int k, size_t n)
-{
-    if (k < kKnnMinK || k > kKnnMaxK)
-        return fail(ctx, ICP_E_ARG, who + ": " + name + " = " + std::to_string(k) + " is outside [" +
-                                        std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
-    if ((size_t)k > n)
-        return fail(ctx, ICP_E_ARG, who + ": " + name + " = " + std::to_string(k) + " exceeds the cloud's " +
-                                        std::to_string(n) + " points");
+    if (hypotheses < 1 || hypotheses >= (1LL << 32))
+        return fail(ctx, ICP_E_ARG, who + ": hypotheses = " + std::to_string(hypotheses) + " is outside [1, 2^32)");
+    if (!std::isfinite(max_dist) || !(max_dist > 0.0))
+        return fail(ctx, ICP_E_ARG, who + ": max_dist = " + std::to_string(max_dist) + " is not finite and > 0");
+    if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0))
+        return fail(ctx, ICP_E_ARG, who + ": edge_ratio = " + std::to_string(edge_ratio) + " is outside [0, 1]");
     return ICP_OK;
 }
 
@@ -423,29 +398,30 @@ int icp_fpfh(icp_ctx *ctx, const double *xyz, size_t n, const double *normals, i
     if (!xyz || !fpfh_out) return fail(ctx, ICP_E_ARG, who + ": xyz or fpfh_out is null");
     if (n == 0 || n > (size_t)INT_MAX)
         return fail(ctx, ICP_E_ARG, who + ": n = " + std::to_string(n) + " is outside [1, INT_MAX]");
-    TRY(knn_k_check(ctx, who, "k", k, n));
+    TRY(knn_k_check(ctx, who, "k", k, "cloud", n));
     if (!normals) {
-        TRY(knn_k_check(ctx, who, "k_normals", k_normals, n));
-        if (viewpoint && !all_finite(viewpoint, 3)) return fail(ctx, ICP_E_ARG, who + ": the viewpoint is not finite");
-    } else if (!all_finite(normals, 3 * n)) {
+        TRY(knn_k_check(ctx, who, "k_normals", k_normals, "cloud", n));
+        if (viewpoint && first_nonfinite(viewpoint, 3) != kAllFinite)
+            return fail(ctx, ICP_E_ARG, who + ": the viewpoint is not finite");
+    } else if (first_nonfinite(normals, 3 * n) != kAllFinite) {
         return fail(ctx, ICP_E_ARG, who + ": a normal is not finite");
     }
     HIPCHK(hipSetDevice(ctx->device));
-    DevTemp tmp;
+    Scratch tmp(ctx); // (owning: freed when the call returns, whatever it returns)
     const size_t nk = n * (size_t)k;
     double *aos = nullptr, *d2 = nullptr, *spfh = nullptr, *fpfh = nullptr, *naos = nullptr;
     double4 *rows = nullptr, *nrm = nullptr;
     int *idx = nullptr;
-    HIPCHK(tmp.get(&aos, 3 * n));
-    HIPCHK(tmp.get(&rows, n));
-    HIPCHK(tmp.get(&nrm, n));
-    HIPCHK(tmp.get(&idx, nk));
-    HIPCHK(tmp.get(&d2, nk));
-    HIPCHK(tmp.get(&spfh, n * kDim));
-    HIPCHK(tmp.get(&fpfh, n * kDim));
+    TRY(tmp.get(&aos, 3 * n));
+    TRY(tmp.get(&rows, n));
+    TRY(tmp.get(&nrm, n));
+    TRY(tmp.get(&idx, nk));
+    TRY(tmp.get(&d2, nk));
+    TRY(tmp.get(&spfh, n * kDim));
+    TRY(tmp.get(&fpfh, n * kDim));
     HIPCHK(hipMemcpyAsync(aos, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
     if (normals) {
-        HIPCHK(tmp.get(&naos, 3 * n));
+        TRY(tmp.get(&naos, 3 * n));
         HIPCHK(hipMemcpyAsync(naos, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
         launch_plane_normals4(naos, (int)n, nrm, ctx->st);
         LAUNCHCHK("fpfh_normals4");
@@ -465,9 +441,7 @@ int icp_fpfh(icp_ctx *ctx, const double *xyz, size_t n, const double *normals, i
     HIPCHK(hipStreamSynchronize(ctx->st));
     HIPCHK(hipMemcpy(fpfh_out, fpfh, sizeof(double) * n * kDim, hipMemcpyDeviceToHost));
     if (spfh_out) HIPCHK(hipMemcpy(spfh_out, spfh, sizeof(double) * n * kDim, hipMemcpyDeviceToHost));
-    if (normals_out)
-        for (size_t j = 0; j < n; ++j)
-            for (int a = 0; a < 3; ++a) normals_out[3 * j + a] = h_nrm[4 * j + a];
+    if (normals_out) rows4_to_xyz(h_nrm.data(), n, normals_out);
     return ICP_OK;
 }
 
@@ -483,15 +457,15 @@ int icp_match_features(icp_ctx *ctx, const double *fa, size_t na, const double *
     HIPCHK(hipSetDevice(ctx->device));
     int chunk = 0, splits = 0;
     match_plan(na, nb, &chunk, &splits);
-    DevTemp tmp;
+    Scratch tmp(ctx); // (owning: freed when the call returns, whatever it returns)
     double *da = nullptr, *db = nullptr, *part_d = nullptr, *dist = nullptr;
     int *part_i = nullptr, *idx = nullptr;
-    HIPCHK(tmp.get(&da, na * kDim));
-    HIPCHK(tmp.get(&db, nb * kDim));
-    HIPCHK(tmp.get(&part_d, na * (size_t)splits));
-    HIPCHK(tmp.get(&part_i, na * (size_t)splits));
-    HIPCHK(tmp.get(&idx, na));
-    HIPCHK(tmp.get(&dist, na));
+    TRY(tmp.get(&da, na * kDim));
+    TRY(tmp.get(&db, nb * kDim));
+    TRY(tmp.get(&part_d, na * (size_t)splits));
+    TRY(tmp.get(&part_i, na * (size_t)splits));
+    TRY(tmp.get(&idx, na));
+    TRY(tmp.get(&dist, na));
     HIPCHK(hipMemcpyAsync(da, fa, sizeof(double) * na * kDim, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemcpyAsync(db, fb, sizeof(double) * nb * kDim, hipMemcpyHostToDevice, ctx->st));
     const dim3 grid((unsigned)((na + kMatchBlock - 1) / kMatchBlock), (unsigned)splits);
@@ -522,29 +496,25 @@ int icp_ransac_pose(icp_ctx *ctx, const double *p_xyz, const double *q_xyz, size
     if (!p_xyz || !q_xyz || !R || !t || !inliers || !best_h)
         return fail(ctx, ICP_E_ARG, who + ": p_xyz, q_xyz, R, t, inliers or best_h is null");
     if (C < 3 || C > (size_t)INT_MAX) return fail(ctx, ICP_E_ARG, who + ": C = " + std::to_string(C) + " is outside [3, INT_MAX]");
-    if (hypotheses < 1 || hypotheses >= (1LL << 32))
-        return fail(ctx, ICP_E_ARG, who + ": hypotheses = " + std::to_string(hypotheses) + " is outside [1, 2^32)");
-    if (!std::isfinite(max_dist) || !(max_dist > 0.0))
-        return fail(ctx, ICP_E_ARG, who + ": max_dist = " + std::to_string(max_dist) + " is not finite and > 0");
-    if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0))
-        return fail(ctx, ICP_E_ARG, who + ": edge_ratio = " + std::to_string(edge_ratio) + " is outside [0, 1]");
-    if (!all_finite(p_xyz, 3 * C) || !all_finite(q_xyz, 3 * C)) return fail(ctx, ICP_E_ARG, who + ": a point is not finite");
+    TRY(ransac_args(ctx, who, hypotheses, max_dist, edge_ratio));
+    if (first_nonfinite(p_xyz, 3 * C) != kAllFinite || first_nonfinite(q_xyz, 3 * C) != kAllFinite)
+        return fail(ctx, ICP_E_ARG, who + ": a point is not finite");
     HIPCHK(hipSetDevice(ctx->device));
-    DevTemp tmp;
+    Scratch tmp(ctx); // (owning: freed when the call returns, whatever it returns)
     double *dp = nullptr, *dq = nullptr, *pose = nullptr, *win = nullptr;
     int *counts = nullptr, *hyp = nullptr, *nsurv = nullptr;
     unsigned long long *best = nullptr;
     unsigned char *mask = nullptr;
     const int batch = (int)std::min<long long>(hypotheses, kRansacBatch);
-    HIPCHK(tmp.get(&dp, 3 * C));
-    HIPCHK(tmp.get(&dq, 3 * C));
-    HIPCHK(tmp.get(&pose, (size_t)batch * kPose));
-    HIPCHK(tmp.get(&win, (size_t)kPose));
-    HIPCHK(tmp.get(&counts, (size_t)batch));
-    HIPCHK(tmp.get(&hyp, (size_t)batch));
-    HIPCHK(tmp.get(&nsurv, (size_t)1));
-    HIPCHK(tmp.get(&best, (size_t)1));
-    HIPCHK(tmp.get(&mask, C));
+    TRY(tmp.get(&dp, 3 * C));
+    TRY(tmp.get(&dq, 3 * C));
+    TRY(tmp.get(&pose, (size_t)batch * kPose));
+    TRY(tmp.get(&win, (size_t)kPose));
+    TRY(tmp.get(&counts, (size_t)batch));
+    TRY(tmp.get(&hyp, (size_t)batch));
+    TRY(tmp.get(&nsurv, (size_t)1));
+    TRY(tmp.get(&best, (size_t)1));
+    TRY(tmp.get(&mask, C));
     HIPCHK(hipMemcpyAsync(dp, p_xyz, sizeof(double) * 3 * C, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemcpyAsync(dq, q_xyz, sizeof(double) * 3 * C, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemsetAsync(best, 0, sizeof(unsigned long long), ctx->st));
@@ -609,16 +579,10 @@ int icp_global_pose(icp_ctx *ctx, const double *m_xyz, size_t nm, const double *
     const double max_dist = prm->max_dist != 0.0 ? prm->max_dist : 1.5 * prm->voxel;
     const double edge_ratio = prm->edge_ratio != 0.0 ? prm->edge_ratio : 0.9;
     // every value the later calls would refuse, before anything runs
-    for (const auto &kv : {std::make_pair("k_normals", k_normals), std::make_pair("k_fpfh", k_fpfh)})
-        if (kv.second < kKnnMinK || kv.second > kKnnMaxK)
-            return fail(ctx, ICP_E_ARG, who + ": " + kv.first + " = " + std::to_string(kv.second) + " is outside [" +
-                                            std::to_string(kKnnMinK) + ", " + std::to_string(kKnnMaxK) + "]");
-    if (hypotheses < 1 || hypotheses >= (1LL << 32))
-        return fail(ctx, ICP_E_ARG, who + ": hypotheses = " + std::to_string(hypotheses) + " is outside [1, 2^32)");
-    if (!std::isfinite(max_dist) || !(max_dist > 0.0))
-        return fail(ctx, ICP_E_ARG, who + ": max_dist = " + std::to_string(max_dist) + " is not finite and > 0");
-    if (!(edge_ratio >= 0.0 && edge_ratio <= 1.0))
-        return fail(ctx, ICP_E_ARG, who + ": edge_ratio = " + std::to_string(edge_ratio) + " is outside [0, 1]");
+    // (the range alone: the levels' sizes are not known yet)
+    TRY(knn_k_check(ctx, who, "k_normals", k_normals, "cloud", SIZE_MAX));
+    TRY(knn_k_check(ctx, who, "k_fpfh", k_fpfh, "cloud", SIZE_MAX));
+    TRY(ransac_args(ctx, who, hypotheses, max_dist, edge_ratio));
     std::vector<double> mc(3 * nm), pc(3 * np);
     size_t cm = 0, cp = 0;
     TRY(icp_voxel_downsample(ctx, m_xyz, nm, prm->voxel, nullptr, mc.data(), nullptr, &cm));

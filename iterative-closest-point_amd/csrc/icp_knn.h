@@ -1,7 +1,7 @@
 // icp_knn.h -- the exact grid k-NN's device half: a lane's sorted (d2, index) list in LDS and the search
 // that fills it.  Shared by the kernels of icp_normals.hip (the lists, the normals) and
-// icp_filter.hip (the statistical filter's mean distances); the rules and the bounds of every loop are
-// stated at the head of icp_normals.hip.  Compiled with -ffp-contract=off.
+// icp_filter.hip (the statistical filter's mean distances), whose grids icp_cloud.hip builds; the rules and
+// the bounds of every loop are stated at the head of icp_normals.hip.  Compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
