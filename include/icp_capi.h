@@ -607,6 +607,75 @@ int icp_filter_radius(icp_ctx *ctx, const double *xyz, size_t n, double radius, 
 int icp_filter_radius_device(icp_ctx *ctx, const double *xyz_dev, size_t n, double radius, int min_neighbors,
                              double *out_xyz_dev, uint8_t *mask_out_dev, size_t *n_out, int32_t *count_out_dev);
 
+/* ---- a registration evaluated: fitness, inlier RMSE, the information matrix --- */
+/* How good the pose reached is: Open3D's evaluate_registration and
+ * get_information_matrix_from_point_clouds, PCL's getFitnessScore.  The call works on the resident model
+ * and the resident scene AS IT LIES NOW: after every applied iteration of an icp_run and every
+ * icp_transform_scene; the coordinates are the caller's.  (icp_run's err is the kept pairs' error of its
+ * last iteration BEFORE the last step is applied, under that run's gate, trim and weights; this call
+ * applies none of them.)
+ *
+ * 1. Distance.  d2(a, b) = (dx*dx + dy*dy) + dz*dz in fp64, exactly as written: the gate's own d2.  The
+ *    nearest-neighbour rule is always the squared-distance first minimum, whatever icp_set_nn_rule and
+ *    the context's nn_mode say.
+ * 2. Forward pair.  D = max_dist * max_dist, the product taken once on the host; max_dist = +inf gives
+ *    D = +inf.  For scene point j, i_j is the lowest index among the model points that minimise d2 and
+ *    d2_j that minimum.  Pair j is kept iff d2_j <= D.  A kept point has idx_out[j] = i_j and
+ *    d2_out[j] = d2_j; a point that is not kept has idx_out[j] = -1 and d2_out[j] = +inf (Open3D's
+ *    correspondence set: a point with nothing within max_dist has no pair).  Both arrays are nullable,
+ *    hold np entries and are in the caller's point order.
+ *    With a finite max_dist a point far from the model costs the scan of a small box of cells.  With
+ *    max_dist = +inf a point far outside the model's box scans every model point (its completeness box is
+ *    over the cell budget): a scene of a million points with a far clump is far too slow at +inf; give
+ *    such a scene a finite max_dist.
+ * 3. Forward summary.  K is the number of kept pairs; fitness = K / np, one fp64 division;
+ *    inlier_rmse = sqrt(S(t) / K) with t_j = d2_j for a kept pair and +0 otherwise; max_inlier_d2 is the
+ *    maximum of the kept d2.  With K == 0 the last two are 0.
+ * 4. Information matrix (Open3D's).  With y = m[i_j] = (x, y, z) as the caller gave it,
+ *    A = sum over the kept pairs of G_j^T G_j, the rows of G_j being (0, z, -y, 1, 0, 0),
+ *    (-z, 0, x, 0, 1, 0) and (y, -x, 0, 0, 0, 1).  It is formed from nine S-sums over the caller's order:
+ *    Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz; each product is rounded first and a pair that is not kept
+ *    contributes +0.  A00 = Syy + Szz, A11 = Sxx + Szz, A22 = Sxx + Syy; A01 = -Sxy, A02 = -Sxz,
+ *    A12 = -Syz; A04 = -Sz, A05 = Sy, A13 = Sz, A15 = -Sx, A23 = -Sy, A24 = Sx; A33 = A44 = A55 = K.  A is
+ *    symmetric and every other entry is 0.  information[] is row-major, the rotation block first.
+ * 5. Sum order.  S is the filters' sum rule (icp_filter_statistical's rule 3 above), over the np (or nm)
+ *    terms in the caller's point order.  No floating-point atomics: two calls give the same bits, and so
+ *    do the host and the device form.  (K and the maximum are integer atomics: a non-negative double
+ *    orders as its bit pattern.)
+ * 6. Reverse direction (both != 0): the same with the roles exchanged.  For model point i the lowest
+ *    caller's-order index among the scene points that minimise d2; model_idx_out and model_d2_out
+ *    (nullable, nm entries, the model's order), K_m, model_fitness = K_m / nm, model_rmse and
+ *    model_max_inlier_d2.  In partial overlap the scene can sit wholly on the model with fitness 1; the
+ *    model's fitness says how much of the model it covers.  There is no second information matrix.  With
+ *    both == 0 the five model fields are 0 and a non-null model_* array is ICP_E_ARG.
+ * 7. Effects.  The call is synchronous, writes its outputs only once everything has run and changes
+ *    nothing that a run or a report depends on: an icp_run after it returns the same bits as that run
+ *    without it (the result, the error trace, icp_get_scene, icp_get_transform), and icp_get_indices,
+ *    icp_get_inliers and the traces answer as before.  Its device memory is scratch of the context, kept
+ *    for the next evaluation (a second call at the same sizes allocates nothing) and freed with it.
+ * 8. Errors.  Nothing has run and nothing is written; icp_last_error names the value.  ICP_E_ARG: a null
+ *    context; a null out; max_dist that is NaN or not > 0; rule 6's case; a context of more than one rank
+ *    (the reverse minimum over shards would be a min-reduction: refused, as the one-to-one rejection
+ *    refuses ranks).  ICP_E_NO_MODEL: no model or no scene.  The clouds' sizes need not be equal and no
+ *    minimum count applies: those are icp_run's checks, not this call's.
+ * The device form takes the four per-point arrays in device memory; out stays a host pointer. */
+typedef struct icp_evaluation {
+    long long scene_points;          /* np */
+    long long correspondences;       /* K */
+    double fitness;                  /* K / np */
+    double inlier_rmse;              /* sqrt(S(d2 of the kept) / K); 0 when K == 0 */
+    double max_inlier_d2;            /* the largest kept d2; 0 when K == 0 */
+    double information[36];          /* row-major 6 x 6, rotation block first */
+    long long model_points;          /* nm; this and the four below are 0 unless both != 0 */
+    long long model_correspondences; /* K_m */
+    double model_fitness, model_rmse, model_max_inlier_d2;
+} icp_evaluation;
+
+int icp_evaluate(icp_ctx *ctx, double max_dist, int both, icp_evaluation *out, int32_t *idx_out, double *d2_out,
+                 int32_t *model_idx_out, double *model_d2_out);
+int icp_evaluate_device(icp_ctx *ctx, double max_dist, int both, icp_evaluation *out, int32_t *idx_out_dev,
+                        double *d2_out_dev, int32_t *model_idx_out_dev, double *model_d2_out_dev);
+
 /* ---- global registration: FPFH descriptors, feature matches, a RANSAC pose ---- */
 /* What a scene that does NOT start near its answer needs before icp_run: a pose from local shape
  * descriptors (Rusu, Blodow and Beetz, "Fast Point Feature Histograms (FPFH) for 3D Registration", ICRA

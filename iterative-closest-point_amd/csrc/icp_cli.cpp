@@ -70,10 +70,17 @@
 //   --ror RADIUS,MIN   radius outlier removal (icp_filter_radius), likewise and after --sor when both are given:
 //                      a point stays when at least MIN other points lie within RADIUS (RADIUS > 0, MIN >= 0);
 //                      one "[ror] model|scene N points, kept M" line per cloud
+//   --evaluate DIST    after the run (and after --global / --pyramid) the registration evaluated (icp_evaluate): the
+//                      scene points with a model point within DIST (> 0, or inf) are the inliers; one "[evaluate]
+//                      scene K of N within DIST, fitness .. inlier RMSE .. largest kept distance .." line goes to stderr
+//   --evaluate-both    the model's side too: a second "[evaluate] model ..." line (needs --evaluate)
+//   --write-information FILE  the 6 x 6 information matrix of the kept pairs (rotation block first), six
+//                      comma-separated rows of 6 significant digits (needs --evaluate)
 //   --write-transform FILE  the total transform q = s R p + t (icp_get_transform) as a 4 x 4 matrix
 //                      [sR t; 0 0 0 1], four comma-separated rows of 6 significant digits
 //   --out PATH         output file (default output.txt, src/load.cc:71)
 //   --device D         HIP device ordinal (default 0)
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -117,7 +124,8 @@ int main(int argc, char **argv)
                     "[--symmetric | --gicp [--gicp-epsilon E]] [--scene-normals FILE | --estimate-scene-normals K] [--write-scene-normals FILE] "
                     "[--robust huber|tukey|cauchy --robust-k K] [--threshold X] [--pyramid H1[,H2,...]] "
                     "[--pyramid-iters K] [--global H [--global-k K] [--global-normals-k K] [--global-hyp N] [--global-seed S] "
-                    "[--global-dist X]] [--sor K,RATIO] [--ror RADIUS,MIN] [--write-transform FILE] [--out PATH]\n");
+                    "[--global-dist X]] [--sor K,RATIO] [--ror RADIUS,MIN] [--evaluate DIST [--evaluate-both] [--write-information FILE]] "
+                    "[--write-transform FILE] [--out PATH]\n");
         return -1;
     }
     const int max_iter = std::atoi(argv[3]);
@@ -133,6 +141,8 @@ int main(int argc, char **argv)
     const char *pyramid = nullptr, *pyramid_iters = nullptr, *write_transform = nullptr;
     const char *global = nullptr, *global_k = nullptr, *global_nk = nullptr, *global_hyp = nullptr, *global_seed = nullptr;
     const char *global_dist = nullptr, *sor = nullptr, *ror = nullptr;
+    const char *evaluate = nullptr, *write_information = nullptr;
+    bool evaluate_both = false;
     for (int a = 4; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--allow-unequal")) allow_unequal = true;
         else if (!std::strcmp(argv[a], "--nn") && a + 1 < argc) {
@@ -166,6 +176,9 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--global-dist") && a + 1 < argc) global_dist = argv[++a];
         else if (!std::strcmp(argv[a], "--sor") && a + 1 < argc) sor = argv[++a];
         else if (!std::strcmp(argv[a], "--ror") && a + 1 < argc) ror = argv[++a];
+        else if (!std::strcmp(argv[a], "--evaluate") && a + 1 < argc) evaluate = argv[++a];
+        else if (!std::strcmp(argv[a], "--evaluate-both")) evaluate_both = true;
+        else if (!std::strcmp(argv[a], "--write-information") && a + 1 < argc) write_information = argv[++a];
         else if (!std::strcmp(argv[a], "--write-transform") && a + 1 < argc) write_transform = argv[++a];
         else if (!std::strcmp(argv[a], "--out") && a + 1 < argc) out = argv[++a];
         else if (!std::strcmp(argv[a], "--device") && a + 1 < argc) device = std::atoi(argv[++a]);
@@ -372,6 +385,20 @@ int main(int argc, char **argv)
         return -1;
     }
 
+    // the evaluation's options: a distance > 0 (inf: every pair), and what needs it
+    double eval_dist = 0.0;
+    if (evaluate) {
+        char *end = nullptr;
+        eval_dist = std::strtod(evaluate, &end);
+        if (end == evaluate || *end || !(eval_dist > 0.0)) {
+            std::fprintf(stderr, "[error] --evaluate: %s is not a distance > 0 (or inf)\n", evaluate);
+            return -1;
+        }
+    } else if (evaluate_both || write_information) {
+        std::fprintf(stderr, "[error] --evaluate-both and --write-information need --evaluate\n");
+        return -1;
+    }
+
     size_t nm = 0, np = 0;
     double *m = load_or_exit(argv[1], &nm);
     double *p = load_or_exit(argv[2], &np);
@@ -463,10 +490,37 @@ int main(int argc, char **argv)
         std::fclose(f);
         return 0;
     };
+    // --evaluate: the registration as it ends, its line(s) and --write-information's matrix in the CSV style
+    const auto evaluate_now = [&]() {
+        icp_evaluation ev{};
+        if ((rc = icp_evaluate(ctx, eval_dist, evaluate_both ? 1 : 0, &ev, nullptr, nullptr, nullptr, nullptr)) != ICP_OK)
+            return die("--evaluate");
+        std::fprintf(stderr, "[evaluate] scene %lld of %lld within %g, fitness %g inlier RMSE %g largest kept distance %g\n",
+                     ev.correspondences, ev.scene_points, eval_dist, ev.fitness, ev.inlier_rmse, std::sqrt(ev.max_inlier_d2));
+        if (evaluate_both)
+            std::fprintf(stderr, "[evaluate] model %lld of %lld within %g, fitness %g inlier RMSE %g largest kept distance %g\n",
+                         ev.model_correspondences, ev.model_points, eval_dist, ev.model_fitness, ev.model_rmse,
+                         std::sqrt(ev.model_max_inlier_d2));
+        if (write_information) {
+            FILE *f = std::fopen(write_information, "w");
+            bool ok = f != nullptr;
+            for (int r = 0; ok && r < 6; ++r) {
+                const double *a = ev.information + 6 * r;
+                ok = std::fprintf(f, "%g,%g,%g,%g,%g,%g\n", a[0], a[1], a[2], a[3], a[4], a[5]) > 0;
+            }
+            if (f && std::fclose(f) != 0) ok = false; // (a full disk shows here at the latest)
+            if (!ok) {
+                std::fprintf(stderr, "[error] cannot write %s\n", write_information);
+                return 2;
+            }
+        }
+        return 0;
+    };
     // What a run ends with: the files asked for, the moved scene, the [output] line.  get_scene: how a
     // failing icp_get_scene is named (null: not at all).
     const auto finish = [&](double *errs, const char *get_scene) {
         int w = 0;
+        if (evaluate && (w = evaluate_now()) != 0) return w;
         if (write_scene_normals &&
             (w = write_normals_file("--write-scene-normals", icp_get_scene_normals, np, write_scene_normals)) != 0)
             return w;

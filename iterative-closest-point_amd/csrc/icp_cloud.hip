@@ -15,7 +15,15 @@ namespace engine {
 Scratch::~Scratch()
 {
     for (void *q : own) (void)hipFree(q);
-    if (kept && begun) kept->want = total;
+    if (!kept || !begun) return;
+    kept->want = total;
+    // The call did not fit: the block grown to its total now, not at the next call's start, so that the
+    // next call at these sizes allocates nothing.  (Every caller has synchronised, or hipFree above has; a
+    // failure leaves an empty block, which the next object grows again, and the call's own status and message.)
+    if (kept->cap < total) {
+        const std::string err = ctx->err;
+        if (grow(ctx, &kept->base, &kept->cap, total) != ICP_OK) ctx->err = err;
+    }
 }
 
 int Scratch::get_bytes(void **out, size_t bytes)

@@ -1,7 +1,8 @@
 // icp_engine.h — private to the engine's translation units: icp_engine.hip (the context, the
 // model and scene set-up, the searches, the per-operation surface), icp_run.hip (icp_run's
 // loops), icp_cloud.hip (the normals, the k-NN lists and the temporary grid of a cloud),
-// icp_global.hip (global registration's four calls) and icp_filter.hip (the outlier filters).  The
+// icp_global.hip (global registration's four calls), icp_filter.hip (the outlier filters) and
+// icp_eval.hip (a registration's evaluation).  The
 // context, the few types they share, the error macros, the run path's knob table and the
 // declarations of the helpers one file calls in another.  The helpers are icp::engine
 // and hidden: the shared library exports the C ABI (include/icp_capi.h) and nothing of this.
@@ -367,6 +368,9 @@ struct icp_ctx {
     // own, the staged clouds -- is a part of this one block (Scratch's kept mode), kept between calls: a
     // call's dozen allocations cost as much as its kernels
     KeptBlock filt_block;
+    // icp_evaluate* (icp_eval.hip): likewise, a block of its own -- the per-point pairs, the sums' terms,
+    // the queries' rows and, with `both`, the scene's temporary grid
+    KeptBlock eval_block;
 
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     icp_stats stats{};
@@ -546,9 +550,10 @@ int grid_budget_for(size_t n);
 // The device arrays of one call on a cloud that is not the resident model; they go, or may be handed out
 // again, with the object.  Owning (kept null): every get is a hipMalloc, freed with the object.  Kept,
 // over a block of the context's: a get is a 256-byte-aligned part of the block while it fits and an
-// allocation of the object's own when it does not; the object leaves the call's total in the block, and
-// the next object over it grows the block to that, once, before it hands anything out -- so a call at the
-// size of the one before it allocates nothing.  A count of 0 yields a valid pointer.
+// allocation of the object's own when it does not; as it goes, the object leaves the call's total in the
+// block and, when the call did not fit, grows the block to that total (should that fail, the next object
+// over it does, once, before it hands anything out) -- so the second call at a size, and every call at the
+// size of the one before it, allocates nothing.  A count of 0 yields a valid pointer.
 class Scratch {
 public:
     explicit Scratch(icp_ctx *ctx, KeptBlock *kept = nullptr) : ctx(ctx), kept(kept) {}

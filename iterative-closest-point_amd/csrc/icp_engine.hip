@@ -1311,6 +1311,7 @@ void icp_ctx_destroy(icp_ctx *ctx)
                     (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
                     (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
                     (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->filt_block.base,
+                    (void *)ctx->eval_block.base,
                     (void *)ctx->trim_keys,
                     (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state,
                     (void *)ctx->uniq_best})

@@ -8,7 +8,7 @@
 //                          knn_search of icp_knn.h with k + 1 entries (the normals kernel's search); the
 //                          epilogue sums the roots of the list's d2 from +0 in list order and divides by
 //                          k: 8 bytes a point are written, not the n x (k + 1) lists
-//   filter_sum_kernel      the sum rule below, one level a launch: a wave a chunk, the chunk's sum to
+//   filter_sum_kernel      (icp_sum.h) the sum rule below, one level a launch: a wave a chunk, the chunk's sum to
 //                          part[chunk]; the first level of the second pass takes (v - mu)^2 as its terms
 //   filter_finish_kernel   one thread: mu = S / n after the first pass; sigma = sqrt(S / (n - 1)) and
 //                          T = mu + ratio * sigma after the second
@@ -40,13 +40,13 @@
 
 #include "icp_engine.h"
 #include "icp_knn.h"
+#include "icp_sum.h"
 
 namespace icp {
 namespace {
 
 using namespace icp::engine;
 
-constexpr int kFilterChunk = 1024; // terms of a chunk of the sum rule
 constexpr int kFilterTile = 1024;  // points per workgroup of the mask / place passes (4 a thread)
 
 __global__ __launch_bounds__(kKnnBlock) void knn_mean_dist_kernel(GridView gv, int n, int k1, int budget,
@@ -62,31 +62,6 @@ __global__ __launch_bounds__(kKnnBlock) void knn_mean_dist_kernel(GridView gv, i
     double s = 0.0;
     for (int e = 0; e < k1; ++e) s += sqrt(ld[e * kKnnBlock]);
     mean[(int)q.w] = s / (double)(k1 - 1);
-}
-
-// level 0 of a pass reads v (with kDev: (v - *mu)^2), a later level the sums of the level before
-template <bool kDev>
-__global__ __launch_bounds__(kBlock) void filter_sum_kernel(const double *__restrict__ v, int len,
-                                                            const double *__restrict__ mu, double *__restrict__ part)
-{
-    const int lane = threadIdx.x & 63;
-    const long long chunk = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    const long long b = chunk * kFilterChunk;
-    if (b >= len) return; // (a whole wave: no barrier below)
-    const int e = (int)std::min<long long>(len, b + kFilterChunk);
-    const double m = kDev ? *mu : 0.0;
-    double a = 0.0;
-    for (int i = (int)b + lane; i < e; i += 64) {
-        if (kDev) {
-            const double d = v[i] - m;
-            a += d * d;
-        } else {
-            a += v[i];
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-    if (lane == 0) part[chunk] = a;
 }
 
 // stats = (mu, sigma, T); pass 0: mu from the first sum, pass 1: sigma and T from the second
@@ -226,29 +201,6 @@ __global__ __launch_bounds__(kBlock) void filter_place_kernel(const double *__re
         }
 }
 
-int blocks_for(size_t n, int per) { return (int)((std::max<size_t>(n, 1) + per - 1) / per); }
-
-// The sum rule over v (kDev: over (v - *mu)^2): level after level into the two halves of part
-// (blocks_for(n, kFilterChunk) + 1 doubles each); -> the device address of S
-template <bool kDev>
-const double *sum_levels(const double *v, int n, const double *mu, double *part, hipStream_t st)
-{
-    const size_t half = (size_t)blocks_for(n, kFilterChunk) + 1;
-    const double *src = v;
-    int len = n, level = 0;
-    for (;;) { // (at most four levels: len falls by 1,024 a level)
-        const int chunks = blocks_for(len, kFilterChunk);
-        double *dst = part + (level & 1 ? half : 0);
-        const int nb = blocks_for(chunks, kBlock / 64);
-        if (level == 0 && kDev) filter_sum_kernel<true><<<nb, kBlock, 0, st>>>(src, len, mu, dst);
-        else filter_sum_kernel<false><<<nb, kBlock, 0, st>>>(src, len, nullptr, dst);
-        if (chunks == 1) return dst;
-        src = dst;
-        len = chunks;
-        ++level;
-    }
-}
-
 // what both filters check first (nothing has run when they fail)
 int filter_args(icp_ctx *ctx, const std::string &who, const void *xyz, size_t n, const size_t *n_out)
 {
@@ -360,7 +312,7 @@ int statistical_dev(icp_ctx *ctx, const std::string &who, const double *aos, siz
 {
     double *mean = nullptr, *part = nullptr, *stats = nullptr;
     TRY(tmp.get(&mean, n));
-    TRY(tmp.get(&part, 2 * ((size_t)blocks_for(n, kFilterChunk) + 1)));
+    TRY(tmp.get(&part, sum_part_doubles(n)));
     TRY(tmp.get(&stats, 3));
     TempGrid tg;
     PhaseClock clock;

@@ -86,6 +86,7 @@ EXPORTED = [
     "icp_set_one_to_one",
     "icp_fpfh", "icp_match_features", "icp_match_features_plan", "icp_ransac_pose", "icp_global_pose",
     "icp_filter_statistical", "icp_filter_statistical_device", "icp_filter_radius", "icp_filter_radius_device",
+    "icp_evaluate", "icp_evaluate_device",
 ]
 
 
@@ -124,6 +125,19 @@ class GlobalParams(C.Structure):
 class GlobalReport(C.Structure):
     _fields_ = [(k, C.c_longlong) for k in ("model_points", "scene_points", "matches", "evaluated", "inliers",
                                             "best_h")]
+
+
+class Evaluation(C.Structure):
+    """icp_evaluation: what icp_evaluate reports of the resident scene against the resident model."""
+    _fields_ = [("scene_points", C.c_longlong), ("correspondences", C.c_longlong), ("fitness", C.c_double),
+                ("inlier_rmse", C.c_double), ("max_inlier_d2", C.c_double), ("information", C.c_double * 36),
+                ("model_points", C.c_longlong), ("model_correspondences", C.c_longlong),
+                ("model_fitness", C.c_double), ("model_rmse", C.c_double), ("model_max_inlier_d2", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "information"}
+        d["information"] = np.array(self.information, dtype=np.float64).reshape(6, 6)
+        return d
 
 
 FPFH_DIM = 33
@@ -257,6 +271,10 @@ def lib() -> C.CDLL:
         L.icp_filter_statistical_device.argtypes = [vp, vp, sz, C.c_int, C.c_double, vp, vp, C.POINTER(sz), vp, dp]
         L.icp_filter_radius.argtypes = [vp, dp, sz, C.c_double, C.c_int, dp, u8p, C.POINTER(sz), i32p]
         L.icp_filter_radius_device.argtypes = [vp, vp, sz, C.c_double, C.c_int, vp, vp, C.POINTER(sz), vp]
+    if hasattr(L, "icp_evaluate"):
+        i32p = C.POINTER(C.c_int32)
+        L.icp_evaluate.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Evaluation), i32p, dp, i32p, dp]
+        L.icp_evaluate_device.argtypes = [vp, C.c_double, C.c_int, C.POINTER(Evaluation), vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -584,6 +602,40 @@ class Context:
         self._check(lib().icp_filter_radius_device(self._h, C.c_void_p(ptr), n, float(radius), int(min_neighbors),
                                                    opt(out_ptr), opt(mask_ptr), C.byref(n_out), opt(count_ptr)))
         return int(n_out.value)
+
+    def evaluate(self, max_dist: float, both: bool = False, per_point: bool = False) -> dict:
+        """icp_evaluate: the resident scene as it lies now against the resident model -> a dict of
+        icp_evaluation's fields, `information` a (6, 6) array.  A pair is kept iff its squared distance is
+        at most max_dist * max_dist (float('inf'): every pair).  both: the model's side too (model_*).
+        per_point: `idx` (int32, -1: no pair) and `d2` (+inf: no pair) of the np scene points in the
+        caller's order, and with both `model_idx` / `model_d2` of the nm model points."""
+        ev = Evaluation()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        idx = d2 = midx = md2 = None
+        if per_point:
+            idx, d2 = np.empty(self._np_local, dtype=np.int32), np.empty(self._np_local)
+            if both:
+                midx, md2 = np.empty(self._nm, dtype=np.int32), np.empty(self._nm)
+        self._check(lib().icp_evaluate(self._h, float(max_dist), 1 if both else 0, C.byref(ev),
+                                       ip(idx) if per_point else None, _dp(d2) if per_point else None,
+                                       ip(midx) if midx is not None else None, _dp(md2) if md2 is not None else None))
+        out = ev.as_dict()
+        if per_point:
+            out["idx"], out["d2"] = idx, d2
+            if both:
+                out["model_idx"], out["model_d2"] = midx, md2
+        return out
+
+    def evaluate_device(self, max_dist: float, both: bool = False, idx_ptr: int | None = None,
+                        d2_ptr: int | None = None, model_idx_ptr: int | None = None,
+                        model_d2_ptr: int | None = None) -> dict:
+        """icp_evaluate_device: as evaluate; the per-point arrays (int32 / fp64, np and nm entries) are device
+        pointers (None: not wanted)."""
+        ev = Evaluation()
+        opt = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        self._check(lib().icp_evaluate_device(self._h, float(max_dist), 1 if both else 0, C.byref(ev), opt(idx_ptr),
+                                              opt(d2_ptr), opt(model_idx_ptr), opt(model_d2_ptr)))
+        return ev.as_dict()
 
     def transform(self):
         """icp_get_transform: (s, R (3, 3), t (3,)) with q = s R p + t mapping the scene as set_scene
@@ -1043,6 +1095,17 @@ def register_global(ctx: Context, m, p, voxel: float, max_iter: int, threshold: 
     ctx.transform_scene(1.0, R0, t0)
     res, errs = ctx.run(max_iter, threshold)
     return res, errs, ctx.transform(), (R0, t0), report
+
+
+def evaluate_registration(ctx: Context, m, p, max_dist: float, pose=None, both: bool = False) -> dict:
+    """Open3D's evaluate_registration on this engine: set_model(m), set_scene(p), the scene moved by
+    pose = (s, R, t) (None: as given) with transform_scene, then ctx.evaluate(max_dist, both)."""
+    ctx.set_model(_cloud(m))
+    ctx.set_scene(_cloud(p))
+    if pose is not None:
+        s, R, t = pose
+        ctx.transform_scene(float(s), R, t)
+    return ctx.evaluate(max_dist, both=both)
 
 
 @dataclass
