@@ -908,6 +908,10 @@ int icp_select_kth(int device, const double *v, size_t n, size_t k, double *out)
  * (nullable, nm entries) = each sorted position's model index.  Call once with start = order =
  * NULL for the sizes.  ICP_E_NO_MODEL without a model. */
 int icp_get_grid(icp_ctx *ctx, int g[3], double lo[3], double *inv_h, int32_t *start, int32_t *order);
+/* The blocks of device and pinned host memory the library holds now, over every context of the process
+ * (exposed for its tests: the count returns to what it was once the contexts made since are destroyed). */
+long /* (the type's second word begins the line that names the function, as every declaration here does) */
+long icp_debug_live_buffers(void);
 
 #ifdef __cplusplus
 }

@@ -14,15 +14,15 @@ namespace engine {
 
 Scratch::~Scratch()
 {
-    for (void *q : own) (void)hipFree(q);
+    own.clear(); // (the object's own allocations go first, as they always did)
     if (!kept || !begun) return;
     kept->want = total;
     // The call did not fit: the block grown to its total now, not at the next call's start, so that the
-    // next call at these sizes allocates nothing.  (Every caller has synchronised, or hipFree above has; a
+    // next call at these sizes allocates nothing.  (Every caller has synchronised, or the frees above have; a
     // failure leaves an empty block, which the next object grows again, and the call's own status and message.)
-    if (kept->cap < total) {
+    if (kept->base.capacity() < total) {
         const std::string err = ctx->err;
-        if (grow(ctx, &kept->base, &kept->cap, total) != ICP_OK) ctx->err = err;
+        if (kept->base.grow(ctx, total) != ICP_OK) ctx->err = err;
     }
 }
 
@@ -30,18 +30,20 @@ int Scratch::get_bytes(void **out, size_t bytes)
 {
     *out = nullptr;
     if (kept) {
-        if (!begun && kept->cap < kept->want) TRY(grow(ctx, &kept->base, &kept->cap, kept->want)); // (once)
+        if (!begun && kept->base.capacity() < kept->want) TRY(kept->base.grow(ctx, kept->want)); // (once)
         begun = true;
         const size_t part = (bytes + 255) & ~(size_t)255;
         total += part;
-        if (off + part <= kept->cap) {
+        if (off + part <= kept->base.capacity()) {
             *out = kept->base + off;
             off += part;
             return ICP_OK;
         }
     }
-    HIPCHK(hipMalloc(out, bytes));
-    own.push_back(*out);
+    DevBuf<char> mine;
+    TRY(mine.grow(ctx, bytes));
+    *out = mine;
+    own.push_back(std::move(mine));
     return ICP_OK;
 }
 
@@ -74,7 +76,7 @@ static int normals_upload(icp_ctx *ctx, const std::string &who, const std::strin
     }
     const size_t bad = first_nonfinite(n_xyz, 3 * n);
     if (bad != kAllFinite) return fail(ctx, ICP_E_ARG, who + ": normal " + std::to_string(bad / 3) + " is not finite");
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+    TRY(ctx->stage.grow(ctx, 3 * n));
     HIPCHK(hipMemcpyAsync(ctx->stage, n_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
     *aos_dev = ctx->stage;
     return ICP_OK;
@@ -86,7 +88,7 @@ static int set_model_normals(icp_ctx *ctx, const double *n_xyz, size_t nm, bool 
     if (!ctx || !n_xyz) return ICP_E_ARG;
     const double *aos_dev = nullptr;
     TRY(normals_upload(ctx, "icp_set_model_normals", "model", ctx->has_model, ctx->nm, n_xyz, nm, host, &aos_dev));
-    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, nm));
+    TRY(ctx->n4.grow(ctx, nm));
     launch_plane_normals4(aos_dev, (int)nm, ctx->n4, ctx->st);
     LAUNCHCHK("plane_normals4");
     HIPCHK(hipStreamSynchronize(ctx->st)); // (the caller's array, or the stage, is free again)
@@ -138,7 +140,7 @@ static bool normals_debug()
 static int normals_launch(icp_ctx *ctx, const GridView &gv, const double4 *rows, size_t n, int k, int budget,
                           const double *viewpoint, double4 *out, const std::string &label)
 {
-    TRY(grow(ctx, &ctx->knn_counters, &ctx->knn_counters_cap, (size_t)kKnnCounters));
+    TRY(ctx->knn_counters.grow(ctx, (size_t)kKnnCounters));
     HIPCHK(hipMemsetAsync(ctx->knn_counters, 0, sizeof(unsigned long long) * kKnnCounters, ctx->st));
     launch_model_normals(gv, rows, (int)n, k, budget, viewpoint, out, ctx->knn_counters, normals_debug(), ctx->st);
     LAUNCHCHK(label + "_normals");
@@ -234,8 +236,8 @@ int icp_model_knn(icp_ctx *ctx, int k, int32_t *idx, double *d2)
     if (!idx) return fail(ctx, ICP_E_ARG, "icp_model_knn: idx is null");
     TRY(knn_args(ctx, "icp_model_knn", "model", model_gridded(ctx), ctx->nm, k, nullptr));
     const size_t cnt = ctx->nm * (size_t)k;
-    TRY(grow(ctx, &ctx->knn_idx, &ctx->knn_idx_cap, cnt));
-    if (d2) TRY(grow(ctx, &ctx->knn_d2, &ctx->knn_d2_cap, cnt));
+    TRY(ctx->knn_idx.grow(ctx, cnt));
+    if (d2) TRY(ctx->knn_d2.grow(ctx, cnt));
     launch_model_knn(grid_view(ctx), ctx->m4, (int)ctx->nm, k, grid_budget(ctx), ctx->knn_idx, d2 ? ctx->knn_d2 : nullptr,
                      ctx->st);
     LAUNCHCHK("model_knn");
@@ -249,7 +251,7 @@ int icp_estimate_model_normals(icp_ctx *ctx, int k, const double *viewpoint, lon
 {
     if (!ctx) return ICP_E_ARG;
     TRY(knn_args(ctx, "icp_estimate_model_normals", "model", model_gridded(ctx), ctx->nm, k, viewpoint));
-    TRY(grow(ctx, &ctx->n4, &ctx->n4_cap, ctx->nm));
+    TRY(ctx->n4.grow(ctx, ctx->nm));
     ctx->has_normals = false; // (until the new ones are complete)
     TRY(normals_launch(ctx, grid_view(ctx), ctx->m4, ctx->nm, k, grid_budget(ctx), viewpoint, ctx->n4, "model"));
     TRY(normals_finish(ctx, ctx->nm, k, "model", degenerate));
@@ -323,7 +325,7 @@ int icp_estimate_scene_normals(icp_ctx *ctx, int k, const double *viewpoint, lon
         LAUNCHCHK("scene_to_file_order");
         P = &ctx->s_tmp;
     }
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+    TRY(ctx->stage.grow(ctx, 3 * n));
     launch_soa_to_aos(P->x, P->y, P->z, n, ctx->stage, ctx->st);
     Scratch mem(ctx); // (freed before the call returns, whatever it returns)
     TempGrid tg;

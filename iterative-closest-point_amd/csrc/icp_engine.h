@@ -11,8 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <atomic>
 #include <cmath>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "icp_canon.h"
@@ -21,16 +23,77 @@
 namespace icp {
 namespace engine {
 
+// Every block of device or pinned host memory the engine keeps is one of these two owning types: the
+// pointer, its capacity and its release travel together, and a struct that holds them frees them with
+// itself.  Movable and swappable, not copyable -- so passing the object itself to a kernel does not
+// compile; it converts to its pointer wherever one is expected.  live_blocks: the blocks both types hold
+// now, process-wide (icp_debug_live_buffers).
+extern std::atomic<long long> live_blocks;
+
+// Device memory.  grow never shrinks and does not preserve the contents: a block too small is freed
+// first; a count of 0 allocates one element.  When it fails the buffer is empty and the context's error
+// is set (ctx may be null, as for fail).
+template <class T> class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { (void)release(); }
+    operator T *() const { return p; }
+    T *get() const { return p; } // (where the pointer is cast on to another type)
+    T *operator->() const { return p; }
+    size_t capacity() const { return cap; } // in elements
+    int grow(icp_ctx *ctx, size_t count);
+    hipError_t release();
+
+private:
+    T *p = nullptr;
+    size_t cap = 0;
+};
+
+// Pinned host memory: mapped and coherent with its device address (dev()), or plain pinned.  grow as
+// DevBuf's: pointer, device address and capacity change together or not at all.
+template <class T, bool Mapped> class HostBuf {
+public:
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { (void)release(); }
+    operator T *() const { return h; }
+    T *get() const { return h; }
+    T *operator->() const { return h; }
+    T *dev() const
+    {
+        static_assert(Mapped, "plain pinned memory has no device address");
+        return d;
+    }
+    size_t capacity() const { return cap; }
+    int grow(icp_ctx *ctx, size_t count);
+    hipError_t release();
+
+private:
+    T *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+};
+template <class T> using MappedBuf = HostBuf<T, true>;
+template <class T> using PinnedBuf = HostBuf<T, false>;
+
 struct DevCloud {
-    double *x = nullptr, *y = nullptr, *z = nullptr;
-    float4 *f = nullptr;
-    size_t n = 0, cap = 0;
+    DevBuf<double> x, y, z;
+    DevBuf<float4> f;
+    size_t n = 0;
+    size_t cap() const { return x.capacity(); } // (grow_cloud keeps the four at one capacity)
 };
 
 // device memory the context keeps for the Scratch objects over it: want = the last call's total
 struct KeptBlock {
-    char *base = nullptr;
-    size_t cap = 0, want = 0;
+    DevBuf<char> base;
+    size_t want = 0;
 };
 
 } // namespace engine
@@ -55,15 +118,15 @@ struct icp_ctx {
 
     // model (replicated)
     DevCloud model;
-    float4 *m32 = nullptr;   // centred fp32 model, padded to nm_pad with far points
-    float4 *mperm = nullptr; // same, (mm, x, y, z) permuted for the MFMA operands
-    float *mm = nullptr;     // |m~|^2 rounded to fp32 (the MFMA's k = 0 operand)
-    char *mimg16 = nullptr;  // f16 split image for the 32x32x16 f16 MFMA (1 KiB / 32 points)
+    DevBuf<float4> m32;      // centred fp32 model, padded to nm_pad with far points
+    DevBuf<float4> mperm;    // same, (mm, x, y, z) permuted for the MFMA operands
+    DevBuf<float> mm;        // |m~|^2 rounded to fp32 (the MFMA's k = 0 operand)
+    DevBuf<char> mimg16;     // f16 split image for the 32x32x16 f16 MFMA (1 KiB / 32 points)
     bool mimg16_pending = false; // (built at the first search that reads it: ensure_mimage16)
     bool m32_pending = false;    // (m32, mperm, mm: built at their first reader, ensure_m32)
-    float *mms16 = nullptr;  // |b_s|^2 (scaled) per model point, fp32
+    DevBuf<float> mms16;     // |b_s|^2 (scaled) per model point, fp32
     double scale16 = 1.0;    // power of two: max |b_s| in [2^11, 2^12)
-    size_t nm = 0, nm_pad = 0, m32_cap = 0, mperm_cap = 0, mm_cap = 0, mimg16_cap = 0, mms16_cap = 0;
+    size_t nm = 0, nm_pad = 0;
     int nn_variant = ICP_NN_VARIANT_AUTO;
     double c[3] = {0, 0, 0}; // centring point = model centroid
     // host copy of the model (AoS): kept when the one-launch paths can take it (small models),
@@ -72,11 +135,11 @@ struct icp_ctx {
     double rm = 0.0;         // max |centred fp32 model coordinate|
     // the model's preparation on the device (icp_model.hip): stats scratch, results (device and
     // pinned host), the kd builder's plan and scratch, the compare counter of icp_ensure_model
-    double *mstat_part = nullptr, *mstat_out = nullptr, *h_mstat = nullptr;
-    int *cmp_diff = nullptr;
+    DevBuf<double> mstat_part, mstat_out;
+    PinnedBuf<double> h_mstat;
+    DevBuf<int> cmp_diff;
     KdPlan kd_plan;
-    char *kd_scratch = nullptr;
-    size_t kd_scratch_cap = 0;
+    DevBuf<char> kd_scratch;
     bool has_model = false;
 
     // scene (this rank's shard), its correspondences
@@ -93,53 +156,39 @@ struct icp_ctx {
     DevCloud qa, qb;
 
     // NN workspace
-    int *idx = nullptr;
-    size_t idx_cap = 0;
-    void *part = nullptr, *part2 = nullptr;
-    size_t part_cap = 0, part2_cap = 0;
-    int *amb1 = nullptr;           // queue of the MFMA certificate
-    size_t amb1_cap = 0;
-    int *amb_count = nullptr, *amb_list = nullptr;
-    double *amb_T = nullptr;
-    size_t amb_cap = 0;
+    DevBuf<int> idx;
+    DevBuf<char> part, part2;
+    DevBuf<int> amb1;              // queue of the MFMA certificate
+    DevBuf<int> amb_count, amb_list;
+    DevBuf<double> amb_T;          // (amb_list and amb_T: one capacity, ensure_queue)
     // exact grid resolver (icp_grid.hip): model grid + the queues around it
     GridParams grid{};
-    int *g_start = nullptr;
-    char *g_sort = nullptr; // the build's sort scratch (launch_grid_build)
-    size_t g_sort_cap = 0;
-    double4 *g_pts = nullptr;
-    float4 *g_pts32 = nullptr; // (the fp32 image of g_pts: the seeded grid search's prefilter)
-    size_t g_pts32_cap = 0;
-    size_t g_start_cap = 0, g_pts_cap = 0;
-    IterState *iter_state = nullptr; // device-resident loop state (icp_iter.hip)
-    size_t iter_state_cap = 0;
-    IterState *h_iter = nullptr;     // mapped host mirror of the last recorded iteration's state
-    IterState *d_iter_mirror = nullptr; // its device address
-    double *h_trace = nullptr, *d_trace = nullptr; // mapped host error trace
-    size_t trace_cap = 0;
-    int *h_sig = nullptr, *d_sig = nullptr; // mapped completion word of the per-operation calls
+    DevBuf<int> g_start;
+    DevBuf<char> g_sort;     // the build's sort scratch (launch_grid_build)
+    DevBuf<double4> g_pts;
+    DevBuf<float4> g_pts32;  // (the fp32 image of g_pts: the seeded grid search's prefilter)
+    DevBuf<IterState> iter_state; // device-resident loop state (icp_iter.hip)
+    MappedBuf<IterState> h_iter;  // mapped host mirror of the last recorded iteration's state
+    MappedBuf<double> h_trace;    // mapped host error trace
+    MappedBuf<int> h_sig;         // mapped completion word of the per-operation calls
     int sig_ticket = 0;
-    double *h_few = nullptr;         // mapped host staging of the few-query path: q (3 x kFewQueries),
-    double *d_few = nullptr;         //   y (3 x kFewQueries), idx (kFewQueries ints); device address
-    int *h_flags = nullptr;          // mapped host (done, iter, ticket, -) per in-flight iteration
-    int *d_flags = nullptr;          // its device address (err_step writes it directly)
-    int flag_ticket = 0;             // last ticket handed to an iteration
-    double *err_trace_dev = nullptr;
-    size_t err_trace_cap = 0;
+    MappedBuf<double> h_few;      // mapped host staging of the few-query path: q (3 x kFewQueries),
+                                  //   y (3 x kFewQueries), idx (kFewQueries ints)
+    MappedBuf<int> h_flags;       // mapped host (done, iter, ticket, -) per in-flight iteration
+                                  // (err_step writes it directly, through its device address)
+    int flag_ticket = 0;          // last ticket handed to an iteration
+    DevBuf<double> err_trace_dev;
     std::vector<hipEvent_t> iter_ev; // per ring slot: (nn begin, nn end, -, all-reduce begin, all-reduce end)
-    unsigned long long *digest = nullptr; // icp_set_index_digest: 3 x digest_cap per-iteration digests
-    unsigned *cert_audit = nullptr;       // icp_set_cert_audit: (max err ratio, min margin) float bits, count
-    size_t digest_cap = 0;
-    double4 *m4 = nullptr;      // model as (x, y, z, 0) doubles: one read per random gather
-    size_t m4_cap = 0;
+    DevBuf<unsigned long long> digest; // icp_set_index_digest: 3 x digest_cap per-iteration digests
+    DevBuf<unsigned> cert_audit;       // icp_set_cert_audit: (max err ratio, min margin) float bits, count
+    size_t digest_cap = 0;             // (the iterations asked for; 0: off)
+    DevBuf<double4> m4;         // model as (x, y, z, 0) doubles: one read per random gather
     // the next model's SoA copy and double4 rows, built while its checks are read back and
     // swapped with model / m4 when they pass (set_model_staged)
     DevCloud model_alt;
-    double4 *m4_alt = nullptr;
-    size_t m4_alt_cap = 0;
+    DevBuf<double4> m4_alt;
     hipEvent_t mstat_ev = nullptr; // (the checks' read-back)
-    unsigned *seed16 = nullptr; // seeded f16 filter: per-query shift (icp_run iterations >= 2)
-    size_t seed16_cap = 0;
+    DevBuf<unsigned> seed16;    // seeded f16 filter: per-query shift (icp_run iterations >= 2)
     bool last_search_timed = false; // the per-operation search recorded its events
     bool seeds_valid = false;   // idx holds the previous search over the resident scene
     // seedd_valid: b_seedd holds D64(p_j, m[idx_j]) of the resident scene (the last icp_run took
@@ -151,155 +200,132 @@ struct icp_ctx {
     // is sized for this many queued queries (0: min(n, 4096)) -- the far count the host last saw
     int second_pass_items = 0;
     int last_q2 = -1; // the last run's last observed second-pass queue (IterState::queued2)
-    int *amb1_hint = nullptr, *amb_hint = nullptr;    // candidates of the level-1 / level-2 queues
-    int *fb_list = nullptr;                           // queries the grid hands back
-    double *fb_T = nullptr;
-    size_t amb1_hint_cap = 0, amb_hint_cap = 0, fb_list_cap = 0, fb_T_cap = 0;
+    DevBuf<int> amb1_hint, amb_hint;                  // candidates of the level-1 / level-2 queues
+    DevBuf<int> fb_list;                              // queries the grid hands back
+    DevBuf<double> fb_T;
 
     // reductions
-    double *partials = nullptr;
-    double *err_part = nullptr; // (multi-rank icp_run: the transform's residual partials, icp_run.hip)
-    size_t err_part_cap = 0;
-    double *canon_rowbuf = nullptr; // (icp_run over a scene in slot order: the canonical rows, icp_canon.h)
-    int *canon_ticket = nullptr;    // (the fold's workgroup ticket, CanonStep::fold_ticket)
-    size_t canon_rowbuf_cap = 0;
-    int *h_far = nullptr; // (pinned: a far count read back once, canon_path's hold_first)
-    double *sums = nullptr;
-    double *h_sums = nullptr; // pinned
-    int *h_amb = nullptr;     // pinned
-    double *stage = nullptr;
-    size_t stage_cap = 0;
+    DevBuf<double> partials;
+    DevBuf<double> err_part;     // (multi-rank icp_run: the transform's residual partials, icp_run.hip)
+    DevBuf<double> canon_rowbuf; // (icp_run over a scene in slot order: the canonical rows, icp_canon.h)
+    DevBuf<int> canon_ticket;    // (the fold's workgroup ticket, CanonStep::fold_ticket)
+    PinnedBuf<int> h_far; // (a far count read back once, canon_path's hold_first)
+    DevBuf<double> sums;
+    PinnedBuf<double> h_sums;
+    PinnedBuf<int> h_amb;
+    DevBuf<double> stage;
     // small host <-> device transfers: a mapped pinned buffer the conversion kernels read and
     // write directly (no pageable-copy staging); bump-allocated, recycled after a sync
-    double *h_io = nullptr, *d_io = nullptr;
-    size_t io_cap = 0, io_off = 0;
+    MappedBuf<double> h_io;
+    size_t io_off = 0;
     bool io_pending = false; // a queued kernel may still read h_io
 
     // ICP_NN_RULE_CPU_SQRT: the near-tie window of every search (launch_nn_cpu_rule_window)
     int nn_rule = ICP_NN_RULE_SQUARED;
-    CpuRuleEntry *cr_entries = nullptr;
-    int *cr_count = nullptr;
-    int *cr_fix = nullptr; // the fix-up's (query, index) pairs
-    size_t cr_cap = 0, cr_count_cap = 0, cr_fix_cap = 0;
+    DevBuf<CpuRuleEntry> cr_entries;
+    DevBuf<int> cr_count;
+    DevBuf<int> cr_fix; // the fix-up's (query, index) pairs
 
     // one-launch registration of small clouds (icp_iter.hip, launch_icp_persistent)
     int run_mode = ICP_RUN_AUTO;
     int n_cu = 0;                    // compute units
     size_t lds_per_cu = 0, lds_per_block = 0;
-    double *pers_part = nullptr;     // 2 x kBlock x kNumSums published partials
-    unsigned *pers_sync = nullptr;   // arrival counter, abort word (+ padding to 16 B)
-    size_t pers_part_cap = 0, pers_sync_cap = 0;
-    double *tail_part = nullptr;     // fused mid-size tail: published partials (18 x kTailMaxBlocks)
-    unsigned *tail_sync = nullptr;   // its barrier words
-    double *mid_q4 = nullptr;        // mid-size one-launch loop: published queries (4 per point)
-    int *mid_res = nullptr;          // and their correspondences
-    int *mid_perm = nullptr;         // its search order (each point's row)
-    char *mid_cnt = nullptr;         // the order's scratch (radix sort)
+    DevBuf<double> pers_part;        // 2 x kBlock x kNumSums published partials
+    DevBuf<unsigned> pers_sync;      // arrival counter, abort word (+ padding to 16 B)
+    DevBuf<double> tail_part;        // fused mid-size tail: published partials (18 x kTailMaxBlocks)
+    DevBuf<unsigned> tail_sync;      // its barrier words
+    DevBuf<double> mid_q4;           // mid-size one-launch loop: published queries (4 per point)
+    DevBuf<int> mid_res;             // and their correspondences
+    DevBuf<int> mid_perm;            // its search order (each point's row)
+    DevBuf<char> mid_cnt;            // the order's scratch (radix sort)
     double m_lo[3] = {0, 0, 0}, m_hi[3] = {0, 0, 0}; // the model's box
     double pm_seed_big = 0.0;        // PersistArgs::seed_big for this model
-    size_t mid_q4_cap = 0, mid_res_cap = 0, mid_perm_cap = 0, mid_cnt_cap = 0;
-    size_t tail_part_cap = 0, tail_sync_cap = 0;
     bool pers_sync_valid = false;    // the barrier words hold pers_epoch_base barriers of grid pers_grid
     unsigned pers_epoch_base = 0;
     int pers_grid = 0;
-    unsigned long long *pers_stamps = nullptr; // ICP_PERSIST_STAMPS=1: phase stamps
-    size_t pers_stamps_cap = 0;
+    DevBuf<unsigned long long> pers_stamps; // ICP_PERSIST_STAMPS=1: phase stamps
     // the model in Morton order for the one-launch NN (models <= kPersistMaxModel points):
     // x[nm] | y[nm] | z[nm] | 64-point block boxes (lo xyz, hi xyz) | original index (int32)
-    double *pm_img = nullptr;
-    size_t pm_img_cap = 0, pm_blocks = 0;
+    DevBuf<double> pm_img;
+    size_t pm_blocks = 0;
     // bundle-bound filter (icp_bundle.hip): the model's kd-ordered bundle and pair images, built
     // per model of >= kBundleMinModel points; the query order of the scene it searches
-    char *b_img = nullptr, *b_pimg = nullptr; // 1 KiB per 32 bundles; 1 KiB per bundle
-    int *b_kd_orig = nullptr;                 // original index per kd position (nm: padding)
-    double4 *b_bctr = nullptr, *b_blk = nullptr; // per bundle / per 32-bundle block: centre, radius
-    int *b_kd = nullptr;                      // the kd order (upload staging)
+    DevBuf<char> b_img, b_pimg;               // 1 KiB per 32 bundles; 1 KiB per bundle
+    DevBuf<int> b_kd_orig;                    // original index per kd position (nm: padding)
+    DevBuf<double4> b_bctr, b_blk;            // per bundle / per 32-bundle block: centre, radius
+    DevBuf<int> b_kd;                         // the kd order (upload staging)
     int nb_pad = 0;                           // bundles (whole LDS tiles)
     // the bundle filter's kd order and images are built at their first use (ensure_bundle):
     // pending from icp_set_model on until then (a run whose searches all take the grid never
     // builds them)
     bool bundle_pending = false;
-    size_t b_img_cap = 0, b_pimg_cap = 0, b_kd_orig_cap = 0, b_bctr_cap = 0, b_blk_cap = 0, b_kd_cap = 0;
-    int *q_order = nullptr;                   // the bundle filter's query order (launch_query_order)
-    int *q_pos = nullptr;                     // its inverse (query j's slot)
-    size_t q_pos_cap = 0;
-    char *q_order_tmp = nullptr;
-    size_t q_order_cap = 0, q_order_tmp_cap = 0;
+    DevBuf<int> q_order;                      // the bundle filter's query order (launch_query_order)
+    DevBuf<int> q_pos;                        // its inverse (query j's slot)
+    DevBuf<char> q_order_tmp;
     const double *q_order_src = nullptr;      // the cloud q_order was computed for (its x array)
     size_t q_order_n = 0;
-    unsigned long long *b_counters = nullptr; // icp_set_bundle_counters: the filter's executed work
-    char *b_qop = nullptr, *b_gop = nullptr;  // v2: per-slot query operands, per-group bounds
-    double4 *b_qraw = nullptr;                // v2: per-slot query coordinates, index, seed
-    int *b_glist = nullptr;                   // v2: fired-block list overflow
-    double *b_seedd = nullptr;                // v2: per point, D64 to its seed (icp_run's transform)
-    size_t b_seedd_cap = 0;
+    DevBuf<unsigned long long> b_counters;    // icp_set_bundle_counters: the filter's executed work
+    DevBuf<char> b_qop, b_gop;                // v2: per-slot query operands, per-group bounds
+    DevBuf<double4> b_qraw;                   // v2: per-slot query coordinates, index, seed
+    DevBuf<int> b_glist;                      // v2: fired-block list overflow
+    DevBuf<double> b_seedd;                   // v2: per point, D64 to its seed (icp_run's transform)
     // the fused grid iteration's exclusion certificate (CertArgs): per point in slot order the
     // bound and the pair; counts = (certified, walked) summed over the run (device)
     hipEvent_t order_ev = nullptr; // icp_set_*_device_stream: the producer stream's point to wait for
-    int4 *cert_state = nullptr;
-    size_t cert_state_cap = 0;
-    unsigned long long *cert_counts = nullptr; // (2 per strand: certified, walked -- CertArgs::counts;
+    DevBuf<int4> cert_state;
+    DevBuf<unsigned long long> cert_counts;    // (2 per strand: certified, walked -- CertArgs::counts;
                                                //  then, in the same allocation, a strand's last walker count and the
                                                //  dispatch order built from it, an int each: CertArgs::walk_last, IterOrder)
-    size_t cert_counts_cap = 0;
     int cert_counts_rows = 0; // (strands the runs since the last fold counted into cert_counts, not yet in stats)
-    char *tail_backup = nullptr;              // icp_run with the fused tail: the starting scene / idx
-    size_t tail_backup_cap = 0;
-    double4 *b_gctr = nullptr;                // v2: per-group (centre, D)
-    int *b_cand = nullptr, *b_cand_n = nullptr; // v2: per filter workgroup, its candidate blocks
-    int *b_wsplit = nullptr, *b_tctl = nullptr; // v2: per filter workgroup its tasks; (count, counter)
-    int2 *b_tasks = nullptr;                  // v2: the task list
-    size_t b_gctr_cap = 0, b_cand_cap = 0, b_cand_n_cap = 0, b_wsplit_cap = 0, b_tctl_cap = 0, b_tasks_cap = 0;
-    size_t b_qop_cap = 0, b_gop_cap = 0, b_qraw_cap = 0, b_glist_cap = 0, b_counters_rows = 0;
+    DevBuf<char> tail_backup;                 // icp_run with the fused tail: the starting scene / idx
+    DevBuf<double4> b_gctr;                   // v2: per-group (centre, D)
+    DevBuf<int> b_cand, b_cand_n;             // v2: per filter workgroup, its candidate blocks
+    DevBuf<int> b_wsplit, b_tctl;             // v2: per filter workgroup its tasks; (count, counter)
+    DevBuf<int2> b_tasks;                     // v2: the task list
+    size_t b_counters_rows = 0;
     // The resident scene in slot order (scene_in_slot_order): point s of the scene (and idx[s]
     // while seeds_valid) is the caller's point s_order[s].  icp_get_scene / icp_get_indices and
     // the index digests map back; every other per-point pass is order-agnostic.
     // the local pair test (icp_bundle_rec.h): the pair image in block frames, the frames (c_B,
     // R_B) and max R_B (-1: not built)
-    char *b_pimg_l = nullptr;
-    float4 *b_frame = nullptr;
-    size_t b_pimg_l_cap = 0, b_frame_cap = 0;
+    DevBuf<char> b_pimg_l;
+    DevBuf<float4> b_frame;
     double b_rlmax = -1.0;
     // the model in kd order and the kd order's inverse (launch_build_kd_tables), and per query
     // its correspondence's kd position (kpos_valid: the last search over the resident scene kept it)
-    double4 *m4kd = nullptr;
-    int *kd_of = nullptr, *kpos = nullptr;
-    size_t m4kd_cap = 0, kd_of_cap = 0, kpos_cap = 0;
+    DevBuf<double4> m4kd;
+    DevBuf<int> kd_of, kpos;
     bool kpos_valid = false;
     // y_ready: the last search over the resident scene also wrote Y = m[idx] (the shifted moments
     // then stream it instead of gathering)
     bool y_ready = false;
     // arrival counters of the passes that end in their own last workgroup (StepFold): [0] the
     // moments + Horn step, [1] the transform + error step; zero between launches
-    unsigned *fold_ticket = nullptr;
+    DevBuf<unsigned> fold_ticket;
     bool scene_slot = false;
     unsigned runs = 0; // (icp_run calls: the timing sample's phase)
     // scene_revert: the scene is in the slot order of a model since replaced -- icp_run puts it
     // back into file order (and sorts it by the new model's box) unless a new scene comes first
     bool scene_revert = false;
     bool p32_stale = false; // the scene's fp32 copy was not kept by the last icp_run (its path never read it)
-    int *s_order = nullptr;
-    size_t s_order_cap = 0;
+    DevBuf<int> s_order;
     DevCloud s_tmp;                           // the permutation's second buffer
-    int *s_tmp_idx = nullptr;
-    size_t s_tmp_idx_cap = 0;
+    DevBuf<int> s_tmp_idx;
 
     // The kept-pairs loop (run_kept: the max-correspondence-distance gate, icp_set_max_distance and
     // icp_gated.hip, and the point-to-plane metric, icp_set_metric and icp_plane.hip).  Scoped to one
     // run, whichever metric: the mask words (the scene's order), the moments' partial rows (kRobustPlaneSums
     // a workgroup, the widest), the device state with its mapped host mirror, the mapped K trace.
-    unsigned long long *kept_mask = nullptr;
-    double *kept_part = nullptr;
-    size_t kept_mask_cap = 0, kept_part_cap = 0;
-    GateState *kept_state = nullptr, *h_kept = nullptr, *d_kept_mirror = nullptr;
-    long long *h_ktrace = nullptr, *d_ktrace = nullptr;
-    size_t ktrace_cap = 0;
+    DevBuf<unsigned long long> kept_mask;
+    DevBuf<double> kept_part;
+    DevBuf<GateState> kept_state;
+    MappedBuf<GateState> h_kept;
+    MappedBuf<long long> h_ktrace;
     // The gate: dmax (0: off), and what icp_get_inliers / icp_get_inlier_trace report, saved at the
     // end of the last gated run (a later ungated plane run leaves it): the flags in the caller's
     // order, K of the last gate evaluated, the recorded iterations' K.
     double gate_dmax = 0.0;
-    unsigned char *gate_flags = nullptr;
-    size_t gate_flags_cap = 0;
+    DevBuf<unsigned char> gate_flags;
     bool gate_have = false; // a gated run has evaluated a gate since icp_set_scene
     long long gate_K = 0;
     std::vector<long long> gate_ktrace;
@@ -308,28 +334,24 @@ struct icp_ctx {
     // iteration's cut C (icp_select.hip), the mapped C trace beside the K trace; and what
     // icp_get_trim_trace reports, saved at the end of the last trimmed run (dropped with the scene).
     double trim_fraction = 1.0;
-    unsigned long long *trim_keys = nullptr;
-    size_t trim_keys_cap = 0;
-    unsigned *trim_bins = nullptr;
-    double *trim_bins_d = nullptr, *trim_cut = nullptr;
-    SelectState *trim_state = nullptr;
-    double *h_ctrace = nullptr, *d_ctrace = nullptr;
-    size_t ctrace_cap = 0;
+    DevBuf<unsigned long long> trim_keys;
+    DevBuf<unsigned> trim_bins;
+    DevBuf<double> trim_bins_d, trim_cut;
+    DevBuf<SelectState> trim_state;
+    MappedBuf<double> h_ctrace;
     bool trim_have = false;
     std::vector<double> trim_ctrace;
     // One-to-one rejection (icp_set_one_to_one): the switch, and per run the table of each model
     // point's smallest d2 key (icp_unique.hip; nm words, all ones at every iteration's start).
     bool one_to_one = false;
-    unsigned long long *uniq_best = nullptr;
-    size_t uniq_best_cap = 0;
+    DevBuf<unsigned long long> uniq_best;
     // Robust weights (icp_set_robust): the kind (ICP_ROBUST_*; 0: off), k and k2 = k * k (fp64, once),
     // the mapped W / K+ traces beside the K trace (grown with it), and what icp_get_robust_trace
     // reports, saved at the end of the last robust run (dropped with the scene).
     int robust_kind = 0;
     double robust_k = 0.0, robust_k2 = 0.0;
-    double *h_wtrace = nullptr, *d_wtrace = nullptr;
-    long long *h_ptrace = nullptr, *d_ptrace = nullptr;
-    size_t wtrace_cap = 0, ptrace_cap = 0;
+    MappedBuf<double> h_wtrace;
+    MappedBuf<long long> h_ptrace;
     bool robust_have = false;
     std::vector<double> robust_wtrace;
     std::vector<long long> robust_ptrace;
@@ -337,8 +359,7 @@ struct icp_ctx {
     // the point-to-plane metric: the model's normals as (nx, ny, nz, 0) by model index (dropped with
     // the model)
     int metric = 0; // ICP_METRIC_*
-    double4 *n4 = nullptr;
-    size_t n4_cap = 0;
+    DevBuf<double4> n4;
     bool has_normals = false;
     // The symmetric form (icp_set_plane_symmetric): the scene's normals u0 as given, in the caller's
     // order (sn; dropped with the scene, kept across icp_transform_scene), and for a scene in slot
@@ -352,18 +373,16 @@ struct icp_ctx {
     bool scene_pristine = false;
     // icp_model_knn's nm x k lists and the estimator's counters (icp_normals.hip): scratch of those two
     // calls alone, so that they leave everything a run reads as they found it
-    int *knn_idx = nullptr;
-    double *knn_d2 = nullptr;
-    unsigned long long *knn_counters = nullptr;
-    size_t knn_idx_cap = 0, knn_d2_cap = 0, knn_counters_cap = 0;
+    DevBuf<int> knn_idx;
+    DevBuf<double> knn_d2;
+    DevBuf<unsigned long long> knn_counters;
 
     // icp_voxel_downsample* (icp_voxel.hip): scratch of those calls alone -- the keys, orders, run
     // heads and box rows (vox_buf), the host form's staged input and output clouds (vox_io: 6 n
     // doubles) and counts (vox_cnt)
-    char *vox_buf = nullptr;
-    double *vox_io = nullptr;
-    int *vox_cnt = nullptr;
-    size_t vox_buf_cap = 0, vox_io_cap = 0, vox_cnt_cap = 0;
+    DevBuf<char> vox_buf;
+    DevBuf<double> vox_io;
+    DevBuf<int> vox_cnt;
     // icp_filter_* (icp_filter.hip): every device array of a call -- the temporary grid's, the filter's
     // own, the staged clouds -- is a part of this one block (Scratch's kept mode), kept between calls: a
     // call's dozen allocations cost as much as its kernels
@@ -510,15 +529,55 @@ constexpr int kSeededBox = 125; // cells of the box a seeded grid search walks w
 
 int fail(icp_ctx *ctx, int code, const std::string &msg);
 
-template <class T> int grow(icp_ctx *ctx, T **p, size_t *cap, size_t count)
+template <class T> hipError_t DevBuf<T>::release()
 {
-    if (*cap >= count && *p) return ICP_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    size_t bytes = sizeof(T) * (count ? count : 1);
-    HIPCHK(hipMalloc((void **)p, bytes));
-    *cap = count;
+    if (!p) return hipSuccess;
+    live_blocks.fetch_sub(1, std::memory_order_relaxed);
+    T *old = p;
+    p = nullptr;
+    cap = 0;
+    return hipFree(old);
+}
+
+template <class T> int DevBuf<T>::grow(icp_ctx *ctx, size_t count)
+{
+    if (cap >= count && p) return ICP_OK;
+    HIPCHK(release());
+    T *fresh = nullptr;
+    HIPCHK(hipMalloc((void **)&fresh, sizeof(T) * (count ? count : 1)));
+    live_blocks.fetch_add(1, std::memory_order_relaxed);
+    p = fresh;
+    cap = count;
+    return ICP_OK;
+}
+
+template <class T, bool Mapped> hipError_t HostBuf<T, Mapped>::release()
+{
+    if (!h) return hipSuccess;
+    live_blocks.fetch_sub(1, std::memory_order_relaxed);
+    T *old = h;
+    h = d = nullptr;
+    cap = 0;
+    return hipHostFree(old);
+}
+
+template <class T, bool Mapped> int HostBuf<T, Mapped>::grow(icp_ctx *ctx, size_t count)
+{
+    if (cap >= count && h) return ICP_OK;
+    HIPCHK(release()); // (the caller has synchronised: no kernel still writes the old block)
+    T *fresh = nullptr;
+    HIPCHK(hipHostMalloc((void **)&fresh, sizeof(T) * (count ? count : 1),
+                         Mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault));
+    live_blocks.fetch_add(1, std::memory_order_relaxed);
+    h = fresh;
+    if (Mapped) {
+        const hipError_t e = hipHostGetDevicePointer((void **)&d, h, 0);
+        if (e != hipSuccess) {
+            (void)release();
+            return fail(ctx, ICP_E_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+        }
+    }
+    cap = count;
     return ICP_OK;
 }
 
@@ -568,7 +627,7 @@ private:
     KeptBlock *kept;
     size_t off = 0, total = 0;
     bool begun = false;
-    std::vector<void *> own;
+    std::vector<DevBuf<char>> own;
 };
 
 // A temporary grid over a cloud that is not the model: the cloud's double4 rows, the grid as the kernels

@@ -141,28 +141,29 @@ int fail(icp_ctx *ctx, int code, const std::string &msg)
             return fail(ctx, ICP_E_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
+std::atomic<long long> live_blocks{0};
+
+// the four arrays at one capacity: all of them anew whenever one is missing or too small, and none
+// of them when an allocation fails
 int grow_cloud(icp_ctx *ctx, DevCloud &c, size_t n, bool with_f32)
 {
-    if (c.cap < n || !c.x || (with_f32 && !c.f)) {
-        for (void *p : {(void *)c.x, (void *)c.y, (void *)c.z, (void *)c.f})
-            if (p) HIPCHK(hipFree(p));
-        c = DevCloud{};
+    if (c.cap() < n || !c.x || (with_f32 && !c.f)) {
+        HIPCHK(c.x.release());
+        HIPCHK(c.y.release());
+        HIPCHK(c.z.release());
+        HIPCHK(c.f.release());
         const size_t m = n ? n : 1;
-        HIPCHK(hipMalloc((void **)&c.x, sizeof(double) * m));
-        HIPCHK(hipMalloc((void **)&c.y, sizeof(double) * m));
-        HIPCHK(hipMalloc((void **)&c.z, sizeof(double) * m));
-        HIPCHK(hipMalloc((void **)&c.f, sizeof(float4) * m));
-        c.cap = m;
+        int rc = c.x.grow(ctx, m);
+        if (rc == ICP_OK) rc = c.y.grow(ctx, m);
+        if (rc == ICP_OK) rc = c.z.grow(ctx, m);
+        if (rc == ICP_OK) rc = c.f.grow(ctx, m);
+        if (rc != ICP_OK) {
+            c = DevCloud{};
+            return rc;
+        }
     }
     c.n = n;
     return ICP_OK;
-}
-
-static void free_cloud(DevCloud &c)
-{
-    for (void *p : {(void *)c.x, (void *)c.y, (void *)c.z, (void *)c.f})
-        if (p) (void)hipFree(p);
-    c = DevCloud{};
 }
 
 // Clouds up to this many doubles (3 x 64k points, 1.5 MiB) move through the mapped buffer.
@@ -176,19 +177,14 @@ static int io_take(icp_ctx *ctx, size_t count, double **h, double **d)
 {
     if (count > 2 * kMappedIo) // callers gate on this; a larger region would run past the buffer
         return fail(ctx, ICP_E_ARG, "io_take: " + std::to_string(count) + " doubles exceed the mapped buffer");
-    if (ctx->io_off + count > ctx->io_cap) {
+    if (ctx->io_off + count > ctx->h_io.capacity()) {
         if (ctx->io_pending) HIPCHK(hipStreamSynchronize(ctx->st));
         ctx->io_pending = false;
         ctx->io_off = 0;
-        if (!ctx->h_io) {
-            ctx->io_cap = 2 * kMappedIo;
-            HIPCHK(hipHostMalloc((void **)&ctx->h_io, sizeof(double) * ctx->io_cap,
-                                 hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_io, ctx->h_io, 0));
-        }
+        TRY(ctx->h_io.grow(ctx, 2 * kMappedIo));
     }
     *h = ctx->h_io + ctx->io_off;
-    *d = ctx->d_io + ctx->io_off;
+    *d = ctx->h_io.dev() + ctx->io_off;
     ctx->io_off += count;
     return ICP_OK;
 }
@@ -210,7 +206,7 @@ static int upload_cloud(icp_ctx *ctx, DevCloud &c, const double *xyz, size_t n, 
         }
         launch_aos_to_soa(d, n, c.x, c.y, c.z, ctx->st);
     } else {
-        TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+        TRY(ctx->stage.grow(ctx, 3 * n));
         HIPCHK(hipMemcpyAsync(ctx->stage, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
         launch_aos_to_soa(ctx->stage, n, c.x, c.y, c.z, ctx->st);
     }
@@ -232,7 +228,7 @@ int download_cloud(icp_ctx *ctx, const DevCloud &c, size_t n, double *xyz)
         std::memcpy(xyz, h, sizeof(double) * 3 * n);
         return ICP_OK;
     }
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+    TRY(ctx->stage.grow(ctx, 3 * n));
     launch_soa_to_aos(c.x, c.y, c.z, n, ctx->stage, ctx->st);
     LAUNCHCHK("download_cloud");
     HIPCHK(hipMemcpyAsync(xyz, ctx->stage, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->st));
@@ -254,13 +250,13 @@ static int model_host_copy(icp_ctx *ctx, const double **out)
 static int ensure_reduction_space(icp_ctx *ctx)
 {
     if (ctx->partials) return ICP_OK;
-    HIPCHK(hipMalloc((void **)&ctx->partials, sizeof(double) * kRedMaxBlocksCap * kRedMaxK));
-    HIPCHK(hipMalloc((void **)&ctx->sums, sizeof(double) * 32));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_sums, sizeof(double) * 32, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_amb, sizeof(int) * 4, hipHostMallocDefault));
+    TRY(ctx->partials.grow(ctx, (size_t)kRedMaxBlocksCap * kRedMaxK));
+    TRY(ctx->sums.grow(ctx, 32));
+    TRY(ctx->h_sums.grow(ctx, 32));
+    TRY(ctx->h_amb.grow(ctx, 4));
     // NN queue counters: present even for an empty shard (horn_step folds and resets them
     // every iteration, whether or not this rank searched anything)
-    HIPCHK(hipMalloc((void **)&ctx->amb_count, sizeof(int) * 4));
+    TRY(ctx->amb_count.grow(ctx, 4));
     HIPCHK(hipMemsetAsync(ctx->amb_count, 0, sizeof(int) * 4, ctx->st)); // (ordered before the stream's kernels)
     return ICP_OK;
 }
@@ -276,17 +272,13 @@ void red_finish(icp_ctx *ctx, size_t n, int K, double *out)
 // queue of queries the fp32 certificate could not settle (list + window T + counter)
 static int ensure_queue(icp_ctx *ctx, size_t n)
 {
-    if (ctx->amb_cap >= n && ctx->amb_list) return ICP_OK;
-    if (ctx->amb_list) HIPCHK(hipFree(ctx->amb_list));
-    if (ctx->amb_T) HIPCHK(hipFree(ctx->amb_T));
-    ctx->amb_list = nullptr;
-    ctx->amb_T = nullptr;
-    ctx->amb_cap = 0;
+    if (ctx->amb_list.capacity() >= n && ctx->amb_list) return ICP_OK;
+    HIPCHK(ctx->amb_list.release()); // (both or neither)
+    HIPCHK(ctx->amb_T.release());
     const size_t m = n ? n : 1;
-    HIPCHK(hipMalloc((void **)&ctx->amb_list, sizeof(int) * m));
-    HIPCHK(hipMalloc((void **)&ctx->amb_T, sizeof(double) * m));
-    ctx->amb_cap = m;
-    return ICP_OK;
+    int rc = ctx->amb_list.grow(ctx, m);
+    if (rc == ICP_OK && (rc = ctx->amb_T.grow(ctx, m)) != ICP_OK) (void)ctx->amb_list.release();
+    return rc;
 }
 
 static int ensure_bundle(icp_ctx *ctx); // (the bundle filter's images at their first use; below)
@@ -314,11 +306,9 @@ int level1_kind(const icp_ctx *ctx, size_t n)
 // launch_model_stats' scratch, its 16 outputs and their host copy, at the first use
 int ensure_model_stats(icp_ctx *ctx)
 {
-    if (ctx->mstat_part) return ICP_OK;
-    HIPCHK(hipMalloc((void **)&ctx->mstat_part, sizeof(double) * model_stats_scratch_doubles()));
-    HIPCHK(hipMalloc((void **)&ctx->mstat_out, sizeof(double) * 16));
-    HIPCHK(hipHostMalloc((void **)&ctx->h_mstat, sizeof(double) * 16, hipHostMallocDefault));
-    return ICP_OK;
+    TRY(ctx->mstat_part.grow(ctx, model_stats_scratch_doubles()));
+    TRY(ctx->mstat_out.grow(ctx, 16));
+    return ctx->h_mstat.grow(ctx, 16);
 }
 
 // a built grid as the kernels take it: its geometry, offsets, points and their fp32 image
@@ -370,10 +360,10 @@ static int query_order(icp_ctx *ctx, const DevCloud &q, size_t n, const int **or
     *order = nullptr;
     if (run_knobs().bundle_order_off) return ICP_OK;
     if (ctx->q_order_src != q.x || ctx->q_order_n != n) {
-        TRY(grow(ctx, &ctx->q_order, &ctx->q_order_cap, n));
-        TRY(grow(ctx, &ctx->q_pos, &ctx->q_pos_cap, n));
+        TRY(ctx->q_order.grow(ctx, n));
+        TRY(ctx->q_pos.grow(ctx, n));
         const size_t bytes = query_order_scratch_bytes((int)n);
-        TRY(grow(ctx, &ctx->q_order_tmp, &ctx->q_order_tmp_cap, bytes));
+        TRY(ctx->q_order_tmp.grow(ctx, bytes));
         if (launch_query_order(q.x, q.y, q.z, (int)n, ctx->m_lo, ctx->m_hi, ctx->q_order_tmp, bytes, ctx->q_order,
                                ctx->st, ctx->q_pos) != 0)
             return fail(ctx, ICP_E_HIP, "query_order: radix sort failed");
@@ -425,23 +415,20 @@ int scene_to_slot_order(icp_ctx *ctx)
     if (ctx->scene_slot || !ctx->scene.n) return ICP_OK;
     DevCloud &P = ctx->scene;
     const size_t n = P.n;
-    TRY(grow(ctx, &ctx->s_order, &ctx->s_order_cap, n));
+    TRY(ctx->s_order.grow(ctx, n));
     const size_t bytes = query_order_scratch_bytes((int)n);
-    TRY(grow(ctx, &ctx->q_order_tmp, &ctx->q_order_tmp_cap, bytes));
+    TRY(ctx->q_order_tmp.grow(ctx, bytes));
     if (launch_query_order(P.x, P.y, P.z, (int)n, ctx->m_lo, ctx->m_hi, ctx->q_order_tmp, bytes, ctx->s_order,
                            ctx->st) != 0)
         return fail(ctx, ICP_E_HIP, "scene order: radix sort failed");
     TRY(grow_cloud(ctx, ctx->s_tmp, n, true));
     const bool with_idx = ctx->seeds_valid;
-    if (with_idx) TRY(grow(ctx, &ctx->s_tmp_idx, &ctx->s_tmp_idx_cap, n));
+    if (with_idx) TRY(ctx->s_tmp_idx.grow(ctx, n));
     launch_permute_cloud(ctx->s_order, (int)n, 0, P.x, P.y, P.z, P.f, with_idx ? ctx->idx : nullptr, ctx->s_tmp.x,
                          ctx->s_tmp.y, ctx->s_tmp.z, ctx->s_tmp.f, with_idx ? ctx->s_tmp_idx : nullptr, ctx->st);
     LAUNCHCHK("scene_to_slot_order");
     std::swap(ctx->scene, ctx->s_tmp);
-    if (with_idx) {
-        std::swap(ctx->idx, ctx->s_tmp_idx);
-        std::swap(ctx->idx_cap, ctx->s_tmp_idx_cap);
-    }
+    if (with_idx) std::swap(ctx->idx, ctx->s_tmp_idx);
     ctx->scene_slot = true;
     ctx->sn_slot_valid = false;
     return ICP_OK;
@@ -505,15 +492,15 @@ int fold_cert_counts(icp_ctx *ctx)
 static int grid_seeded_search(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop, const double *seedd,
                               hipEvent_t ev1)
 {
-    TRY(grow(ctx, &ctx->amb1, &ctx->amb1_cap, n));
-    TRY(grow(ctx, &ctx->amb1_hint, &ctx->amb1_hint_cap, n));
-    TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
-    TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+    TRY(ctx->amb1.grow(ctx, n));
+    TRY(ctx->amb1_hint.grow(ctx, n));
+    TRY(ctx->fb_list.grow(ctx, n));
+    TRY(ctx->fb_T.grow(ctx, n));
     int *kpos_out = nullptr;
     // (kd tables of the current model only: nb_pad > 0 -- set_model resets it, and pending bundle
     // images leave the last model's tables in place)
     if (ctx->nn_rule == ICP_NN_RULE_SQUARED && ctx->m4kd && ctx->kd_of && ctx->nb_pad > 0) {
-        TRY(grow(ctx, &ctx->kpos, &ctx->kpos_cap, n));
+        TRY(ctx->kpos.grow(ctx, n));
         kpos_out = ctx->kpos;
     }
     // (an XCD a contiguous eighth of the slot order: measured faster for sparse shards, slower
@@ -522,7 +509,7 @@ static int grid_seeded_search(icp_ctx *ctx, const DevCloud &q, size_t n, const i
     // with the seed distances (the policy's searches): every level also writes each answered
     // query's correspondence y = m[idx] (the moments then stream y: no gather)
     const DevCloud &Y = ctx->Y;
-    const bool y_out = seedd && Y.x && Y.cap >= n;
+    const bool y_out = seedd && Y.x && Y.cap() >= n;
     double *yx = y_out ? Y.x : nullptr, *yy = y_out ? Y.y : nullptr, *yz = y_out ? Y.z : nullptr;
     if (y_out) {
         kpos_out = nullptr;
@@ -568,8 +555,8 @@ static int grid_seeded_search(icp_ctx *ctx, const DevCloud &q, size_t n, const i
 static int ensure_mimage16(icp_ctx *ctx)
 {
     if (!ctx->mimg16_pending) return ICP_OK;
-    TRY(grow(ctx, &ctx->mimg16, &ctx->mimg16_cap, ctx->nm_pad * 32));
-    TRY(grow(ctx, &ctx->mms16, &ctx->mms16_cap, ctx->nm_pad));
+    TRY(ctx->mimg16.grow(ctx, ctx->nm_pad * 32));
+    TRY(ctx->mms16.grow(ctx, ctx->nm_pad));
     launch_build_mimage16(ctx->model.x, ctx->model.y, ctx->model.z, (int)ctx->nm, (int)ctx->nm_pad, ctx->c,
                           ctx->scale16, ctx->mimg16, ctx->mms16, ctx->st);
     LAUNCHCHK("build_mimage16");
@@ -585,11 +572,11 @@ static int ensure_mimage16(icp_ctx *ctx)
 static int ensure_m32(icp_ctx *ctx)
 {
     if (!ctx->m32_pending) return ICP_OK;
-    TRY(grow(ctx, &ctx->m32, &ctx->m32_cap, ctx->nm_pad));
-    TRY(grow(ctx, &ctx->mperm, &ctx->mperm_cap, ctx->nm_pad));
-    TRY(grow(ctx, &ctx->mm, &ctx->mm_cap, ctx->nm_pad));
+    TRY(ctx->m32.grow(ctx, ctx->nm_pad));
+    TRY(ctx->mperm.grow(ctx, ctx->nm_pad));
+    TRY(ctx->mm.grow(ctx, ctx->nm_pad));
     launch_model_f32_images_soa(ctx->model.x, ctx->model.y, ctx->model.z, (int)ctx->nm, (int)ctx->nm_pad, ctx->c,
-                                ctx->m32, (float *)ctx->mperm, ctx->mm, ctx->st);
+                                ctx->m32, (float *)ctx->mperm.get(), ctx->mm, ctx->st);
     LAUNCHCHK("model_f32_images");
     ctx->m32_pending = false;
     return ICP_OK;
@@ -603,7 +590,7 @@ static int ensure_m32(icp_ctx *ctx)
 // ICP_CELL_SEED=0: the ring search (A/B).
 static int grid_unseeded_slot(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop, hipEvent_t ev1)
 {
-    TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
+    TRY(ctx->b_seedd.grow(ctx, n));
     launch_nn_grid_cell_seed((int)n, q.x, q.y, q.z, grid_view(ctx), (int)ctx->nm, ctx->idx, ctx->b_seedd, ctx->st);
     LAUNCHCHK("nn_grid_cell_seed");
     return grid_seeded_search(ctx, q, n, stop, ctx->b_seedd, ev1);
@@ -623,7 +610,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
 {
     const SeedState none;
     const SeedState &w = ws ? *ws : none;
-    TRY(grow(ctx, &ctx->idx, &ctx->idx_cap, n));
+    TRY(ctx->idx.grow(ctx, n));
     ctx->kpos_valid = false;
     ctx->y_ready = false;
     if (!n) return ICP_OK;
@@ -637,8 +624,8 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         ctx->stats.last_filter = ICP_FILTER_FP64;
         const NNPlan pl = plan_nn64(n, ctx->nm);
         const size_t need = (size_t)pl.splits * n * (sizeof(double) + sizeof(int));
-        TRY(grow(ctx, (char **)&ctx->part, &ctx->part_cap, need));
-        double *pb = (double *)ctx->part;
+        TRY(ctx->part.grow(ctx, need));
+        double *pb = (double *)ctx->part.get();
         int *pi = (int *)(pb + (size_t)pl.splits * n);
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
         launch_nn_fp64(q.x, q.y, q.z, (int)n, ctx->model.x, ctx->model.y, ctx->model.z, (int)ctx->nm,
@@ -658,8 +645,8 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
     } else if (ctx->nn_variant == ICP_NN_VARIANT_GRID) {
         // exact grid search for every query; over-budget boxes -> fp64 brute force per query
         ctx->stats.last_filter = ICP_FILTER_GRID;
-        TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
-        TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+        TRY(ctx->fb_list.grow(ctx, n));
+        TRY(ctx->fb_T.grow(ctx, n));
         const bool cell_seeds = !seeded && slot_order && run_knobs().cell_seed;
         if (!cell_seeds) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
@@ -692,8 +679,8 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
             // The run's policy then keeps to the grid until its far count says otherwise, and a
             // registration that stays near the model never builds the bundle images (§3.6)
             ctx->stats.last_filter = ICP_FILTER_GRID;
-            TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
-            TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+            TRY(ctx->fb_list.grow(ctx, n));
+            TRY(ctx->fb_T.grow(ctx, n));
             if (!run_knobs().cell_seed) TRY(ensure_m32(ctx)); // (launch_nn_resolve below reads m32)
             if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
             if (run_knobs().cell_seed) return grid_unseeded_slot(ctx, q, n, stop, ev1);
@@ -729,7 +716,7 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         // (local: the partials carry kd positions; every writer of idx below then keeps kpos too,
         // unless the CPU rule's host fix-up may rewrite idx after the search)
         if (local && ctx->nn_rule == ICP_NN_RULE_SQUARED && ctx->m4kd) {
-            TRY(grow(ctx, &ctx->kpos, &ctx->kpos_cap, n));
+            TRY(ctx->kpos.grow(ctx, n));
             kpos_out = ctx->kpos;
         }
         // the transform's records serve only the form this search runs: the local pair test's
@@ -742,45 +729,41 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         // writes them), the f16 seeds from a transform that wrote them
         const bool seeds_ready = local ? records_ready && wu.seed16 == 2 : wu.seed16 == 1;
         if (sd && !seeds_ready) { // (icp_run: the previous iteration's transform wrote them)
-            TRY(grow(ctx, &ctx->seed16, &ctx->seed16_cap, n));
+            TRY(ctx->seed16.grow(ctx, n));
             if (!local) // (local: the prep writes each query's shift there)
                 launch_mfma16_seed(q.x, q.y, q.z, (int)n, ctx->idx, ctx->m4, ctx->c, ctx->scale16, ctx->seed16,
                                    ctx->st);
         }
         const unsigned *seeds = sd ? ctx->seed16 : nullptr;
-        TRY(grow(ctx, (char **)&ctx->part, &ctx->part_cap,
-                 (size_t)pl.splits * n * (2 * sizeof(float) + sizeof(int))));
-        float *pb = (float *)ctx->part;
+        TRY(ctx->part.grow(ctx, (size_t)pl.splits * n * (2 * sizeof(float) + sizeof(int))));
+        float *pb = (float *)ctx->part.get();
         float *ps = pb + (size_t)pl.splits * n;
         int *pi = (int *)(ps + (size_t)pl.splits * n);
-        TRY(grow(ctx, &ctx->amb1, &ctx->amb1_cap, n));
-        TRY(grow(ctx, &ctx->amb1_hint, &ctx->amb1_hint_cap, n));
-        TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
-        TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+        TRY(ctx->amb1.grow(ctx, n));
+        TRY(ctx->amb1_hint.grow(ctx, n));
+        TRY(ctx->fb_list.grow(ctx, n));
+        TRY(ctx->fb_T.grow(ctx, n));
         const int *order = nullptr;
         // (slot_order: q is the resident scene, already stored in the filter's order)
         if (l1 == 3 && !slot_order) TRY(query_order(ctx, q, n, &order));
         if (v2) { // every query's operands, once, in the filter's slot order
             const size_t nslots = bundle2_slots(pl);
-            TRY(grow(ctx, &ctx->b_qop, &ctx->b_qop_cap, nslots * 64));
-            TRY(grow(ctx, &ctx->b_qraw, &ctx->b_qraw_cap, nslots));
-            TRY(grow(ctx, &ctx->b_gop, &ctx->b_gop_cap, nslots));
-            TRY(grow(ctx, &ctx->b_glist, &ctx->b_glist_cap, bundle2_list_ints(pl, ctx->nb_pad)));
-            TRY(grow(ctx, &ctx->b_cand, &ctx->b_cand_cap, (size_t)pl.qblocks * (ctx->nb_pad >> 5)));
-            TRY(grow(ctx, &ctx->b_cand_n, &ctx->b_cand_n_cap, (size_t)pl.qblocks));
-            TRY(grow(ctx, &ctx->b_wsplit, &ctx->b_wsplit_cap, (size_t)pl.qblocks));
-            TRY(grow(ctx, &ctx->b_tasks, &ctx->b_tasks_cap, bundle2_task_count(pl)));
-            if (ctx->b_tctl_cap < (size_t)kBundleTctlInts || !ctx->b_tctl) { // (the done counter starts at zero)
-                TRY(grow(ctx, &ctx->b_tctl, &ctx->b_tctl_cap, kBundleTctlInts));
+            TRY(ctx->b_qop.grow(ctx, nslots * 64));
+            TRY(ctx->b_qraw.grow(ctx, nslots));
+            TRY(ctx->b_gop.grow(ctx, nslots));
+            TRY(ctx->b_glist.grow(ctx, bundle2_list_ints(pl, ctx->nb_pad)));
+            TRY(ctx->b_cand.grow(ctx, (size_t)pl.qblocks * (ctx->nb_pad >> 5)));
+            TRY(ctx->b_cand_n.grow(ctx, (size_t)pl.qblocks));
+            TRY(ctx->b_wsplit.grow(ctx, (size_t)pl.qblocks));
+            TRY(ctx->b_tasks.grow(ctx, bundle2_task_count(pl)));
+            if (ctx->b_tctl.capacity() < (size_t)kBundleTctlInts || !ctx->b_tctl) { // (the done counter starts at zero)
+                TRY(ctx->b_tctl.grow(ctx, kBundleTctlInts));
                 HIPCHK(hipMemsetAsync(ctx->b_tctl, 0, sizeof(int) * kBundleTctlInts, ctx->st));
             }
-            TRY(grow(ctx, &ctx->b_gctr, &ctx->b_gctr_cap, nslots / 32));
+            TRY(ctx->b_gctr.grow(ctx, nslots / 32));
             if (ctx->b_counters && ctx->b_counters_rows < bundle2_counter_rows(pl)) { // (per-wave rows)
-                HIPCHK(hipFree(ctx->b_counters));
-                ctx->b_counters = nullptr;
                 ctx->b_counters_rows = bundle2_counter_rows(pl);
-                HIPCHK(hipMalloc((void **)&ctx->b_counters,
-                                 sizeof(unsigned long long) * kBundleCounterFields * ctx->b_counters_rows));
+                TRY(ctx->b_counters.grow(ctx, kBundleCounterFields * ctx->b_counters_rows));
                 HIPCHK(hipMemsetAsync(ctx->b_counters, 0,
                                       sizeof(unsigned long long) * kBundleCounterFields * ctx->b_counters_rows,
                                       ctx->st));
@@ -837,13 +820,13 @@ int nn_search_begin(icp_ctx *ctx, const DevCloud &q, size_t n, bool seeded, hipE
         ctx->stats.last_filter = ICP_FILTER_VALU;
         const NNPlan pl = plan_nn32(n, ctx->nm_pad);
         const size_t need = (size_t)pl.splits * n * (2 * sizeof(float) + sizeof(int));
-        TRY(grow(ctx, (char **)&ctx->part, &ctx->part_cap, need));
-        float *pb = (float *)ctx->part;
+        TRY(ctx->part.grow(ctx, need));
+        float *pb = (float *)ctx->part.get();
         float *ps = pb + (size_t)pl.splits * n;
         int *pi = (int *)(ps + (size_t)pl.splits * n);
-        TRY(grow(ctx, &ctx->amb_hint, &ctx->amb_hint_cap, n));
-        TRY(grow(ctx, &ctx->fb_list, &ctx->fb_list_cap, n));
-        TRY(grow(ctx, &ctx->fb_T, &ctx->fb_T_cap, n));
+        TRY(ctx->amb_hint.grow(ctx, n));
+        TRY(ctx->fb_list.grow(ctx, n));
+        TRY(ctx->fb_T.grow(ctx, n));
         TRY(ensure_m32(ctx)); // (the fp32 filter and the brute-force resolver read m32)
         if (ev0) HIPCHK(hipEventRecord(ev0, ctx->st));
         launch_nn_filter(q.f, (int)n, ctx->m32, (int)ctx->nm_pad, pl, pb, ps, pi, ctx->st, stop);
@@ -904,18 +887,18 @@ static double cpu_rule_distance(const double q[3], const double *m)
 int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop)
 {
     if (ctx->nn_rule != ICP_NN_RULE_CPU_SQRT || n == 0) return ICP_OK;
-    TRY(grow(ctx, &ctx->cr_count, &ctx->cr_count_cap, 1));
+    TRY(ctx->cr_count.grow(ctx, 1));
     size_t want = std::min<size_t>(n, 4096);
     for (int pass = 0; pass < 2; ++pass) {
-        TRY(grow(ctx, &ctx->cr_entries, &ctx->cr_cap, want));
+        TRY(ctx->cr_entries.grow(ctx, want));
         HIPCHK(hipMemsetAsync(ctx->cr_count, 0, sizeof(int), ctx->st));
         launch_nn_cpu_rule_window((int)n, q.x, q.y, q.z, ctx->m4, grid_view(ctx), grid_budget(ctx), ctx->idx,
-                                  ctx->cr_count, ctx->cr_entries, (int)ctx->cr_cap, ctx->st, stop);
+                                  ctx->cr_count, ctx->cr_entries, (int)ctx->cr_entries.capacity(), ctx->st, stop);
         LAUNCHCHK("nn_cpu_rule_window");
         int cnt = 0;
         HIPCHK(hipMemcpyAsync(&cnt, ctx->cr_count, sizeof(int), hipMemcpyDeviceToHost, ctx->st));
         HIPCHK(hipStreamSynchronize(ctx->st));
-        if ((size_t)cnt > ctx->cr_cap) { // more near ties than entries: once more with room for all
+        if ((size_t)cnt > ctx->cr_entries.capacity()) { // more near ties than entries: once more with room for all
             want = (size_t)cnt;
             continue;
         }
@@ -955,7 +938,7 @@ int cpu_rule_fixup(icp_ctx *ctx, const DevCloud &q, size_t n, const int *stop)
         }
         if (!changed.empty()) {
             const size_t npairs = changed.size() / 2;
-            TRY(grow(ctx, &ctx->cr_fix, &ctx->cr_fix_cap, changed.size()));
+            TRY(ctx->cr_fix.grow(ctx, changed.size()));
             HIPCHK(hipMemcpyAsync(ctx->cr_fix, changed.data(), sizeof(int) * changed.size(), hipMemcpyHostToDevice,
                                   ctx->st));
             launch_scatter_pairs(ctx->cr_fix, (int)npairs, ctx->idx, ctx->st);
@@ -1040,34 +1023,34 @@ int check_ready(icp_ctx *ctx, bool need_scene)
 static int build_bundle(icp_ctx *ctx, size_t nm, const int *kd_h)
 {
     const int nb_pad = bundle_pad(nm);
-    TRY(grow(ctx, &ctx->b_kd, &ctx->b_kd_cap, nm));
+    TRY(ctx->b_kd.grow(ctx, nm));
     if (kd_h) {
         HIPCHK(hipMemcpyAsync(ctx->b_kd, kd_h, sizeof(int) * nm, hipMemcpyHostToDevice, ctx->st));
     } else {
         kd_plan(nm, ctx->kd_plan); // (ctx-owned: outlives the stream's copy of it)
-        TRY(grow(ctx, &ctx->kd_scratch, &ctx->kd_scratch_cap, kd_order_scratch_bytes(ctx->kd_plan)));
+        TRY(ctx->kd_scratch.grow(ctx, kd_order_scratch_bytes(ctx->kd_plan)));
         if (launch_kd_order(ctx->model.x, ctx->model.y, ctx->model.z, ctx->kd_plan, ctx->kd_scratch,
-                            ctx->kd_scratch_cap, ctx->b_kd, ctx->st) != 0)
+                            ctx->kd_scratch.capacity(), ctx->b_kd, ctx->st) != 0)
             return fail(ctx, ICP_E_HIP, "the bundle kd order's build failed");
     }
     const size_t nbx = (size_t)nb_pad + 32; // + the null block (icp_bundle.hip)
-    TRY(grow(ctx, &ctx->b_img, &ctx->b_img_cap, nbx * 32));
-    TRY(grow(ctx, &ctx->b_pimg, &ctx->b_pimg_cap, nbx * 1024));
-    TRY(grow(ctx, &ctx->b_kd_orig, &ctx->b_kd_orig_cap, nbx * 32));
-    TRY(grow(ctx, &ctx->b_bctr, &ctx->b_bctr_cap, nbx));
-    TRY(grow(ctx, &ctx->b_blk, &ctx->b_blk_cap, nbx / 32));
+    TRY(ctx->b_img.grow(ctx, nbx * 32));
+    TRY(ctx->b_pimg.grow(ctx, nbx * 1024));
+    TRY(ctx->b_kd_orig.grow(ctx, nbx * 32));
+    TRY(ctx->b_bctr.grow(ctx, nbx));
+    TRY(ctx->b_blk.grow(ctx, nbx / 32));
     launch_build_bundle_images(ctx->model.x, ctx->model.y, ctx->model.z, (int)nm, ctx->b_kd, nb_pad, ctx->c,
                                ctx->scale16, ctx->b_img, ctx->b_pimg, ctx->b_kd_orig, ctx->b_bctr, ctx->b_blk, ctx->st);
     LAUNCHCHK("build_bundle_images");
     // the local pair test's image and block frames, and max R_B (the certificate's R)
     const size_t nfr = nbx / 32;
-    TRY(grow(ctx, &ctx->b_pimg_l, &ctx->b_pimg_l_cap, nbx * 1024));
-    TRY(grow(ctx, &ctx->b_frame, &ctx->b_frame_cap, nfr));
+    TRY(ctx->b_pimg_l.grow(ctx, nbx * 1024));
+    TRY(ctx->b_frame.grow(ctx, nfr));
     launch_build_local_images(ctx->model.x, ctx->model.y, ctx->model.z, (int)nm, ctx->b_kd, nb_pad, ctx->c,
                               ctx->scale16, ctx->b_pimg_l, ctx->b_frame, ctx->st);
     LAUNCHCHK("build_local_images");
-    TRY(grow(ctx, &ctx->m4kd, &ctx->m4kd_cap, nm));
-    TRY(grow(ctx, &ctx->kd_of, &ctx->kd_of_cap, nm));
+    TRY(ctx->m4kd.grow(ctx, nm));
+    TRY(ctx->kd_of.grow(ctx, nm));
     launch_build_kd_tables(ctx->m4, ctx->b_kd_orig, (int)nm, ctx->m4kd, ctx->kd_of, ctx->st);
     LAUNCHCHK("build_kd_tables");
     std::vector<float4> fr(nfr);
@@ -1223,15 +1206,14 @@ int icp_set_bundle_counters(icp_ctx *ctx, int enable)
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->st));
     if (!enable) {
-        if (ctx->b_counters) HIPCHK(hipFree(ctx->b_counters));
-        ctx->b_counters = nullptr;
+        HIPCHK(ctx->b_counters.release());
         ctx->b_counters_rows = 0;
         return ICP_OK;
     }
     // (rows: one for v1's shared counters, per wave task for v2; sized at the next search)
     if (!ctx->b_counters) {
         ctx->b_counters_rows = 1;
-        HIPCHK(hipMalloc((void **)&ctx->b_counters, kBundleCounterFields * sizeof(unsigned long long)));
+        TRY(ctx->b_counters.grow(ctx, kBundleCounterFields));
     }
     HIPCHK(hipMemsetAsync(ctx->b_counters, 0, kBundleCounterFields * sizeof(unsigned long long) * ctx->b_counters_rows,
                           ctx->st));
@@ -1278,66 +1260,18 @@ void icp_ctx_destroy(icp_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->st) (void)hipStreamSynchronize(ctx->st);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
-    free_cloud(ctx->model);
-    free_cloud(ctx->model_alt);
-    if (ctx->m4_alt) (void)hipFree(ctx->m4_alt);
-    free_cloud(ctx->scene);
-    free_cloud(ctx->Y);
-    free_cloud(ctx->qa);
-    free_cloud(ctx->qb);
-    free_cloud(ctx->s_tmp);
-    free_cloud(ctx->sn);
-    free_cloud(ctx->sn_slot);
-    for (void *p : {(void *)ctx->m32, (void *)ctx->mperm, (void *)ctx->mm, (void *)ctx->mimg16,
-                    (void *)ctx->mms16, ctx->part2,
-                    (void *)ctx->amb1, (void *)ctx->idx, ctx->part, (void *)ctx->amb_count,
-                    (void *)ctx->amb_list, (void *)ctx->amb_T, (void *)ctx->partials, (void *)ctx->err_part,
-                    (void *)ctx->sums, (void *)ctx->stage, (void *)ctx->g_sort,
-                    (void *)ctx->g_start, (void *)ctx->g_pts, (void *)ctx->g_pts32,
-                    (void *)ctx->amb1_hint, (void *)ctx->amb_hint, (void *)ctx->fb_list,
-                    (void *)ctx->fb_T, (void *)ctx->seed16, (void *)ctx->m4,
-                    (void *)ctx->iter_state, (void *)ctx->err_trace_dev, (void *)ctx->digest, (void *)ctx->fold_ticket,
-                    (void *)ctx->cert_audit, (void *)ctx->pers_part, (void *)ctx->pers_sync,
-                    (void *)ctx->pers_stamps, (void *)ctx->pm_img, (void *)ctx->b_img, (void *)ctx->b_pimg, (void *)ctx->b_kd_orig,
-                    (void *)ctx->b_bctr, (void *)ctx->b_blk, (void *)ctx->b_gctr, (void *)ctx->b_cand,
-                    (void *)ctx->b_cand_n, (void *)ctx->b_wsplit, (void *)ctx->b_tasks, (void *)ctx->b_tctl,
-                    (void *)ctx->b_kd, (void *)ctx->b_seedd, (void *)ctx->tail_backup, (void *)ctx->q_order, (void *)ctx->q_order_tmp, (void *)ctx->b_counters,
-                    (void *)ctx->b_qop, (void *)ctx->b_gop, (void *)ctx->b_qraw, (void *)ctx->b_glist, (void *)ctx->q_pos, (void *)ctx->cr_entries,
-                    (void *)ctx->cr_count, (void *)ctx->cr_fix, (void *)ctx->tail_part, (void *)ctx->tail_sync,
-                    (void *)ctx->mid_q4, (void *)ctx->mid_res, (void *)ctx->mid_perm, (void *)ctx->mid_cnt,
-                    (void *)ctx->s_order, (void *)ctx->s_tmp_idx, (void *)ctx->b_pimg_l, (void *)ctx->b_frame,
-                    (void *)ctx->m4kd, (void *)ctx->kd_of, (void *)ctx->kpos, (void *)ctx->canon_rowbuf,
-                    (void *)ctx->canon_ticket, (void *)ctx->cert_state, (void *)ctx->cert_counts,
-                    (void *)ctx->kept_mask, (void *)ctx->kept_part, (void *)ctx->kept_state, (void *)ctx->gate_flags,
-                    (void *)ctx->n4, (void *)ctx->knn_idx, (void *)ctx->knn_d2, (void *)ctx->knn_counters,
-                    (void *)ctx->vox_buf, (void *)ctx->vox_io, (void *)ctx->vox_cnt, (void *)ctx->filt_block.base,
-                    (void *)ctx->eval_block.base,
-                    (void *)ctx->trim_keys,
-                    (void *)ctx->trim_bins, (void *)ctx->trim_bins_d, (void *)ctx->trim_cut, (void *)ctx->trim_state,
-                    (void *)ctx->uniq_best})
-        if (p) (void)hipFree(p);
-    if (ctx->h_sums) (void)hipHostFree(ctx->h_sums);
-    if (ctx->h_amb) (void)hipHostFree(ctx->h_amb);
-    if (ctx->h_iter) (void)hipHostFree(ctx->h_iter);
-    if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
-    if (ctx->h_far) (void)hipHostFree(ctx->h_far);
-    if (ctx->h_kept) (void)hipHostFree(ctx->h_kept);
-    if (ctx->h_ktrace) (void)hipHostFree(ctx->h_ktrace);
-    if (ctx->h_wtrace) (void)hipHostFree(ctx->h_wtrace);
-    if (ctx->h_ptrace) (void)hipHostFree(ctx->h_ptrace);
-    if (ctx->h_ctrace) (void)hipHostFree(ctx->h_ctrace);
-    if (ctx->h_few) (void)hipHostFree(ctx->h_few);
-    if (ctx->h_sig) (void)hipHostFree(ctx->h_sig);
-    if (ctx->h_trace) (void)hipHostFree(ctx->h_trace);
-    if (ctx->h_io) (void)hipHostFree(ctx->h_io);
     for (auto e : ctx->iter_ev) (void)hipEventDestroy(e);
     if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
     if (ctx->mstat_ev) (void)hipEventDestroy(ctx->mstat_ev);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->st) (void)hipStreamDestroy(ctx->st);
+    // The members free themselves, here: after the stream was synchronised above (no kernel still
+    // uses a block) and with the context's device current (a process may hold contexts on several).
     delete ctx;
 }
+
+long long icp_debug_live_buffers(void) { return live_blocks.load(std::memory_order_relaxed); }
 
 const char *icp_last_error(const icp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -1482,7 +1416,7 @@ int icp_set_plane_to_plane(icp_ctx *ctx, double epsilon)
 // The model's AoS copy -> ctx->stage (pageable host memory: the runtime's staged copy).
 static int stage_model(icp_ctx *ctx, const double *m_xyz, size_t nm)
 {
-    TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * nm));
+    TRY(ctx->stage.grow(ctx, 3 * nm));
     HIPCHK(hipMemcpyAsync(ctx->stage, m_xyz, sizeof(double) * 3 * nm, hipMemcpyHostToDevice, ctx->st));
     return ICP_OK;
 }
@@ -1522,7 +1456,7 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     // the SoA fp64 copy and the double4 rows need no statistic: built into the spare buffers while
     // the host waits for the checks (the wait was an idle gap of ~20 us at C4), swapped in below
     TRY(grow_cloud(ctx, ctx->model_alt, nm, true));
-    TRY(grow(ctx, &ctx->m4_alt, &ctx->m4_alt_cap, nm));
+    TRY(ctx->m4_alt.grow(ctx, nm));
     launch_aos_to_soa4(aos, nm, ctx->model_alt.x, ctx->model_alt.y, ctx->model_alt.z, ctx->m4_alt, ctx->st);
     LAUNCHCHK("aos_to_soa4");
     HIPCHK(hipEventSynchronize(ctx->mstat_ev)); // (the checks only: the copy above runs on)
@@ -1558,7 +1492,6 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     const size_t nm_pad = (nm + kTile32 - 1) / kTile32 * kTile32;
     std::swap(ctx->model, ctx->model_alt);
     std::swap(ctx->m4, ctx->m4_alt);
-    std::swap(ctx->m4_cap, ctx->m4_alt_cap);
     // ICP_M32_LAZY=0 (A/B, read once): the fp32 images here, from the uploaded copy; else at
     // their first reader (ensure_m32)
     static const bool m32_lazy = [] {
@@ -1567,10 +1500,10 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     }();
     ctx->m32_pending = m32_lazy;
     if (!m32_lazy) {
-        TRY(grow(ctx, &ctx->m32, &ctx->m32_cap, nm_pad));
-        TRY(grow(ctx, &ctx->mperm, &ctx->mperm_cap, nm_pad));
-        TRY(grow(ctx, &ctx->mm, &ctx->mm_cap, nm_pad));
-        launch_model_f32_images(aos, (int)nm, (int)nm_pad, ctx->c, ctx->m32, (float *)ctx->mperm, ctx->mm, ctx->st);
+        TRY(ctx->m32.grow(ctx, nm_pad));
+        TRY(ctx->mperm.grow(ctx, nm_pad));
+        TRY(ctx->mm.grow(ctx, nm_pad));
+        launch_model_f32_images(aos, (int)nm, (int)nm_pad, ctx->c, ctx->m32, (float *)ctx->mperm.get(), ctx->mm, ctx->st);
         LAUNCHCHK("model_f32_images");
     }
     ctx->scale16 = rm64 > 0.0 ? std::ldexp(1.0, (int)std::floor(std::log2(4096.0 / rm64))) : 1.0;
@@ -1579,11 +1512,11 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     // uniform grid over the fp64 model for the exact resolver (its box: step 1's)
     ctx->grid = grid_params_box(lo, hi, nm);
     const long long ncell = grid_cells(ctx->grid);
-    TRY(grow(ctx, &ctx->g_start, &ctx->g_start_cap, (size_t)ncell + 1));
-    TRY(grow(ctx, &ctx->g_pts, &ctx->g_pts_cap, nm));
-    TRY(grow(ctx, &ctx->g_pts32, &ctx->g_pts32_cap, nm));
+    TRY(ctx->g_start.grow(ctx, (size_t)ncell + 1));
+    TRY(ctx->g_pts.grow(ctx, nm));
+    TRY(ctx->g_pts32.grow(ctx, nm));
     const size_t gbytes = grid_build_scratch_bytes((int)nm, ncell);
-    TRY(grow(ctx, &ctx->g_sort, &ctx->g_sort_cap, gbytes));
+    TRY(ctx->g_sort.grow(ctx, gbytes));
     if (launch_grid_build(ctx->model.x, ctx->model.y, ctx->model.z, ctx->m4, (int)nm, ctx->grid, ctx->g_sort, gbytes,
                           ctx->g_start, ctx->g_pts, ctx->g_pts32, ctx->st) != 0)
         return fail(ctx, ICP_E_HIP, "grid build: radix sort failed");
@@ -1607,7 +1540,7 @@ static int set_model_staged(icp_ctx *ctx, const double *m_xyz, size_t nm, const 
     std::vector<double> pm;
     if (nm <= (size_t)std::max(kPersistMaxModel, kPersistMidMaxModel)) { // the one-launch loops' model image
         pm = persist_model_image(m_xyz, nm, &ctx->pm_blocks);
-        TRY(grow(ctx, &ctx->pm_img, &ctx->pm_img_cap, pm.size()));
+        TRY(ctx->pm_img.grow(ctx, pm.size()));
         HIPCHK(hipMemcpyAsync(ctx->pm_img, pm.data(), sizeof(double) * pm.size(), hipMemcpyHostToDevice, ctx->st));
         { // the mid-size search's stale-seed scale: a move beyond 2 diagonals of a median 16-point block
             const size_t nb16 = (nm + 15) / 16;
@@ -1722,7 +1655,7 @@ int icp_ensure_model(icp_ctx *ctx, const double *m_xyz, size_t nm, int *uploaded
         if (ctx->model_host.size() == 3 * nm) { // the kept host copy compares exactly
             if (std::memcmp(ctx->model_host.data(), m_xyz, sizeof(double) * 3 * nm) == 0) return ICP_OK;
         } else { // a large model: its upload compared bit for bit with the resident copy on the device
-            if (!ctx->cmp_diff) HIPCHK(hipMalloc((void **)&ctx->cmp_diff, sizeof(int)));
+            TRY(ctx->cmp_diff.grow(ctx, 1));
             TRY(stage_model(ctx, m_xyz, nm));
             HIPCHK(hipMemsetAsync(ctx->cmp_diff, 0, sizeof(int), ctx->st));
             launch_model_compare(ctx->stage, (int)nm, ctx->model.x, ctx->model.y, ctx->model.z, ctx->cmp_diff,
@@ -1756,9 +1689,9 @@ static int scene_from_aos(icp_ctx *ctx, const double *aos, size_t n, bool *slot)
     if (!n) return ICP_OK;
     DevCloud &P = ctx->scene;
     if (ctx->has_model && want_slot_order(ctx, n)) {
-        TRY(grow(ctx, &ctx->s_order, &ctx->s_order_cap, n));
+        TRY(ctx->s_order.grow(ctx, n));
         const size_t bytes = query_order_scratch_bytes((int)n);
-        TRY(grow(ctx, &ctx->q_order_tmp, &ctx->q_order_tmp_cap, bytes));
+        TRY(ctx->q_order_tmp.grow(ctx, bytes));
         if (launch_slot_order_aos(aos, (int)n, ctx->m_lo, ctx->m_hi, ctx->q_order_tmp, bytes, ctx->s_order, ctx->c,
                                   P.x, P.y, P.z, P.f, ctx->st) != 0)
             return fail(ctx, ICP_E_HIP, "scene order: radix sort failed");
@@ -1784,7 +1717,7 @@ int icp_set_scene(icp_ctx *ctx, const double *p_xyz, size_t np_local, size_t np_
         TRY(upload_cloud(ctx, ctx->scene, p_xyz, np_local, true));
     } else { // large: a pageable copy into the stage, then as icp_set_scene_device
         TRY(grow_cloud(ctx, ctx->scene, np_local, true));
-        TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * np_local));
+        TRY(ctx->stage.grow(ctx, 3 * np_local));
         HIPCHK(hipMemcpyAsync(ctx->stage, p_xyz, sizeof(double) * 3 * np_local, hipMemcpyHostToDevice, ctx->st));
         TRY(scene_from_aos(ctx, ctx->stage, np_local, &slot));
         HIPCHK(hipStreamSynchronize(ctx->st));
@@ -1917,7 +1850,7 @@ int icp_transform_scene(icp_ctx *ctx, double s, const double R[9], const double 
     bool slot = false;
     if (n) {
         DevCloud &P = ctx->scene;
-        TRY(grow(ctx, &ctx->stage, &ctx->stage_cap, 3 * n));
+        TRY(ctx->stage.grow(ctx, 3 * n));
         launch_transform_to_aos(P.x, P.y, P.z, (int)n, ctx->scene_slot ? ctx->s_order : nullptr, xf, ctx->stage, ctx->st);
         LAUNCHCHK("transform_to_aos");
         if (3 * n <= kMappedIo) {
@@ -1945,7 +1878,7 @@ int icp_transform_scene(icp_ctx *ctx, double s, const double R[9], const double 
 static int voxel_box(icp_ctx *ctx, const double *xyz_dev, size_t n, double lo[3], double hi[3])
 {
     const int rows = voxel_box_blocks((int)n);
-    double *part = (double *)ctx->vox_buf; // (the head of the scratch: read back before the passes write it)
+    double *part = (double *)ctx->vox_buf.get(); // (the head of the scratch: read back before the passes write it)
     launch_voxel_box(xyz_dev, (int)n, part, ctx->st);
     LAUNCHCHK("voxel_box");
     std::vector<double> h(8 * (size_t)rows);
@@ -1972,7 +1905,7 @@ static int voxel_downsample_dev(icp_ctx *ctx, const double *xyz_dev, size_t n, d
                                 double *xyz_out_dev, int32_t *count_out_dev, size_t *n_out)
 {
     const size_t bytes = std::max(voxel_scratch_bytes((int)n), sizeof(double) * 8 * (size_t)voxel_box_blocks((int)n)) + 256;
-    TRY(grow(ctx, &ctx->vox_buf, &ctx->vox_buf_cap, bytes));
+    TRY(ctx->vox_buf.grow(ctx, bytes));
     double lo[3], hi[3];
     TRY(voxel_box(ctx, xyz_dev, n, lo, hi));
     VoxelGrid vg{};
@@ -2034,8 +1967,8 @@ int icp_voxel_downsample(icp_ctx *ctx, const double *xyz, size_t n, double voxel
     TRY(voxel_args(ctx, xyz, n, voxel, origin, xyz_out, n_out));
     const size_t bad = first_nonfinite(xyz, 3 * n);
     if (bad != kAllFinite) return fail(ctx, ICP_E_ARG, "icp_voxel_downsample: point " + std::to_string(bad / 3) + " is not finite");
-    TRY(grow(ctx, &ctx->vox_io, &ctx->vox_io_cap, 6 * n));
-    if (count_out) TRY(grow(ctx, &ctx->vox_cnt, &ctx->vox_cnt_cap, n));
+    TRY(ctx->vox_io.grow(ctx, 6 * n));
+    if (count_out) TRY(ctx->vox_cnt.grow(ctx, n));
     double *in = ctx->vox_io, *out = ctx->vox_io + 3 * n;
     HIPCHK(hipMemcpyAsync(in, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->st));
     size_t cells = 0;
@@ -2063,28 +1996,23 @@ constexpr size_t kFewQueries = 32;
 static int sync_by_flag(icp_ctx *ctx)
 {
     if (!ctx->h_sig) {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_sig, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        TRY(ctx->h_sig.grow(ctx, 64 / sizeof(int)));
         std::memset(ctx->h_sig, 0, 64);
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_sig, ctx->h_sig, 0));
     }
     const int ticket = ++ctx->sig_ticket;
-    launch_signal(ctx->d_sig, ticket, ctx->st);
+    launch_signal(ctx->h_sig.dev(), ticket, ctx->st);
     LAUNCHCHK("signal");
     return wait_flag(ctx, ctx->h_sig, ticket);
 }
 
 static int closest_few(icp_ctx *ctx, const double *p_xyz, size_t np, double *y_xyz_out, int32_t *idx_out)
 {
-    if (!ctx->h_few) {
-        HIPCHK(hipHostMalloc((void **)&ctx->h_few, sizeof(double) * 7 * kFewQueries,
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void **)&ctx->d_few, ctx->h_few, 0));
-    }
+    TRY(ctx->h_few.grow(ctx, 7 * kFewQueries));
     double *hq = ctx->h_few, *hy = ctx->h_few + 3 * kFewQueries;
     int *hi = (int *)(ctx->h_few + 6 * kFewQueries);
     std::memcpy(hq, p_xyz, sizeof(double) * 3 * np);
-    launch_nn_exact_few(ctx->d_few, (int)np, ctx->m4, (int)ctx->nm, (int *)(ctx->d_few + 6 * kFewQueries),
-                        ctx->d_few + 3 * kFewQueries, ctx->st);
+    launch_nn_exact_few(ctx->h_few.dev(), (int)np, ctx->m4, (int)ctx->nm, (int *)(ctx->h_few.dev() + 6 * kFewQueries),
+                        ctx->h_few.dev() + 3 * kFewQueries, ctx->st);
     LAUNCHCHK("nn_exact_few");
     TRY(sync_by_flag(ctx));
     if (y_xyz_out) std::memcpy(y_xyz_out, hy, sizeof(double) * 3 * np);
@@ -2345,7 +2273,7 @@ int icp_get_indices(icp_ctx *ctx, int32_t *idx_out)
     HIPCHK(hipSetDevice(ctx->device));
     const int *src = ctx->idx;
     if (ctx->scene_slot && ctx->scene.n) { // back to the caller's order
-        TRY(grow(ctx, &ctx->s_tmp_idx, &ctx->s_tmp_idx_cap, ctx->scene.n));
+        TRY(ctx->s_tmp_idx.grow(ctx, ctx->scene.n));
         launch_permute_cloud(ctx->s_order, (int)ctx->scene.n, 1, nullptr, nullptr, nullptr, nullptr, ctx->idx, nullptr,
                              nullptr, nullptr, nullptr, ctx->s_tmp_idx, ctx->st);
         LAUNCHCHK("indices_to_file_order");
@@ -2362,12 +2290,7 @@ int icp_set_index_digest(icp_ctx *ctx, size_t cap)
     if (!ctx) return ICP_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     if (cap) {
-        size_t have = ctx->digest ? ctx->digest_cap : 0;
-        if (have < cap) {
-            if (ctx->digest) HIPCHK(hipFree(ctx->digest));
-            ctx->digest = nullptr;
-            HIPCHK(hipMalloc((void **)&ctx->digest, sizeof(unsigned long long) * 3 * cap));
-        }
+        TRY(ctx->digest.grow(ctx, 3 * cap));
         // (on the engine stream: a null-stream hipMemset is not ordered against the non-blocking
         // engine stream and may land in the middle of the next run's digests -- seen once in
         // the 8-context C5 test, a digest 9% short)
@@ -2404,11 +2327,10 @@ int icp_set_cert_audit(icp_ctx *ctx, int enable)
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->st));
     if (!enable) {
-        if (ctx->cert_audit) HIPCHK(hipFree(ctx->cert_audit));
-        ctx->cert_audit = nullptr;
+        HIPCHK(ctx->cert_audit.release());
         return ICP_OK;
     }
-    if (!ctx->cert_audit) HIPCHK(hipMalloc((void **)&ctx->cert_audit, 4 * sizeof(unsigned)));
+    TRY(ctx->cert_audit.grow(ctx, 4));
     return cert_audit_reset(ctx);
 }
 
@@ -2420,8 +2342,8 @@ int icp_bundle_audit(icp_ctx *ctx, int groups, icp_bundle_audit_result *out)
     TRY(ensure_bundle(ctx));
     if (!ctx->b_img || !ctx->b_bctr || !ctx->b_kd_orig || ctx->nb_pad <= 0 || !P.n || !ctx->seeds_valid)
         return fail(ctx, ICP_E_NO_MODEL, "icp_bundle_audit: needs the bundle images and a scene with correspondences");
-    unsigned long long *buf = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, 6 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> buf;
+    TRY(buf.grow(ctx, 6));
     const double inf = INFINITY;
     unsigned long long init[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     std::memcpy(&init[1], &inf, sizeof(double));
@@ -2444,7 +2366,6 @@ int icp_bundle_audit(icp_ctx *ctx, int groups, icp_bundle_audit_result *out)
             out->checked = (long long)h[5];
         }
     }
-    (void)hipFree(buf);
     return rc == ICP_OK ? ICP_OK : fail(ctx, rc, "icp_bundle_audit: HIP error");
 }
 
@@ -2466,16 +2387,17 @@ int icp_sort_pairs(int device, const uint32_t *keys, size_t n, int bits, uint32_
     if (hipSetDevice(device) != hipSuccess) return ICP_E_HIP;
     size_t temp = 0;
     (void)icp::sort_pairs_u32(nullptr, temp, nullptr, nullptr, nullptr, nullptr, (int)n, bits, nullptr);
-    char *buf = nullptr;
+    DevBuf<char> mem;
     const size_t kb = ((n * 4 + 255) & ~(size_t)255);
-    if (hipMalloc(&buf, 3 * kb + temp) != hipSuccess) return ICP_E_HIP;
+    if (mem.grow(nullptr, 3 * kb + temp) != ICP_OK) return ICP_E_HIP;
+    char *buf = mem;
     unsigned *k0 = (unsigned *)buf, *k1 = (unsigned *)(buf + kb);
     int *v1 = (int *)(buf + 2 * kb);
     bool ok = hipMemcpy(k0, keys, n * 4, hipMemcpyHostToDevice) == hipSuccess &&
               icp::sort_pairs_u32(buf + 3 * kb, temp, k0, k1, nullptr, v1, (int)n, bits, nullptr) == hipSuccess &&
               hipMemcpy(order_out, v1, n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
               (!keys_out || hipMemcpy(keys_out, k1, n * 4, hipMemcpyDeviceToHost) == hipSuccess);
-    ok = hipFree(buf) == hipSuccess && ok;
+    ok = mem.release() == hipSuccess && ok;
     return ok ? ICP_OK : ICP_E_HIP;
 }
 
@@ -2485,8 +2407,9 @@ int icp_select_kth(int device, const double *v, size_t n, size_t k, double *out)
     if (hipSetDevice(device) != hipSuccess) return ICP_E_HIP;
     // one allocation: the values, their keys, the bins, the state, the result
     const size_t vb = (n * 8 + 255) & ~(size_t)255, bb = sizeof(unsigned) * icp::kSelectBins;
-    char *buf = nullptr;
-    if (hipMalloc(&buf, 2 * vb + bb + 256 + 256) != hipSuccess) return ICP_E_HIP;
+    DevBuf<char> mem;
+    if (mem.grow(nullptr, 2 * vb + bb + 256 + 256) != ICP_OK) return ICP_E_HIP;
+    char *buf = mem;
     double *dv = (double *)buf;
     unsigned long long *keys = (unsigned long long *)(buf + vb);
     unsigned *bins = (unsigned *)(buf + 2 * vb);
@@ -2498,7 +2421,7 @@ int icp_select_kth(int device, const double *v, size_t n, size_t k, double *out)
         icp::launch_select_kth(keys, (int)n, (unsigned long long)k, state, nullptr, bins, cut, nullptr, nullptr, nullptr);
         ok = hipGetLastError() == hipSuccess && hipMemcpy(out, cut, sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
-    ok = hipFree(buf) == hipSuccess && ok;
+    ok = mem.release() == hipSuccess && ok;
     return ok ? ICP_OK : ICP_E_HIP;
 }
 

@@ -198,13 +198,9 @@ int finish_run(icp_ctx *ctx, double threshold, double *err_trace, icp_result *re
 // the run all-reduces its sums (ranks > 1 or a communicator): error test one iteration late
 bool lag_run(const icp_ctx *ctx) { return ctx->comm != nullptr || ctx->world > 1; }
 
-// `bytes` of mapped, coherent host memory (*h) and its device address (*d)
-template <class T> int mapped_alloc(icp_ctx *ctx, T **h, T **d, size_t bytes)
-{
-    HIPCHK(hipHostMalloc((void **)h, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void **)d, *h, 0));
-    return ICP_OK;
-}
+// entries of a run's mapped trace (the error's; the kept-pairs loop's K, W, K+ and C): at least
+// max_iter, 64 to begin with (the previous run ended with a sync, so a trace too short may go)
+size_t trace_entries(int max_iter) { return (size_t)std::max(max_iter, 64); }
 
 // What one icp_run keeps from its set-up and across its iterations (run_setup builds it; both
 // schedules, the wait side and the drain take it)
@@ -372,7 +368,8 @@ void records_args(const LoopRun &r, SeedArgs &s)
         ctx->bundle_pending || ctx->nb_pad <= 0 || level1_kind(ctx, r.n) != 3 || !bundle_v2())
         return;
     const size_t nslots = bundle2_slots(plan_nn_bundle2(r.n, ctx->nb_pad));
-    if (!ctx->b_qop || ctx->b_qop_cap < nslots * 64 || ctx->b_gop_cap < nslots || ctx->b_gctr_cap < nslots / 32)
+    if (!ctx->b_qop || ctx->b_qop.capacity() < nslots * 64 || ctx->b_gop.capacity() < nslots ||
+        ctx->b_gctr.capacity() < nslots / 32)
         return;
     s.qop = ctx->b_qop;
     s.gop = ctx->b_gop;
@@ -409,11 +406,11 @@ int enqueue_err_step(LoopRun &r, int it, const double *partials = nullptr, bool 
     // (done, iter) straight into mapped host memory, then the slot's ticket
     r.slot_ticket[sl] = ++ctx->flag_ticket;
     if (horn)
-        launch_err_horn_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, ctx->d_flags + 4 * sl,
-                             r.slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace, ctx->c, 1, ctx->amb_count, ctx->st);
+        launch_err_horn_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, ctx->h_flags.dev() + 4 * sl,
+                             r.slot_ticket[sl], ctx->h_iter.dev(), ctx->h_trace.dev(), ctx->c, 1, ctx->amb_count, ctx->st);
     else
-        launch_err_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, ctx->d_flags + 4 * sl,
-                        r.slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace, ctx->st, partials, red_blocks(r.n));
+        launch_err_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, ctx->h_flags.dev() + 4 * sl,
+                        r.slot_ticket[sl], ctx->h_iter.dev(), ctx->h_trace.dev(), ctx->st, partials, red_blocks(r.n));
     LAUNCHCHK("err_step");
     return ICP_OK;
 }
@@ -536,15 +533,15 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     static_assert(2 * kTailMaxBlocks <= 2 * kBlock, "pers_part holds the mid kernel's rows");
     const size_t n = ctx->scene.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
-    TRY(grow(ctx, &ctx->idx, &ctx->idx_cap, n)); // (a fresh context has run no search yet)
-    TRY(grow(ctx, &ctx->pers_part, &ctx->pers_part_cap, (size_t)2 * kBlock * kNumSums));
+    TRY(ctx->idx.grow(ctx, n)); // (a fresh context has run no search yet)
+    TRY(ctx->pers_part.grow(ctx, (size_t)2 * kBlock * kNumSums));
     const bool stamps = run_knobs().persist_stamps; // (ICP_PERSIST_STAMPS)
     if (stamps) {
         const size_t ns = (size_t)2 * kPersistMaxStamps + 2 * kBlock + 8 * kBlock + 2 * kBlock;
-        TRY(grow(ctx, &ctx->pers_stamps, &ctx->pers_stamps_cap, ns));
+        TRY(ctx->pers_stamps.grow(ctx, ns));
         HIPCHK(hipMemsetAsync(ctx->pers_stamps, 0, sizeof(unsigned long long) * ns, ctx->st));
     }
-    TRY(grow(ctx, &ctx->pers_sync, &ctx->pers_sync_cap, kPersistSyncWords));
+    TRY(ctx->pers_sync.grow(ctx, kPersistSyncWords));
     // the barrier words count on from the previous launch of the same grid (no memset launch);
     // zeroed on the first launch, when the grid changes and after an aborted launch
     if (!ctx->pers_sync_valid || ctx->pers_grid != grid) {
@@ -570,7 +567,7 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     a.idx = ctx->idx;
     a.part = ctx->pers_part;
     a.sync = ctx->pers_sync;
-    a.h_abort = ctx->d_flags + 3;
+    a.h_abort = ctx->h_flags.dev() + 3;
     a.N = (double)ctx->np_total;
     a.c0 = ctx->c[0];
     a.c1 = ctx->c[1];
@@ -579,12 +576,12 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     a.max_iter = max_iter;
     a.err_trace = ctx->err_trace_dev;
     a.s_glob = ctx->iter_state;
-    a.h_state = ctx->d_iter_mirror;
-    a.h_trace = ctx->d_trace;
+    a.h_state = ctx->h_iter.dev();
+    a.h_trace = ctx->h_trace.dev();
     a.stamps = stamps ? ctx->pers_stamps : nullptr;
     a.cull = run_knobs().persist_cull; // (ICP_PERSIST_NN=all: every model point for every query, A/B)
     a.epoch_base = ctx->pers_epoch_base;
-    a.h_epochs = ctx->d_flags + 7;
+    a.h_epochs = ctx->h_flags.dev() + 7;
     // (tests: ICP_PERSIST_TEST_ABORT=1 makes the first barrier fail as if a workgroup never came)
     a.test_abort = run_test_knobs().persist_test_abort;
     for (int k = 0; k < 3; ++k) a.m0[k] = ctx->model_host[k];
@@ -597,11 +594,11 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
             launch_run_init(ctx->iter_state, ctx->amb_count, ctx->st);
             TRY(nn_search_begin(ctx, P, n, false, nullptr, nullptr, false, nullptr, &ctx->iter_state->done));
         }
-        TRY(grow(ctx, &ctx->mid_q4, &ctx->mid_q4_cap, 4 * n));
-        TRY(grow(ctx, &ctx->mid_res, &ctx->mid_res_cap, n));
-        TRY(grow(ctx, &ctx->mid_perm, &ctx->mid_perm_cap, n));
+        TRY(ctx->mid_q4.grow(ctx, 4 * n));
+        TRY(ctx->mid_res.grow(ctx, n));
+        TRY(ctx->mid_perm.grow(ctx, n));
         const size_t ob = mid_order_scratch_bytes((int)n);
-        TRY(grow(ctx, (char **)&ctx->mid_cnt, &ctx->mid_cnt_cap, ob));
+        TRY(ctx->mid_cnt.grow(ctx, ob));
         if (launch_mid_order(P.x, P.y, P.z, (int)n, ctx->m_lo, ctx->m_hi, ctx->mid_cnt, ob, ctx->mid_perm, ctx->st))
             return fail(ctx, ICP_E_HIP, "icp_run: the mid-size search order (radix sort) failed");
         LAUNCHCHK("mid_order");
@@ -651,19 +648,6 @@ int run_persistent(icp_ctx *ctx, int grid, size_t lds, bool mid, int max_iter, d
     ctx->stats.persistent_runs += 1;
     ctx->stats.last_filter = ICP_FILTER_ONE_LAUNCH;
     return finish_run(ctx, threshold, err_trace, res, wall0);
-}
-
-// a mapped trace of T (the kept-pairs loop's K, W, K+ and C) of at least max_iter entries
-template <class T> int grow_trace(icp_ctx *ctx, T **h, T **d, size_t *cap, int max_iter)
-{
-    if (*cap >= (size_t)std::max(max_iter, 1)) return ICP_OK;
-    if (*h) HIPCHK(hipHostFree(*h)); // (the previous run ended with a sync)
-    *h = nullptr;
-    *cap = 0;
-    const size_t want = (size_t)std::max(max_iter, 64);
-    TRY(mapped_alloc(ctx, h, d, sizeof(T) * want));
-    *cap = want;
-    return ICP_OK;
 }
 
 // icp_run over the kept pairs: the max-correspondence-distance gate (icp_set_max_distance; kernels
@@ -737,26 +721,26 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     const int width = kept_width(plane, robust != 0);
     const bool ranks = lag_run(ctx);
     const int nb = red_blocks(n);
-    TRY(grow(ctx, &ctx->kept_mask, &ctx->kept_mask_cap, (n + 63) / 64));
-    if (gated) TRY(grow(ctx, &ctx->gate_flags, &ctx->gate_flags_cap, n));
-    TRY(grow(ctx, &ctx->kept_part, &ctx->kept_part_cap, (size_t)kRedMaxBlocksCap * kRobustPlaneSums));
-    if (!ctx->kept_state) HIPCHK(hipMalloc((void **)&ctx->kept_state, sizeof(GateState)));
-    if (!ctx->h_kept) TRY(mapped_alloc(ctx, &ctx->h_kept, &ctx->d_kept_mirror, sizeof(GateState)));
-    TRY(grow_trace(ctx, &ctx->h_ktrace, &ctx->d_ktrace, &ctx->ktrace_cap, max_iter));
+    TRY(ctx->kept_mask.grow(ctx, (n + 63) / 64));
+    if (gated) TRY(ctx->gate_flags.grow(ctx, n));
+    TRY(ctx->kept_part.grow(ctx, (size_t)kRedMaxBlocksCap * kRobustPlaneSums));
+    TRY(ctx->kept_state.grow(ctx, 1));
+    TRY(ctx->h_kept.grow(ctx, 1));
+    TRY(ctx->h_ktrace.grow(ctx, trace_entries(max_iter)));
     if (robust) {
-        TRY(grow_trace(ctx, &ctx->h_wtrace, &ctx->d_wtrace, &ctx->wtrace_cap, max_iter));
-        TRY(grow_trace(ctx, &ctx->h_ptrace, &ctx->d_ptrace, &ctx->ptrace_cap, max_iter));
+        TRY(ctx->h_wtrace.grow(ctx, trace_entries(max_iter)));
+        TRY(ctx->h_ptrace.grow(ctx, trace_entries(max_iter)));
     }
     if (trim) {
-        TRY(grow_trace(ctx, &ctx->h_ctrace, &ctx->d_ctrace, &ctx->ctrace_cap, max_iter));
-        TRY(grow(ctx, &ctx->trim_keys, &ctx->trim_keys_cap, n));
-        if (!ctx->trim_bins) HIPCHK(hipMalloc((void **)&ctx->trim_bins, sizeof(unsigned) * kSelectBins));
-        if (!ctx->trim_bins_d) HIPCHK(hipMalloc((void **)&ctx->trim_bins_d, sizeof(double) * kSelectBins));
-        if (!ctx->trim_state) HIPCHK(hipMalloc((void **)&ctx->trim_state, sizeof(SelectState)));
-        if (!ctx->trim_cut) HIPCHK(hipMalloc((void **)&ctx->trim_cut, sizeof(double)));
+        TRY(ctx->h_ctrace.grow(ctx, trace_entries(max_iter)));
+        TRY(ctx->trim_keys.grow(ctx, n));
+        TRY(ctx->trim_bins.grow(ctx, kSelectBins));
+        TRY(ctx->trim_bins_d.grow(ctx, kSelectBins));
+        TRY(ctx->trim_state.grow(ctx, 1));
+        TRY(ctx->trim_cut.grow(ctx, 1));
         HIPCHK(hipMemsetAsync(ctx->trim_bins, 0, sizeof(unsigned) * kSelectBins, ctx->st)); // (each pick leaves them zero)
     }
-    if (uniq) TRY(grow(ctx, &ctx->uniq_best, &ctx->uniq_best_cap, ctx->nm));
+    if (uniq) TRY(ctx->uniq_best.grow(ctx, ctx->nm));
     std::memset(ctx->h_kept, 0, sizeof(GateState));
     HIPCHK(hipMemsetAsync(ctx->kept_state, 0, sizeof(GateState), ctx->st));
     IterState *sd = ctx->iter_state;
@@ -800,9 +784,9 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     fold.plane = plane, fold.robust = robust != 0, fold.trim_few = trim_few;
     fold.symm = symm;
     fold.sums = ctx->sums, fold.amb_count = ctx->amb_count;
-    fold.st_dev = sd, fold.h_state = ctx->d_iter_mirror;
-    fold.gate = ctx->kept_state, fold.h_gate = ctx->d_kept_mirror;
-    fold.h_wtrace = ctx->d_wtrace, fold.h_ptrace = ctx->d_ptrace;
+    fold.st_dev = sd, fold.h_state = ctx->h_iter.dev();
+    fold.gate = ctx->kept_state, fold.h_gate = ctx->h_kept.dev();
+    fold.h_wtrace = ctx->h_wtrace.dev(), fold.h_ptrace = ctx->h_ptrace.dev();
     fold.st = ctx->st;
     for (int k = 0; k < 3; ++k) pass.c[k] = fold.c[k] = ctx->c[k];
     const auto moments = [&](bool y_ready, bool do_step) {
@@ -838,7 +822,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                 LAUNCHCHK("select_keys");
                 if (!ranks) {
                     launch_select_kth(ctx->trim_keys, (int)n, (unsigned long long)T, ctx->trim_state, &sd->done, ctx->trim_bins,
-                                      ctx->trim_cut, sd, ctx->d_ctrace, ctx->st);
+                                      ctx->trim_cut, sd, ctx->h_ctrace.dev(), ctx->st);
                     LAUNCHCHK("select_kth");
                 }
                 for (int pass = 0; ranks && pass < kSelectPasses; ++pass) { // (each pass's bins all-reduced before its pick)
@@ -847,7 +831,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
                     LAUNCHCHK("select_bins");
                     TRY(allreduce(ctx, ctx->trim_bins_d, kSelectBins));
                     launch_select_pick(ctx->trim_bins, ctx->trim_bins_d, pass, (unsigned long long)T, ctx->trim_state, &sd->done,
-                                       ctx->trim_cut, sd, ctx->d_ctrace, ctx->st);
+                                       ctx->trim_cut, sd, ctx->h_ctrace.dev(), ctx->st);
                     LAUNCHCHK("select_pick");
                 }
             }
@@ -892,7 +876,7 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
             r.slot_ticket[sl] = ++ctx->flag_ticket;
             const auto err = [&](const double *part, int nblocks, bool do_step) {
                 launch_gated_err(part, nblocks, ctx->sums, do_step, threshold, max_iter, ctx->err_trace_dev, sd, ctx->kept_state,
-                                 ctx->d_ktrace, ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace,
+                                 ctx->h_ktrace.dev(), ctx->h_flags.dev() + 4 * sl, r.slot_ticket[sl], ctx->h_iter.dev(), ctx->h_trace.dev(),
                                  ctx->st);
             };
             err(ctx->partials, nb, !ranks);
@@ -922,16 +906,16 @@ int run_kept(icp_ctx *ctx, int max_iter, double threshold, double *err_trace, ic
     if (gated && r.enqueued > 0) { // (the mapped buffers are the next run's, gated or not)
         ctx->gate_have = true;
         ctx->gate_K = hk.K;
-        ctx->gate_ktrace.assign(ctx->h_ktrace, ctx->h_ktrace + ctx->h_iter->iter);
+        ctx->gate_ktrace.assign(ctx->h_ktrace.get(), ctx->h_ktrace + ctx->h_iter->iter);
     }
     if (trim && r.enqueued > 0) { // (icp_get_trim_trace: the recorded iterations' C)
         ctx->trim_have = true;
-        ctx->trim_ctrace.assign(ctx->h_ctrace, ctx->h_ctrace + ctx->h_iter->iter);
+        ctx->trim_ctrace.assign(ctx->h_ctrace.get(), ctx->h_ctrace + ctx->h_iter->iter);
     }
     if (robust && r.enqueued > 0) { // (icp_get_robust_trace: the recorded iterations' W and K+)
         ctx->robust_have = true;
-        ctx->robust_wtrace.assign(ctx->h_wtrace, ctx->h_wtrace + ctx->h_iter->iter);
-        ctx->robust_ptrace.assign(ctx->h_ptrace, ctx->h_ptrace + ctx->h_iter->iter);
+        ctx->robust_wtrace.assign(ctx->h_wtrace.get(), ctx->h_wtrace + ctx->h_iter->iter);
+        ctx->robust_ptrace.assign(ctx->h_ptrace.get(), ctx->h_ptrace + ctx->h_iter->iter);
     }
     TRY(finish_run(ctx, threshold, err_trace, res, wall0));
     const std::string trimmed = (trim ? " (the trim keeps T = " + std::to_string(T) + " of " + std::to_string(ctx->np_total) +
@@ -983,31 +967,27 @@ int run_setup_buffers(LoopRun &r)
     r.lag = lag_run(ctx);
     r.tk = run_test_knobs();
     DevCloud &P = ctx->scene;
-    TRY(grow(ctx, &ctx->iter_state, &ctx->iter_state_cap, 1));
-    if (!ctx->h_iter) TRY(mapped_alloc(ctx, &ctx->h_iter, &ctx->d_iter_mirror, sizeof(IterState)));
-    if (ctx->trace_cap < (size_t)std::max(r.max_iter, 1)) { // (the previous run ended with a sync)
-        if (ctx->h_trace) HIPCHK(hipHostFree(ctx->h_trace));
-        ctx->trace_cap = (size_t)std::max(r.max_iter, 64);
-        TRY(mapped_alloc(ctx, &ctx->h_trace, &ctx->d_trace, sizeof(double) * ctx->trace_cap));
-    }
+    TRY(ctx->iter_state.grow(ctx, 1));
+    TRY(ctx->h_iter.grow(ctx, 1));
+    TRY(ctx->h_trace.grow(ctx, trace_entries(r.max_iter)));
     std::memset(ctx->h_iter, 0, sizeof(IterState));
     if (!ctx->h_flags) {
-        TRY(mapped_alloc(ctx, &ctx->h_flags, &ctx->d_flags, sizeof(int) * 4 * kRing));
+        TRY(ctx->h_flags.grow(ctx, 4 * kRing));
         std::memset(ctx->h_flags, 0, sizeof(int) * 4 * kRing);
     }
     // seeded f16 searches: each transform writes the next search's seeds (no seed kernel)
     r.fuse_seeds = ctx->nn_mode == ICP_NN_CERTIFIED && level1_kind(ctx, n) >= 2;
     if (r.fuse_seeds) {
-        TRY(grow(ctx, &ctx->seed16, &ctx->seed16_cap, n));
+        TRY(ctx->seed16.grow(ctx, n));
         r.sa.seed16 = ctx->seed16;
         for (int a = 0; a < 3; ++a) r.sa.c[a] = ctx->c[a];
         r.sa.scale = ctx->scale16;
         if (level1_kind(ctx, n) == 3 && bundle_v2()) { // the bundle filter's seed distances too
-            TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
+            TRY(ctx->b_seedd.grow(ctx, n));
             r.sa.seedd = ctx->b_seedd;
         }
     }
-    TRY(grow(ctx, &ctx->err_trace_dev, &ctx->err_trace_cap, (size_t)(r.max_iter > 0 ? r.max_iter : 1)));
+    TRY(ctx->err_trace_dev.grow(ctx, (size_t)(r.max_iter > 0 ? r.max_iter : 1)));
     while (ctx->iter_ev.size() < 5 * (size_t)kRing) { // (nn begin, nn end, -, all-reduce begin, end) per slot
         hipEvent_t e;
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
@@ -1047,7 +1027,7 @@ int run_setup_policy(LoopRun &r)
     if (want_slot_order(ctx, n)) TRY(scene_to_slot_order(ctx));
     if (ctx->scene_slot && ctx->nn_variant == ICP_NN_VARIANT_GRID && ctx->nn_mode == ICP_NN_CERTIFIED && !r.sa.seedd) {
         // the grid variant's seeded searches read the transform's seed distances too
-        TRY(grow(ctx, &ctx->b_seedd, &ctx->b_seedd_cap, n));
+        TRY(ctx->b_seedd.grow(ctx, n));
         r.sa.seedd = ctx->b_seedd;
     }
     r.digest_order = ctx->scene_slot ? ctx->s_order : nullptr;
@@ -1113,9 +1093,9 @@ int run_setup_steps(LoopRun &r, bool no_tail)
     // iteration's moments fold folds them too (launch_reduce_pair: one launch fewer an iteration,
     // the same bits); the last iteration folds its own before the final all-reduce
     r.err_pair = k.err_pair && r.lag && red_blocks(n) > 1 && !r.fused_steps && !r.fused_moments;
-    if (r.err_pair) TRY(grow(ctx, &ctx->err_part, &ctx->err_part_cap, (size_t)kRedMaxBlocksCap));
+    if (r.err_pair) TRY(ctx->err_part.grow(ctx, (size_t)kRedMaxBlocksCap));
     if ((r.fused_steps || r.fused_moments) && !ctx->fold_ticket) {
-        HIPCHK(hipMalloc((void **)&ctx->fold_ticket, 2 * sizeof(unsigned)));
+        TRY(ctx->fold_ticket.grow(ctx, 2));
         HIPCHK(hipMemsetAsync(ctx->fold_ticket, 0, 2 * sizeof(unsigned), ctx->st));
     }
     // mid-size single-rank runs: iterations >= 2 end in ONE fused launch (moments ... error step)
@@ -1125,11 +1105,11 @@ int run_setup_steps(LoopRun &r, bool no_tail)
                    n > (size_t)kRedSingle && r.tail_blocks <= kTailMaxBlocks && r.tail_blocks <= ctx->n_cu * 3 / 4;
     r.seeds_at_start = ctx->seeds_valid;
     if (r.fused_tail) {
-        TRY(grow(ctx, &ctx->tail_part, &ctx->tail_part_cap, (size_t)19 * kTailMaxBlocks));
-        TRY(grow(ctx, &ctx->tail_sync, &ctx->tail_sync_cap, kPersistSyncWords));
+        TRY(ctx->tail_part.grow(ctx, (size_t)19 * kTailMaxBlocks));
+        TRY(ctx->tail_sync.grow(ctx, kPersistSyncWords));
         HIPCHK(hipMemsetAsync(ctx->tail_sync, 0, kPersistSyncWords * sizeof(unsigned), ctx->st));
         ctx->h_flags[11] = 0; // its barriers' abort word (mapped host)
-        TRY(grow(ctx, &ctx->tail_backup, &ctx->tail_backup_cap, n * (3 * sizeof(double) + sizeof(float4) + sizeof(int))));
+        TRY(ctx->tail_backup.grow(ctx, n * (3 * sizeof(double) + sizeof(float4) + sizeof(int))));
         TRY(tail_snapshot(ctx, n, r.seeds_at_start, false));
     }
     if (ctx->digest_cap) HIPCHK(hipMemsetAsync(ctx->digest, 0, sizeof(unsigned long long) * 3 * ctx->digest_cap, ctx->st));
@@ -1157,8 +1137,8 @@ int run_setup_canon(LoopRun &r)
     IterState *sd = ctx->iter_state;
     r.canon = k.canon && ctx->scene_slot && n > 0;
     if (r.canon) {
-        TRY(grow(ctx, &ctx->canon_rowbuf, &ctx->canon_rowbuf_cap, (size_t)canon_strands(n) * kCanonCols)); // (rows, or strands)
-        if (!ctx->h_far) HIPCHK(hipHostMalloc((void **)&ctx->h_far, sizeof(int), hipHostMallocDefault));
+        TRY(ctx->canon_rowbuf.grow(ctx, (size_t)canon_strands(n) * kCanonCols)); // (rows, or strands)
+        TRY(ctx->h_far.grow(ctx, 1));
         // the first iteration's shift of p: the scene's centroid (all ranks'), where run_init put the
         // model's centre c -- a scene far from the model would otherwise cancel (D / sigma)^2 of the
         // one-pass moments' precision (the shift of y follows the first search: the mean of a sample
@@ -1177,7 +1157,7 @@ int run_setup_canon(LoopRun &r)
     // ICP_CERT=0: every query walks (A/B); ICP_CERT_TWO=0: the one-point form;
     // ICP_CERT_SKIN: the walk's extra radius in grid cells (default 0.25).
     if (r.canon && k.cert && k.grid_iter && ctx->g_pts32) {
-        TRY(grow(ctx, &ctx->cert_state, &ctx->cert_state_cap, n));
+        TRY(ctx->cert_state.grow(ctx, n));
         // the counts accumulate on the device over the runs of one scene size (64-bit: no wrap),
         // read when the stats are; another size folds them into the stats first (a synchronisation
         // the runs of a registration loop do not pay: 60 us a run at C4, profiles/r06/r06fold3)
@@ -1185,7 +1165,7 @@ int run_setup_canon(LoopRun &r)
         // (3 words a strand: the two counts, then walk_last and the order table, an int each)
         if (ctx->cert_counts_rows != crows) {
             TRY(fold_cert_counts(ctx));
-            TRY(grow(ctx, &ctx->cert_counts, &ctx->cert_counts_cap, 3 * (size_t)crows));
+            TRY(ctx->cert_counts.grow(ctx, 3 * (size_t)crows));
             HIPCHK(hipMemsetAsync(ctx->cert_counts, 0, 3 * (size_t)crows * sizeof(ctx->cert_counts[0]), ctx->st));
             ctx->cert_counts_rows = crows;
         }
@@ -1215,12 +1195,12 @@ int run_setup_canon(LoopRun &r)
     r.cs.max_iter = r.max_iter;
     r.cs.err_trace = ctx->err_trace_dev;
     r.cs.s = sd;
-    r.cs.h_state = ctx->d_iter_mirror;
-    r.cs.h_trace = ctx->d_trace;
+    r.cs.h_state = ctx->h_iter.dev();
+    r.cs.h_trace = ctx->h_trace.dev();
     for (int a = 0; a < 3; ++a) r.cs.c[a] = ctx->c[a];
     r.cs.cnt = ctx->amb_count;
     if (!ctx->canon_ticket) {
-        HIPCHK(hipMalloc((void **)&ctx->canon_ticket, sizeof(int)));
+        TRY(ctx->canon_ticket.grow(ctx, 1));
         HIPCHK(hipMemsetAsync(ctx->canon_ticket, 0, sizeof(int), ctx->st));
     }
     r.cs.fold_ticket = ctx->canon_ticket;
@@ -1302,7 +1282,7 @@ int canon_end(LoopRun &r, int it, bool horn, int slot)
     CanonStep &cs = r.cs;
     const int sl = it % kRing;
     r.slot_ticket[sl] = ++ctx->flag_ticket;
-    cs.hflag = ctx->d_flags + 4 * sl;
+    cs.hflag = ctx->h_flags.dev() + 4 * sl;
     cs.ticket = r.slot_ticket[sl];
     const int strands = r.rows_strands; // (the fused kernel wrote the rows as strands)
     r.rows_strands = 0;
@@ -1323,11 +1303,11 @@ int canon_end(LoopRun &r, int it, bool horn, int slot)
     if (tm) HIPCHK(hipEventRecord(ctx->iter_ev[5 * slot + 4], ctx->st));
     if (horn)
         launch_err_horn_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, cs.hflag, cs.ticket,
-                             ctx->d_iter_mirror, ctx->d_trace, ctx->c, 1, ctx->amb_count, ctx->st,
+                             ctx->h_iter.dev(), ctx->h_trace.dev(), ctx->c, 1, ctx->amb_count, ctx->st,
                              r.grid_policy ? 1 : 0);
     else
         launch_err_step(ctx->sums, r.N, r.threshold, r.max_iter, ctx->err_trace_dev, sd, cs.hflag, cs.ticket,
-                        ctx->d_iter_mirror, ctx->d_trace, ctx->st, nullptr, 0);
+                        ctx->h_iter.dev(), ctx->h_trace.dev(), ctx->st, nullptr, 0);
     LAUNCHCHK("err_step");
     return ICP_OK;
 }
@@ -1466,7 +1446,7 @@ int enqueue_canon_first_k1(LoopRun &r, int slot, bool timed)
     icp_ctx *ctx = r.ctx;
     const size_t n = r.n;
     DevCloud &P = ctx->scene, &Y = ctx->Y;
-    TRY(grow(ctx, &ctx->idx, &ctx->idx_cap, n));
+    TRY(ctx->idx.grow(ctx, n));
     launch_nn_grid_cell_seed((int)n, P.x, P.y, P.z, grid_view(ctx), (int)ctx->nm, ctx->idx, nullptr, ctx->st, Y.x, Y.y,
                              Y.z);
     LAUNCHCHK("nn_grid_cell_seed");
@@ -1585,7 +1565,7 @@ int enqueue_tail_small(LoopRun &r)
     r.slot_ticket[sl] = ++ctx->flag_ticket;
     launch_iteration_tail_small(ctx->idx, ctx->m4, P.x, P.y, P.z, (int)r.n, Y.x, Y.y, Y.z, P.f, ctx->sums, r.N, ctx->c,
                                 ctx->amb_count, ctx->iter_state, r.threshold, r.max_iter, ctx->err_trace_dev,
-                                ctx->d_flags + 4 * sl, r.slot_ticket[sl], ctx->d_iter_mirror, ctx->d_trace, ctx->st);
+                                ctx->h_flags.dev() + 4 * sl, r.slot_ticket[sl], ctx->h_iter.dev(), ctx->h_trace.dev(), ctx->st);
     LAUNCHCHK("iteration_tail_small");
     r.ws = SeedState{}; // (it writes no seeds)
     ++r.enqueued;
@@ -1616,7 +1596,7 @@ int enqueue_tail_fused(LoopRun &r)
     ta.part1 = ctx->tail_part + (size_t)18 * kTailMaxBlocks;
     ta.sync = ctx->tail_sync;
     ta.epoch_base = r.tail_epoch;
-    ta.h_abort = ctx->d_flags + 11;
+    ta.h_abort = ctx->h_flags.dev() + 11;
     ta.N = r.N;
     ta.c0 = ctx->c[0];
     ta.c1 = ctx->c[1];
@@ -1626,10 +1606,10 @@ int enqueue_tail_fused(LoopRun &r)
     ta.threshold = r.threshold;
     ta.max_iter = r.max_iter;
     ta.err_trace = ctx->err_trace_dev;
-    ta.hflag = ctx->d_flags + 4 * sl;
+    ta.hflag = ctx->h_flags.dev() + 4 * sl;
     ta.ticket = r.slot_ticket[sl];
-    ta.h_state = ctx->d_iter_mirror;
-    ta.h_trace = ctx->d_trace;
+    ta.h_state = ctx->h_iter.dev();
+    ta.h_trace = ctx->h_trace.dev();
     const bool split_err = run_knobs().tail_split_err; // (A/B)
     ta.sums_out = split_err ? ctx->sums : nullptr;
     ta.test_abort = r.tk.tail_test_abort; // (tests: fails the tail's first barrier -- the rerun path)
@@ -1720,10 +1700,10 @@ int enqueue_steps(LoopRun &r, int slot, bool timed)
         ef.threshold = r.threshold;
         ef.max_iter = r.max_iter;
         ef.err_trace = ctx->err_trace_dev;
-        ef.hflag = ctx->d_flags + 4 * sl;
+        ef.hflag = ctx->h_flags.dev() + 4 * sl;
         ef.hticket = r.slot_ticket[sl];
-        ef.h_state = ctx->d_iter_mirror;
-        ef.h_trace = ctx->d_trace;
+        ef.h_state = ctx->h_iter.dev();
+        ef.h_trace = ctx->h_trace.dev();
     }
     launch_transform_err_dev(P.x, P.y, P.z, Y.x, Y.y, Y.z, (int)n, &sd->xf, &sd->done, r.need_p32 ? P.f : nullptr,
                              r.err_pair ? ctx->err_part : red_target(ctx, n, ctx->sums + kSumErr), sa_t, ctx->st, ef);

@@ -74,7 +74,7 @@ EXPORTED = [
     "icp_ensure_model", "icp_subtract_col", "icp_get_indices", "icp_set_index_digest",
     "icp_get_index_digest", "icp_set_cert_audit", "icp_set_run_mode", "icp_set_nn_rule",
     "icp_get_comm_info", "icp_set_bundle_counters", "icp_get_bundle_counters", "icp_get_model_order",
-    "icp_bundle_audit", "icp_sort_pairs", "icp_get_grid",
+    "icp_bundle_audit", "icp_sort_pairs", "icp_get_grid", "icp_debug_live_buffers",
     "icp_set_max_distance", "icp_get_inliers", "icp_get_inlier_trace",
     "icp_set_metric", "icp_set_model_normals", "icp_set_model_normals_device",
     "icp_model_knn", "icp_estimate_model_normals", "icp_get_model_normals",
@@ -214,6 +214,8 @@ def lib() -> C.CDLL:
     L.icp_get_grid.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.icp_sort_pairs.argtypes = [C.c_int, C.POINTER(C.c_uint32), sz, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.icp_debug_live_buffers.argtypes = []
+    L.icp_debug_live_buffers.restype = C.c_longlong
     L.icp_set_index_digest.argtypes = [vp, sz]
     L.icp_get_index_digest.argtypes = [vp, C.POINTER(C.c_uint64), sz]
     L.icp_set_cert_audit.argtypes = [vp, C.c_int]
@@ -320,6 +322,11 @@ def sort_pairs(keys, bits: int, device: int = 0):
     if rc != ICP_OK:
         raise ICPError(rc, strerror(rc))
     return order, out
+
+
+def debug_live_buffers() -> int:
+    """The blocks of device and pinned host memory the library holds now (icp_debug_live_buffers)."""
+    return int(lib().icp_debug_live_buffers())
 
 
 def select_kth(values, k: int, device: int = 0) -> float:
